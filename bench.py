@@ -11,11 +11,16 @@ crops x AUG_K=2 views x flip (+ coarse inference on view 0's pyramid), [C] stude
 [D] weighted loss, backward, (RCCL all-reduce of the flat student gradient when N > 1), SGD, [E] EMA teacher.
 img = one source crop consumed per step (2 labeled + 2 unlabeled = 4 per GPU per step); weak scaling.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel = the large-tile convolution kernel with the most
-event-bracketed time in a separate leg: conv3x3_strip_kernel or conv_fwd_glds_kernel<128,128>, on the matrix pipe through
-the two-term fp16 split -- 3 MFMA products per multiply, peak 2500 / 3 TFLOP/s; the 6-product line of the 3-term bf16
-split and the fp32-input MFMA peak are quoted beside it) and `cpu_baseline` (the CPU oracle timed on this node's host
-cores on a bounded sample; baseline only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the headline figure
+(`value` imgs/sec, `ms_per_step`, per-step spread, losses of the last step).  `--full` adds, after the timed steps,
+`roofline` (dominant kernel = the large-tile convolution kernel with the most event-bracketed time in a separate leg:
+conv3x3_strip_kernel or conv_fwd_glds_kernel<128,128>, on the matrix pipe through the two-term fp16 split -- 3 MFMA products
+per multiply, peak 2500 / 3 TFLOP/s; the 6-product line of the 3-term bf16 split and the fp32-input MFMA peak are quoted
+beside it; the convolution family, the single-stream leg), `forward_leg`, `fp32_mfma_mode` and `cpu_baseline` (the CPU
+oracle timed on this node's host cores on a bounded sample; baseline only).
+
+`--dump-outputs DIR` writes what the last timed step computed as float32 .npy files (see dump_outputs); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -42,10 +47,12 @@ N_LAB, N_UNLAB, N_INST = 2, 2, 12
 # iterations, and the trainer -- like the reference's bare `except` (MTtrainer.py:247-275) -- skips the whole consistency
 # branch of such a step: 36 instead of 47 ms, i.e. work missing from the timed region (seen as a bimodal per-step series,
 # mmt-psm_amd/tools/step_series.py).  A real run past START_MT has detections on every image.  The bench therefore
-# freezes the drift: the same optimizer / EMA kernels run on the same bytes every step, with a learning rate that keeps
+# freezes the drift: the same optimizer / EMA kernels run on the same bytes every step, with a learning rate of 0 that keeps
 # the weights where the data-dependent sizes (proposals, detections, pseudo instances) are those of step 0, and it
-# counts the steps whose consistency branch was skipped (must be 0) in the JSON line.
-BENCH_BASE_LR = 1e-7
+# counts the steps whose consistency branch was skipped (must be 0) in the JSON line.  Exactly 0: at any positive rate the
+# order of the backward pass's float atomics leaves the weights an ulp apart from run to run, near-tied discrete decisions
+# of later steps (NMS, samplers) amplify that, and two runs with the same arguments would not compute the same last step.
+BENCH_BASE_LR = 0.0
 
 
 def build(device, rank, irnet=False, crop=None, n_inst=None, base_lr=None, n_lab=None, n_unlab=None, supervised=False):
@@ -116,6 +123,28 @@ def build(device, rank, irnet=False, crop=None, n_inst=None, base_lr=None, n_lab
                 [to_image_list(list(u), cfg.DATALOADER.SIZE_DIVISIBILITY) for u in unl])
 
     return cfg, trainer, batch
+
+
+DUMP_SAMPLE = 1 << 21   # elements of each flat vector written by --dump-outputs (fixed, seeded positions)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(d, trainer, losses):
+    """--dump-outputs DIR: what the last timed step returned and left behind, as float32 .npy files.  Every loss of the dict
+    train_step returned (<key>.npy, 0-d), and, at DUMP_SAMPLE fixed positions drawn with DUMP_SEED (every element when the
+    vector is shorter), the flat student gradient of that step (student_grad.npy), the student after its SGD update
+    (student_params.npy) and the teacher after its EMA update (teacher_params.npy): about 25 MB in all."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(d, k + ".npy"), v.detach().float().cpu().numpy())
+    for name, t in (("student_grad", trainer.flat_s.grad), ("student_params", trainer.flat_s.data),
+                    ("teacher_params", trainer.flat_t.data)):
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            t = t[torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values.to(t.device)]
+        np.save(os.path.join(d, name + ".npy"), t.float().cpu().numpy())
 
 
 def cpu_baseline():
@@ -356,8 +385,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)    # 10 warm-up + 50 timed steps
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--profile-steps", type=int, default=10, help="steps of the separate event-bracketed leg (roofline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the measurements beyond the headline figure: the "
+                    "event-bracketed roofline leg, the single-stream, convolution-family, forward and fp32-input MFMA legs and the "
+                    "CPU baseline (off: set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--profile-steps", type=int, default=10, help="steps of the separate event-bracketed leg (roofline; --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--irnet", action="store_true", help="IR-Net on (BASELINE configs[4] in fp32); not the headline line")
     ap.add_argument("--f16x2", action="store_true", help="(default since round 3; kept for old command lines) convolutions on the "
                     "two-term fp16 split: 3 matrix products per multiply instead of 6")
@@ -373,6 +406,8 @@ def main():
         raise SystemExit("bench.py needs an MI355X: the HIP library is the only compute path (no CPU fallback)")
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` outside a launcher: start the N ranks here (one process per GPU, RCCL over xGMI) --
         # the line this process would otherwise print is a one-rank number labelled with a flag nobody read
@@ -459,6 +494,65 @@ def main():
         t = torch.tensor([skipped], dtype=torch.int64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         skipped = int(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, losses)
+
+    def headline():
+        """the line's figures from the timed steps alone (rank 0)"""
+        imgs_per_step = per_gpu * world
+        value = imgs_per_step * args.steps / dt          # whole-job throughput over the K bracketed steps
+        import statistics
+        med = statistics.median(per_step)                 # per-step durations from the step-boundary events (rank 0)
+        out = {
+            "metric": "imgs/sec (student+teacher step, 1000x1000, AUG_K=2)",
+            "value": round(value, 4), "unit": "imgs/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "median_ms_per_step": round(med, 3),
+            "p10_p90_ms_per_step": [round(sorted(per_step)[len(per_step) // 10], 3),
+                                    round(sorted(per_step)[(len(per_step) * 9) // 10 - (1 if len(per_step) >= 10 else 0)], 3)],
+            "imgs_per_sec_at_median": round(imgs_per_step / (med * 1e-3), 4),
+            "higher_is_better": True, "scaling": "weak",
+            "library_calls_per_step": round(c_calls, 1),   # interpreter -> C-ABI calls of both launch-issuing threads (VERDICT r3 #7)
+            "rccl_ranks": dist.get_world_size() if use_dist else 0,
+            "backend": (dist.get_backend() + " (RCCL)") if use_dist else "none (single process, no process group)",
+            "vs_baseline": None, "dtype": "bf16" if mode == 1 else "f32", "data": "synthetic",
+            "config": {"workload": ("Mask R-CNN R50-FPN supervised-only step (BASELINE configs[1]): per GPU 4 labeled 1000x1000x3 "
+                                    "crops, MT.LAMBDA 0, fwd+bwd+SGD, fp32, IR-Net %s" if args.supervised else
+                                    "MMT-PSM mean-teacher step (BASELINE configs[2]; configs[3] when n_gpus>1): per GPU 2 "
+                                    "labeled + 2 unlabeled 1000x1000x3 crops, AUG_K=2 + flip, AUG_S=1, MT.LAMBDA 5, "
+                                    "PSM+MGD, EMA teacher, fwd+bwd+SGD, R50-FPN fp32, IR-Net %s") % (
+                                       "ON (relation NMS + mask relation; RELATION_NMS.LOSS 0.01)" if args.irnet else "off"),
+                       "image_forwards_per_step_per_gpu": 4 if args.supervised else 12, "parallelism": "dp%d" % world,
+                       "base_lr": BENCH_BASE_LR, "consistency_branch_skipped_steps": skipped,
+                       "losses": {k: round(float(v.detach()), 5) for k, v in losses.items()}},
+        }
+        return out
+
+    def describe(out):
+        """what the line says about the arithmetic and the exchange, after every leg that ran"""
+        out["config"]["conv_arithmetic"] = ARITH_BF16_STORAGE if _hip.bf16_storage() else ARITH[mode]
+        if _hip.F16X2 and mode == 3:
+            out["config"]["conv_arithmetic"] = (
+                "fp32 tensors; products on the fp16 matrix pipe as a two-term fp16 split of both operands, each tensor scaled by a "
+                "power of two derived on the device from its largest magnitude (3 MFMAs per multiply, fp32 accumulate): error vs "
+                "fp64 <= the 3-term bf16 split's and the fp32-input MFMA's (profiles/r03_precision_f16x2.txt); tensors whose crest "
+                "factor max/mean exceeds 2^17 fall back to the 3-term bf16 split (6 MFMAs) per consuming site; "
+                "MMT_F16X2=0 / --bf16x3 selects that split everywhere, MMT_CONV_PRECISION=0 the fp32-input MFMA")
+            out["config"]["f16_split_launches"] = dict(_hip.F16_STATS)
+        if use_dist and getattr(trainer._bucketed, "last_trace", None) is not None:
+            # MMT_DIST_TRACE=1: when each piece of the flat gradient went out and arrived, on the device clock of the last step
+            out["dist_trace"] = dict(trainer._bucketed.last_trace, backend=dist.get_backend(), world=world,
+                                     teacher_stream_priority=trainer.t_stream.priority if trainer.t_stream is not None else None,
+                                     grad_mbytes=round(trainer.flat_s.grad.numel() * 4 / 1e6, 1))
+        return out
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(describe(headline())), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return
+
+    # --full: the legs below run after the timed steps and never enter the headline figures
     nxt = args.warmup + args.steps
     npf = max(1, min(args.profile_steps, args.steps))
     if use_dist:   # the bracketed leg also records when each piece of the gradient went out and arrived (`dist_trace`):
@@ -562,10 +656,6 @@ def main():
         _hip.set_conv_precision(mode)
 
     if rank == 0:
-        imgs_per_step = per_gpu * world
-        value = imgs_per_step * args.steps / dt          # whole-job throughput over the K bracketed steps
-        import statistics
-        med = statistics.median(per_step)                 # per-step durations from the step-boundary events (rank 0)
         flops = sum(p[0] for p in prof)
         ms = sum(p[1].elapsed_time(p[2]) for p in prof)
         ach = flops / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
@@ -587,30 +677,9 @@ def main():
                                 "mmt-psm_amd/tools/make_profiles.sh" % (str(tj.get("csrc_sha1"))[:12], csrc_sha1()[:12]))
         except Exception:
             pass
-        out = {
-            "metric": "imgs/sec (student+teacher step, 1000x1000, AUG_K=2)",
-            "value": round(value, 4), "unit": "imgs/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "median_ms_per_step": round(med, 3),
-            "p10_p90_ms_per_step": [round(sorted(per_step)[len(per_step) // 10], 3),
-                                    round(sorted(per_step)[(len(per_step) * 9) // 10 - (1 if len(per_step) >= 10 else 0)], 3)],
-            "imgs_per_sec_at_median": round(imgs_per_step / (med * 1e-3), 4),
-            "higher_is_better": True, "scaling": "weak",
-            "library_calls_per_step": round(c_calls, 1),   # interpreter -> C-ABI calls of both launch-issuing threads
-            "rccl_ranks": dist.get_world_size() if use_dist else 0,
-            "backend": (dist.get_backend() + " (RCCL)") if use_dist else "none (single process, no process group)",
-            "vs_baseline": None, "dtype": "bf16" if mode == 1 else "f32", "data": "synthetic",
-            "config": {"workload": ("Mask R-CNN R50-FPN supervised-only step (BASELINE configs[1]): per GPU 4 labeled 1000x1000x3 "
-                                    "crops, MT.LAMBDA 0, fwd+bwd+SGD, fp32, IR-Net %s" if args.supervised else
-                                    "MMT-PSM mean-teacher step (BASELINE configs[2]; configs[3] when n_gpus>1): per GPU 2 "
-                                    "labeled + 2 unlabeled 1000x1000x3 crops, AUG_K=2 + flip, AUG_S=1, MT.LAMBDA 5, "
-                                    "PSM+MGD, EMA teacher, fwd+bwd+SGD, R50-FPN fp32, IR-Net %s") % (
-                                       "ON (relation NMS + mask relation; RELATION_NMS.LOSS 0.01)" if args.irnet else "off"),
-                       "image_forwards_per_step_per_gpu": 4 if args.supervised else 12, "parallelism": "dp%d" % world,
-                       "base_lr": BENCH_BASE_LR, "consistency_branch_skipped_steps": skipped,
-                       "losses": {k: round(float(v.detach()), 5) for k, v in losses.items()}},
-            "roofline": dict(roofline(mode, ach, traffic, alg_bytes, flops, ms, prof, dtp, npf, dom),
-                             **({"traffic_note": traffic_note} if traffic_note else {})),
-        }
+        out = headline()
+        out["roofline"] = dict(roofline(mode, ach, traffic, alg_bytes, flops, ms, prof, dtp, npf, dom),
+                               **({"traffic_note": traffic_note} if traffic_note else {}))
         pres = [q[5] for q in prof if len(q) > 5 and q[5] is not None]
         if pres:
             # launches whose input planes no producing epilogue had written: one split pass over the input in front of them
@@ -660,15 +729,7 @@ def main():
             out["roofline"]["unsplit_k_launches"] = {
                 "launches_per_step": len(uns) // max(npf, 1), "achieved": round(fu / (mu * 1e-3) / 1e12, 2),
                 "frac": round(fu / (mu * 1e-3) / 1e12 / out["roofline"]["peak"], 4), "avg_launch_ms": round(mu / len(uns), 4)}
-        out["config"]["conv_arithmetic"] = ARITH_BF16_STORAGE if _hip.bf16_storage() else ARITH[mode]
-        if _hip.F16X2 and mode == 3:
-            out["config"]["conv_arithmetic"] = (
-                "fp32 tensors; products on the fp16 matrix pipe as a two-term fp16 split of both operands, each tensor scaled by a "
-                "power of two derived on the device from its largest magnitude (3 MFMAs per multiply, fp32 accumulate): error vs "
-                "fp64 <= the 3-term bf16 split's and the fp32-input MFMA's (profiles/r03_precision_f16x2.txt); tensors whose crest "
-                "factor max/mean exceeds 2^17 fall back to the 3-term bf16 split (6 MFMAs) per consuming site; "
-                "MMT_F16X2=0 / --bf16x3 selects that split everywhere, MMT_CONV_PRECISION=0 the fp32-input MFMA")
-            out["config"]["f16_split_launches"] = dict(_hip.F16_STATS)
+        describe(out)
         if single is not None:
             # `achieved` above is bracketed on the launch stream while the teacher's stream shares the GPU; this is the same
             # kernel, same shapes, in a single-stream run of the same step (MMT_OVERLAP_TEACHER=0)
@@ -680,11 +741,6 @@ def main():
             out["forward_leg"] = fwd_leg
         if ref_fp32 is not None:
             out["fp32_mfma_mode"] = ref_fp32
-        if use_dist and getattr(trainer._bucketed, "last_trace", None) is not None:
-            # MMT_DIST_TRACE=1: when each piece of the flat gradient went out and arrived, on the device clock of the last step
-            out["dist_trace"] = dict(trainer._bucketed.last_trace, backend=dist.get_backend(), world=world,
-                                     teacher_stream_priority=trainer.t_stream.priority if trainer.t_stream is not None else None,
-                                     grad_mbytes=round(trainer.flat_s.grad.numel() * 4 / 1e6, 1))
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)

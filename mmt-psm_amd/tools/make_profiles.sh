@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $OUT/bench_default.json 2> /tmp/err_default.txt
+python $R/bench.py --full > $OUT/bench_default.json 2> $TMPDIR/err_default.txt
 export MMT_BENCH_NO_FP32_LEG=1 MMT_BENCH_NO_FAMILY_LEG=1   # (the profiled runs hold the step alone)
 reduce() {  # csv of a --pmc pass -> per-kernel table of one counter
 python3 - "$1" "$2" <<'PY'
@@ -29,21 +29,21 @@ for TAG in f16x2 bf16x3 mode0; do
   unset MMT_CONV_PRECISION MMT_F16X2
   [ $TAG = bf16x3 ] && export MMT_F16X2=0
   [ $TAG = mode0 ] && export MMT_CONV_PRECISION=0
-  rm -rf /tmp/ps$TAG
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps$TAG -- python $R/bench.py --no-cpu-baseline --steps 5 --warmup 2 --profile-steps 5 > $OUT/bench_under_rocprof_$TAG.json 2> /tmp/err_$TAG.txt
-  cp $(find /tmp/ps$TAG -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_$TAG.csv
+  rm -rf $TMPDIR/ps$TAG
+  rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/ps$TAG -- python $R/bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --profile-steps 5 > $OUT/bench_under_rocprof_$TAG.json 2> $TMPDIR/err_$TAG.txt
+  cp $(find $TMPDIR/ps$TAG -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_$TAG.csv
   if [ $TAG != bf16x3 ]; then
     for C in FETCH_SIZE WRITE_SIZE; do
-      rm -rf /tmp/pp
-      rocprofv3 --kernel-trace --pmc $C --output-format csv -d /tmp/pp -- python $R/bench.py --no-cpu-baseline --steps 2 --warmup 1 --profile-steps 1 > /dev/null 2>&1
-      reduce $(find /tmp/pp -name "*counter_collection.csv" | head -1) $C > $OUT/pmc_${C}_by_kernel_$TAG.csv
+      rm -rf $TMPDIR/pp
+      rocprofv3 --kernel-trace --pmc $C --output-format csv -d $TMPDIR/pp -- python $R/bench.py --full --no-cpu-baseline --steps 2 --warmup 1 --profile-steps 1 > /dev/null 2>&1
+      reduce $(find $TMPDIR/pp -name "*counter_collection.csv" | head -1) $C > $OUT/pmc_${C}_by_kernel_$TAG.csv
     done
   fi
 done
 unset MMT_CONV_PRECISION MMT_F16X2
-rm -rf /tmp/pq
-MMT_OVERLAP_TEACHER=0 MMT_WGRAD_STREAM=0 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA --output-format csv -d /tmp/pq -- python $R/bench.py --no-cpu-baseline --steps 2 --warmup 1 --profile-steps 1 > /dev/null 2>&1
-python3 - $(find /tmp/pq -name "*counter_collection.csv" | head -1) > $OUT/pmc_mfma_busy.txt <<'PY'
+rm -rf $TMPDIR/pq
+MMT_OVERLAP_TEACHER=0 MMT_WGRAD_STREAM=0 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA --output-format csv -d $TMPDIR/pq -- python $R/bench.py --full --no-cpu-baseline --steps 2 --warmup 1 --profile-steps 1 > /dev/null 2>&1
+python3 - $(find $TMPDIR/pq -name "*counter_collection.csv" | head -1) > $OUT/pmc_mfma_busy.txt <<'PY'
 import csv, sys, collections
 agg = collections.defaultdict(lambda: collections.defaultdict(float))
 for r in csv.DictReader(open(sys.argv[1])):
@@ -66,11 +66,11 @@ python $R/mmt-psm_amd/tools/host_phases.py 2>/dev/null | tail -36 > $OUT/host_de
 python $R/mmt-psm_amd/tools/op_sites.py 2>/dev/null | grep -v amdgpu.ids | head -60 > $OUT/library_op_sites.txt
 python $R/mmt-psm_amd/tools/call_hist.py 5 2>/dev/null | grep -v amdgpu.ids > $OUT/call_hist.txt
 STEPS=120 python $R/mmt-psm_amd/tools/step_series.py 2>/dev/null | tail -3 > $OUT/step_series_bench.txt
-python $R/bench.py --bf16x3 --no-cpu-baseline > $OUT/bench_bf16x3.json 2>/dev/null
-python $R/bench.py --bf16 --no-cpu-baseline > $OUT/bench_bf16.json 2>/dev/null
-python $R/bench.py --bf16 --irnet --no-cpu-baseline > $OUT/bench_bf16_irnet.json 2>/dev/null
-python $R/bench.py --irnet --no-cpu-baseline > $OUT/bench_irnet.json 2>/dev/null
-MMT_FORCE_DIST=1 MMT_DIST_TRACE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29751 $R/bench.py --gpus 1 --steps 10 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' > $OUT/bench_rccl_world1.json
+python $R/bench.py --full --bf16x3 --no-cpu-baseline > $OUT/bench_bf16x3.json 2>/dev/null
+python $R/bench.py --full --bf16 --no-cpu-baseline > $OUT/bench_bf16.json 2>/dev/null
+python $R/bench.py --full --bf16 --irnet --no-cpu-baseline > $OUT/bench_bf16_irnet.json 2>/dev/null
+python $R/bench.py --full --irnet --no-cpu-baseline > $OUT/bench_irnet.json 2>/dev/null
+MMT_FORCE_DIST=1 MMT_DIST_TRACE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29751 $R/bench.py --full --gpus 1 --steps 10 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' > $OUT/bench_rccl_world1.json
 python $R/mmt-psm_amd/tools/clock_under_load.py 2>/dev/null | grep -v amdgpu.ids > $OUT/clock_under_load.txt
 python $R/mmt-psm_amd/tools/bench_f16x2.py 2>/dev/null | grep -v amdgpu.ids > $OUT/precision_f16x2.txt
 python $R/mmt-psm_amd/tools/bench_f16x2_glds.py 2>/dev/null | grep -v amdgpu.ids >> $OUT/precision_f16x2.txt

@@ -23,13 +23,13 @@ def is_library(n):
 
 out = ["# Round 6 -- profiles of `python bench.py` on 1 x MI355X (state at the end of the round)", "",
        "Produced by `mmt-psm_amd/tools/make_profiles.sh` (GPU box) + `mmt-psm_amd/tools/summarize_profiles.py`. Files: "
-       "`r06_bench_default.json` (un-profiled `python bench.py`: 10 warm-up + 50 timed steps, median next to the mean, event brackets "
+       "`r06_bench_default.json` (un-profiled `python bench.py --full`: 10 warm-up + 50 timed steps, median next to the mean, event brackets "
        "in a separate 10-step leg, CPU baseline 1 + 3 steps); per arithmetic `r06_kernel_stats_<tag>.csv` (rocprofv3 --kernel-trace "
-       "--stats of `bench.py --steps 5 --warmup 2 --profile-steps 5 --no-cpu-baseline`), `r06_bench_under_rocprof_<tag>.json` (the line "
+       "--stats of `bench.py --full --steps 5 --warmup 2 --profile-steps 5 --no-cpu-baseline`), `r06_bench_under_rocprof_<tag>.json` (the line "
        "that run printed), `r06_pmc_{FETCH,WRITE}_SIZE_by_kernel_<tag>.csv` (two separate --pmc passes, --kernel-trace only); "
        "`r06_pmc_mfma_busy.txt` (one SQ pass, single-stream); `pmc_traffic.json` = what bench.py reports as roofline.traffic. "
        "Tags: " + "; ".join("**%s** = %s" % kv for kv in ARITH.items()) + ".", ""]
-traffic = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes, --kernel-trace only) of `python bench.py "
+traffic = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes, --kernel-trace only) of `python bench.py --full "
                      "--steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline`; per-kernel tables profiles/r06_pmc_*_by_kernel_*.csv",
            "fetch_correction": 2.0, "csrc_sha1": __import__("importlib").import_module("bench").csrc_sha1(),
            "note": "FETCH_SIZE on gfx950 reports 1/2 of the bytes of a wide coalesced read (MI355X_MICROARCH.md, HBM section): "
@@ -147,11 +147,11 @@ extra = [("split_sites.txt", "the launches of one step that still run a plane-sp
          ("step_series_bench.txt", "per-step ms over 120 steps with the bench's frozen learning rate"),
          ("clock_under_load.txt", "shader clock and board power of the GPU under the dominant kernel back to back, the fp32-input MFMA kernel, an HBM copy, the bench step"),
          ("precision_f16x2.txt", "time and error against fp64 of the default arithmetic, the 3-term bf16 split and the fp32-input MFMA on the strip and tiled shapes, for activation-like, gradient-like, extreme-scale and outlier-laden operands; launches of a step on the fp16 split and the tensors that still take a reduction pass of their own"),
-         ("bench_bf16x3.json", "`python bench.py --bf16x3`: the round-2 default arithmetic (3-term bf16 split, 6 products) on this round's code"),
-         ("bench_bf16.json", "`python bench.py --bf16`: bf16 products + bf16 activation storage"),
-         ("bench_bf16_irnet.json", "`python bench.py --bf16 --irnet` = BASELINE configs[4] on one GPU"),
-         ("bench_irnet.json", "`python bench.py --irnet`: IR-Net on, fp32-grade arithmetic"),
-         ("bench_rccl_world1.json", "`MMT_FORCE_DIST=1 MMT_DIST_TRACE=1 torch.distributed.run --nproc-per-node 1 bench.py --gpus 1`: the RCCL path at world size 1 with the bucketed exchange; `dist_trace` = per-piece issue / arrival times")]
+         ("bench_bf16x3.json", "`python bench.py --full --bf16x3`: the round-2 default arithmetic (3-term bf16 split, 6 products) on this round's code"),
+         ("bench_bf16.json", "`python bench.py --full --bf16`: bf16 products + bf16 activation storage"),
+         ("bench_bf16_irnet.json", "`python bench.py --full --bf16 --irnet` = BASELINE configs[4] on one GPU"),
+         ("bench_irnet.json", "`python bench.py --full --irnet`: IR-Net on, fp32-grade arithmetic"),
+         ("bench_rccl_world1.json", "`MMT_FORCE_DIST=1 MMT_DIST_TRACE=1 torch.distributed.run --nproc-per-node 1 bench.py --full --gpus 1`: the RCCL path at world size 1 with the bucketed exchange; `dist_trace` = per-piece issue / arrival times")]
 out += ["## How the step is put together; other configurations", ""]
 for f, what in extra:
     if os.path.exists(os.path.join(SRC, f)) and os.path.getsize(os.path.join(SRC, f)) > 0:

@@ -65,7 +65,7 @@ def test_bench_two_ranks_self_spawned():
     env = dict(os.environ, MMT_BENCH_NO_FP32_LEG="1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "2",
                         "--profile-steps", "1", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     out = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -100,7 +100,7 @@ def test_rccl_world1_bench_with_bucketed_exchange():
     env = dict(os.environ, MMT_FORCE_DIST="1", MMT_DIST_TRACE="1", MMT_BUCKETED_ALLREDUCE="1", MMT_BENCH_NO_FP32_LEG="1",
                HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29741", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+           "--master-port", "29741", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "2",
            "--profile-steps", "1", "--no-cpu-baseline"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
