@@ -585,6 +585,23 @@ int mmt_mgd_level_forward(const float* s, const mmt_mgd_teachers* T /*[host]*/, 
                           int C, float* acc, void* stream);
 int mmt_mgd_level_backward(const float* s, const mmt_mgd_teachers* T /*[host]*/, const float* m, int N, int H, int W,
                            int C, const float* coef, float* grad_s, void* stream);
+/* MGD over S student views (MT.AUG_S > 1; generalized_rcnn.py:201-215, 253-280), one pyramid LEVEL, ONE launch for all
+ * (student, teacher) pairs.  Student j was computed on a mirrored input when mirror[j] (the odd views):
+ *   term(i,j) = sum_p (s_j'[p] - t_i'[p])^2 m[p] / (sum(m)*C + 1e-7),  ' = un-mirrored (flip[i] / mirror[j])
+ * s_j, t_i NHWC [N,H,W,C]; m [N,H,W] {0,1}; 1 <= ns <= 4, 1 <= nt <= 8, ns * nt <= 16 (else MMT_EINVAL).
+ * forward : acc[j*nt + i] += sum_p (s_j' - t_i')^2 m,  acc[ns*nt] += sum(m)          (acc zeroed by the caller)
+ * backward: grad_s [ns][N,H,W,C] (view j in its own frame q; p = the mirrored pixel of q when mirror[j]):
+ *           grad_s[j][q] = 2 m[p] * sum_i coef[j*nt + i] (s_j[q] - t_i'[p])    (coef: DEVICE array [ns*nt])
+ * Every student, teacher and mask element is read once per launch (a thread holds the column pair (w, W-1-w)). */
+typedef struct {
+  const float* s[4];
+  int mirror[4];
+  int ns;
+} mmt_mgd_students;
+int mmt_mgd_views_forward(const mmt_mgd_students* S /*[host]*/, const mmt_mgd_teachers* T /*[host]*/, const float* m, int N,
+                          int H, int W, int C, float* acc, void* stream);
+int mmt_mgd_views_backward(const mmt_mgd_students* S /*[host]*/, const mmt_mgd_teachers* T /*[host]*/, const float* m, int N,
+                           int H, int W, int C, const float* coef, float* grad_s, void* stream);
 /* binary mask pyramid level: m[n,h,w] = adaptive_avg_pool2d(seg[n], (H,W)) > 0.5, seg int32 [N,IH,IW] */
 int mmt_mask_pool(const int32_t* seg, int N, int IH, int IW, int H, int W, float* m, void* stream);
 

@@ -141,6 +141,177 @@ extern "C" int mmt_mgd_level_backward(const float* s, const mmt_mgd_teachers* T,
   return mgd_launch(true, s, T, m, N, H, W, C, nullptr, coef, grad_s, stream);
 }
 
+// ----------------------------------------------------------------------------- MGD over S student views
+// One thread per (image row, column pair (w, W-1-w), float4 of channels): the centre column of an odd W is its own pair.  Both
+// columns of every student, every teacher and the mask are loaded once, and every (student j, teacher i) term of both pixels is
+// formed from registers, whatever the flips -- each operand element is read once per launch.
+#define MGD_MAX_S 4
+#define MGD_MAX_T 8
+#define MGD_MAX_TERMS 16   // S * nt accumulators (forward) / coefficients (backward) per thread
+
+struct MgdS {
+  const float* s[MGD_MAX_S];
+  int mirror[MGD_MAX_S];
+};
+
+template <bool BWD, int S>
+__global__ __launch_bounds__(256) void mgd_views_kernel(MgdS Sv, MgdT T, const float* __restrict__ m, long rows, int W,
+                                                        int C4, float* __restrict__ acc, const float* __restrict__ coef,
+                                                        float* __restrict__ grad) {
+  const int nt = T.nt;
+  const int Wh = (W + 1) >> 1;
+  float num[S][MGD_MAX_T];
+  float cf[S][MGD_MAX_T];
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int k = 0; k < MGD_MAX_T; k++) {
+      num[j][k] = 0.f;
+      cf[j][k] = (BWD && k < nt) ? coef[j * nt + k] : 0.f;
+    }
+  float msum = 0.f;
+  const long total = rows * Wh * C4;
+  const long plane = rows * W * C4;   // float4s of one view
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long rp = i / C4;
+    const int c4 = (int)(i - rp * C4);
+    const long row = rp / Wh;
+    const int wa = (int)(rp - row * Wh), wb = W - 1 - wa;
+    const bool pair = wa != wb;
+    const long pa = row * W + wa, pb = row * W + wb;   // pixels
+    const float ma = m[pa];
+    const float mb = pair ? m[pb] : 0.f;               // (the centre column counts once)
+    if (!BWD && c4 == 0) msum += ma + mb;
+    f32x4 sa[S], sb[S];
+#pragma unroll
+    for (int j = 0; j < S; j++) {
+      sa[j] = ((const f32x4*)Sv.s[j])[pa * C4 + c4];
+      sb[j] = pair ? ((const f32x4*)Sv.s[j])[pb * C4 + c4] : sa[j];
+    }
+    f32x4 ga[S], gb[S];
+#pragma unroll
+    for (int j = 0; j < S; j++) { ga[j] = f32x4{0.f, 0.f, 0.f, 0.f}; gb[j] = ga[j]; }
+#pragma unroll
+    for (int k = 0; k < MGD_MAX_T; k++) {
+      if (k >= nt) break;
+      const f32x4 ta = ((const f32x4*)T.t[k])[pa * C4 + c4];
+      const f32x4 tb = pair ? ((const f32x4*)T.t[k])[pb * C4 + c4] : ta;
+      const int fk = T.flip[k];
+#pragma unroll
+      for (int j = 0; j < S; j++) {
+        const int mj = Sv.mirror[j];
+        if (BWD) {
+          // d/ds_j in view j's own frame q: the teacher index mirrors when flip_k XOR mirror_j
+          const bool x = (fk ^ mj) != 0;
+          const f32x4 tqa = x ? tb : ta, tqb = x ? ta : tb;
+#pragma unroll
+          for (int e = 0; e < 4; e++) {
+            ga[j][e] += cf[j][k] * (sa[j][e] - tqa[e]);
+            gb[j][e] += cf[j][k] * (sb[j][e] - tqb[e]);
+          }
+        } else {
+          // un-mirrored frame p: s_j'[wa] = s_j[mirror ? wb : wa], t_k'[wa] = t_k[flip ? wb : wa]; likewise at wb
+          const f32x4 s1 = mj ? sb[j] : sa[j], s2 = mj ? sa[j] : sb[j];
+          const f32x4 t1 = fk ? tb : ta, t2 = fk ? ta : tb;
+          float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+          for (int e = 0; e < 4; e++) {
+            const float d1 = s1[e] - t1[e], d2 = s2[e] - t2[e];
+            a1 += d1 * d1;
+            a2 += d2 * d2;
+          }
+          num[j][k] += a1 * ma + a2 * mb;
+        }
+      }
+    }
+    if (BWD) {
+#pragma unroll
+      for (int j = 0; j < S; j++) {
+        const int mj = Sv.mirror[j];
+        // the mask is read at the mirrored pixel when the student is mirrored
+        const float mqa = 2.f * (mj ? (pair ? mb : ma) : ma), mqb = 2.f * (mj ? ma : mb);
+        f32x4 oa, ob;
+#pragma unroll
+        for (int e = 0; e < 4; e++) { oa[e] = ga[j][e] * mqa; ob[e] = gb[j][e] * mqb; }
+        ((f32x4*)grad)[j * plane + pa * C4 + c4] = oa;
+        if (pair) ((f32x4*)grad)[j * plane + pb * C4 + c4] = ob;
+      }
+    }
+  }
+  if (!BWD) {
+    __shared__ float red[4][S * MGD_MAX_T + 1];
+    const int wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < S; j++)
+#pragma unroll
+      for (int k = 0; k < MGD_MAX_T; k++) {
+        const float v = wave_sum(num[j][k]);
+        if ((threadIdx.x & 63) == 0) red[wv][j * MGD_MAX_T + k] = v;
+      }
+    const float ms = wave_sum(msum);
+    if ((threadIdx.x & 63) == 0) red[wv][S * MGD_MAX_T] = ms;
+    __syncthreads();
+    for (int q = threadIdx.x; q <= S * MGD_MAX_T; q += 256) {
+      const float v = red[0][q] + red[1][q] + red[2][q] + red[3][q];
+      if (q == S * MGD_MAX_T) {
+        atomicAdd(acc + S * nt, v);
+      } else {
+        const int j = q / MGD_MAX_T, k = q - j * MGD_MAX_T;
+        if (k < nt) atomicAdd(acc + j * nt + k, v);
+      }
+    }
+  }
+}
+
+template <bool BWD, int S>
+static void mgd_views_go(int blocks, hipStream_t st, const MgdS& sv, const MgdT& q, const float* m, long rows, int W, int C4,
+                         float* acc, const float* coef, float* grad) {
+  hipLaunchKernelGGL((mgd_views_kernel<BWD, S>), dim3(blocks), dim3(256), 0, st, sv, q, m, rows, W, C4, acc, coef, grad);
+}
+
+static int mgd_views_launch(bool bwd, const mmt_mgd_students* Sv, const mmt_mgd_teachers* T, const float* m, int N, int H,
+                            int W, int C, float* acc, const float* coef, float* grad, void* stream) {
+  if (!Sv || !T || Sv->ns < 1 || Sv->ns > MGD_MAX_S || T->nt < 1 || T->nt > MGD_MAX_T || Sv->ns * T->nt > MGD_MAX_TERMS ||
+      (C & 3) || N < 0 || H < 0 || W < 0)
+    return MMT_EINVAL;
+  MgdT q;
+  for (int i = 0; i < MGD_MAX_T; i++) { q.t[i] = T->t[i < T->nt ? i : 0]; q.flip[i] = T->flip[i < T->nt ? i : 0] ? 1 : 0; }
+  q.nt = T->nt;
+  MgdS sv;
+  for (int j = 0; j < MGD_MAX_S; j++) {
+    sv.s[j] = Sv->s[j < Sv->ns ? j : 0];
+    sv.mirror[j] = Sv->mirror[j < Sv->ns ? j : 0] ? 1 : 0;
+  }
+  const long rows = (long)N * H;
+  const long total = rows * ((W + 1) / 2) * (C / 4);
+  if (total == 0) return 0;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipStream_t st = (hipStream_t)stream;
+  const int C4 = C / 4;
+  switch (Sv->ns * 2 + (bwd ? 1 : 0)) {
+    case 2: mgd_views_go<false, 1>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
+    case 3: mgd_views_go<true, 1>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
+    case 4: mgd_views_go<false, 2>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
+    case 5: mgd_views_go<true, 2>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
+    case 6: mgd_views_go<false, 3>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
+    case 7: mgd_views_go<true, 3>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
+    case 8: mgd_views_go<false, 4>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
+    default: mgd_views_go<true, 4>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
+  }
+  MMT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmt_mgd_views_forward(const mmt_mgd_students* S, const mmt_mgd_teachers* T, const float* m, int N, int H, int W,
+                                     int C, float* acc, void* stream) {
+  return mgd_views_launch(false, S, T, m, N, H, W, C, acc, nullptr, nullptr, stream);
+}
+extern "C" int mmt_mgd_views_backward(const mmt_mgd_students* S, const mmt_mgd_teachers* T, const float* m, int N, int H,
+                                      int W, int C, const float* coef, float* grad_s, void* stream) {
+  return mgd_views_launch(true, S, T, m, N, H, W, C, nullptr, coef, grad_s, stream);
+}
+
 __global__ __launch_bounds__(256) void mask_pool_kernel(const int* __restrict__ seg, int N, int IH, int IW, int H,
                                                         int W, float* __restrict__ m) {
   // one wave per output pixel, lanes sweep the pooling window; the sum of small integers is exact in fp32 in any

@@ -77,6 +77,10 @@ class MgdTeachers(ctypes.Structure):
     _fields_ = [("t", c_void_p * 8), ("flip", c_int * 8), ("nt", c_int)]
 
 
+class MgdStudents(ctypes.Structure):
+    _fields_ = [("s", c_void_p * 4), ("mirror", c_int * 4), ("ns", c_int)]
+
+
 _SIGS = {
     "mmt_version": [],
     "mmt_roi_align_forward": [ctypes.POINTER(Pyramid), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
@@ -163,6 +167,10 @@ _SIGS = {
     "mmt_mask_bce": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "mmt_mgd_level_forward": [c_void_p, ctypes.POINTER(MgdTeachers), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_mgd_level_backward": [c_void_p, ctypes.POINTER(MgdTeachers), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "mmt_mgd_views_forward": [ctypes.POINTER(MgdStudents), ctypes.POINTER(MgdTeachers), c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                              c_void_p],
+    "mmt_mgd_views_backward": [ctypes.POINTER(MgdStudents), ctypes.POINTER(MgdTeachers), c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                               c_void_p, c_void_p],
     "mmt_mask_pool": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_psm_rows": [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "mmt_psm_variance": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
@@ -2360,6 +2368,62 @@ def mgd_level_backward(s, ts, flips, m, coef):
     _check(lib().mmt_mgd_level_backward(_p(s), ctypes.byref(T), _p(m), N, H, W, C, _p(coef), _p(g), _stream()),
            "mmt_mgd_level_backward")
     return g
+
+
+MGD_MAX_STUDENTS, MGD_MAX_TEACHERS, MGD_MAX_TERMS = 4, 8, 16   # the register budget of mmt_mgd_views_* (include/mmtpsm.h)
+
+
+def mgd_views_supported(ns, nt):
+    return 1 <= ns <= MGD_MAX_STUDENTS and 1 <= nt <= MGD_MAX_TEACHERS and ns * nt <= MGD_MAX_TERMS
+
+
+def _students(ss, mirrors):
+    S = MgdStudents()
+    S.ns = len(ss)
+    for j, (s, f) in enumerate(zip(ss, mirrors)):
+        S.s[j] = s.data_ptr()
+        S.mirror[j] = 1 if f else 0
+    return S
+
+
+def _views_check(ss, ts):
+    if not mgd_views_supported(len(ss), len(ts)):
+        raise RuntimeError("MGD over student views: %d students x %d teacher views is beyond the kernel's register budget "
+                           "(at most %d students, %d teachers, %d pairs)" % (len(ss), len(ts), MGD_MAX_STUDENTS, MGD_MAX_TEACHERS,
+                                                                            MGD_MAX_TERMS))
+    for t in list(ss) + list(ts):
+        if t.shape != ss[0].shape or t.dtype != torch.float32:
+            raise RuntimeError("MGD over student views: every student and teacher embedding of a level is fp32 and has the same shape")
+
+
+def mgd_views_forward(ss, mirrors, ts, flips, m, acc=None):
+    """-> acc (ns*nt+1,) = [num(j, i) at j*nt + i ..., msum] of one level, all student views x all teacher views in ONE launch;
+    `acc`: a zeroed row to accumulate into"""
+    ss = [nhwc(s) for s in ss]
+    ts = [nhwc(t) for t in ts]
+    _views_check(ss, ts)
+    N, C, Hh, W = ss[0].shape
+    if acc is None:
+        acc = torch.zeros((len(ss) * len(ts) + 1,), dtype=torch.float32, device=ss[0].device)
+    S, T = _students(ss, mirrors), _teachers(ts, flips)
+    _check(lib().mmt_mgd_views_forward(ctypes.byref(S), ctypes.byref(T), _p(m), N, Hh, W, C, _p(acc), _stream()),
+           "mmt_mgd_views_forward")
+    return acc
+
+
+def mgd_views_backward(ss, mirrors, ts, flips, m, coef):
+    """-> [gradient of student j, in view j's own frame] (NHWC views of one [ns, N, H, W, C] buffer); coef (ns*nt,) at j*nt + i"""
+    ss = [nhwc(s) for s in ss]
+    ts = [nhwc(t) for t in ts]
+    _views_check(ss, ts)
+    N, C, Hh, W = ss[0].shape
+    g = empty_nhwc(len(ss) * N, C, Hh, W, ss[0].device)
+    S, T = _students(ss, mirrors), _teachers(ts, flips)
+    if coef.dtype != torch.float32 or not coef.is_contiguous():
+        coef = coef.float().contiguous()
+    _check(lib().mmt_mgd_views_backward(ctypes.byref(S), ctypes.byref(T), _p(m), N, Hh, W, C, _p(coef), _p(g), _stream()),
+           "mmt_mgd_views_backward")
+    return [g[j * N:(j + 1) * N] for j in range(len(ss))]
 
 
 def mask_pool(seg, H, W):

@@ -387,9 +387,12 @@ class MTtrainer(object):
         feats_s = feats_u = None
         early, cut = False, None
         job = None
-        if use_mt and self.student_bs == 1:
+        xu = None
+        if use_mt:
             xs = data_s.tensors.to(self.device)
-            xu = data_u_list[-1].tensors.to(self.device)
+            # AUG_S > 1: the S views as one batch -- the same pass schedules as for the single view
+            xu = data_u_list[-1].tensors.to(self.device) if self.student_bs == 1 else self._student_views(data_u_list)
+        if xu is not None:
             if self.student_passes == "pair" and xs.shape == xu.shape:
                 # one set of forward launches for both passes (N = 4), two autograd graphs (modeling/backbone/backbone.py:
                 # forward_pair): the schedule below is that of "split"
@@ -642,11 +645,31 @@ class MTtrainer(object):
         job["thread"].start()
         return job
 
+    def _student_views(self, data_u_list):
+        """AUG_S > 1: the last AUG_S views of the unlabeled batch as one batch, odd views mirrored (generalized_rcnn.py:209-214) --
+        the input of the step's student passes; None when the views' shapes differ (forward_student then runs them one by one)"""
+        views = [u.tensors for u in data_u_list[-self.student_bs:]]
+        if any(v.shape != views[0].shape for v in views):
+            return None
+        views = [v.to(self.device) for v in views]
+        return torch.cat([torch.flip(v, (3,)) if j % 2 == 1 else v for j, v in enumerate(views)], 0)
+
     def forward_unlabel(self, data_u_list, features=None, job=None):
         """MTtrainer.py:247-275 (N_STEP_UNLABEL = 1)"""
         student = [s.to(self.device) for s in data_u_list[-self.student_bs:]]
         emb = None
-        if features is not None and len(features) == 1 and self.cfg.MT.FG_HINT and self.cfg.MT.CLS_LOSS and torch.is_grad_enabled():
+        if features is not None and len(features) == 1 and len(student) > 1:
+            # AUG_S > 1: features[0] is ONE pyramid over the S views (the step's student pass); forked as below when both consistency
+            # losses consume it, the hint adaptor runs once over the batched levels, the box head too (forward_student)
+            f_emb = f_box = features[0]
+            if self.cfg.MT.FG_HINT and self.cfg.MT.CLS_LOSS and torch.is_grad_enabled():
+                f_emb, f_box = fused.fork_levels(features[0], 2)
+            n = f_box[0].shape[0] // len(student)
+            if self.cfg.MT.FG_HINT:
+                emb = self.student.get_emb_feature(self.student.view_slices(f_emb, n, len(student)))
+            features = self.student.view_slices(f_box, n, len(student))
+            f_emb = None
+        elif features is not None and len(features) == 1 and self.cfg.MT.FG_HINT and self.cfg.MT.CLS_LOSS and torch.is_grad_enabled():
             # two consumers of every pyramid level (hint adaptor, box pooler): their gradients are summed in one launch
             f_emb, f_box = fused.fork_levels(features[0], 2)
             if job is None:
@@ -654,7 +677,7 @@ class MTtrainer(object):
             features, f_emb = [f_box], [f_emb]
         else:
             f_emb = features
-        if job is not None and features is not None and self.cfg.MT.FG_HINT:
+        if job is not None and features is not None and self.cfg.MT.FG_HINT and emb is None:
             emb = self.student.get_emb_feature(f_emb)  # independent of the teacher: queued before the wait
         try:
             if job is not None:

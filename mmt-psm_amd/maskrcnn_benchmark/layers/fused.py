@@ -678,6 +678,41 @@ class MGDLossFn(torch.autograd.Function):
         return (None, None, None) + tuple(grads) + (None,) * (len(ctx.teachers[0]) * len(ctx.students))
 
 
+class MGDViewsLossFn(torch.autograd.Function):
+    """fg_hint_loss with S > 1 student views (generalized_rcnn.py:243-282; odd views were computed on mirrored inputs): mean over
+    (teacher pyramid x student view x level) masked-L2 terms, one forward and one backward launch per level for all pairs"""
+
+    @staticmethod
+    def forward(ctx, seg, flips, n_levels, n_students, *embs):
+        L, S = n_levels, n_students
+        students = [[H.nhwc(embs[j * L + l]) for j in range(S)] for l in range(L)]
+        nt = (len(embs) - S * L) // L
+        teachers = [[H.nhwc(embs[S * L + i * L + l]) for i in range(nt)] for l in range(L)]
+        mirrors = [j % 2 == 1 for j in range(S)]    # students[1::2] of the reference
+        C = students[0][0].shape[1]
+        acc = torch.zeros((L, S * nt + 1), dtype=torch.float32, device=students[0][0].device)   # one fill for all levels
+        masks = []
+        for l in range(L):
+            s0 = students[l][0]
+            if s0.shape[1] != C:
+                raise RuntimeError("MGD: the embeddings of all levels have the same width")
+            m = H.mask_pool(seg, s0.shape[2], s0.shape[3])
+            H.mgd_views_forward(students[l], mirrors, teachers[l], flips, m, acc[l])
+            masks.append(m)
+        den = acc[:, S * nt] * C + 1e-7
+        ctx.students, ctx.teachers, ctx.masks, ctx.den, ctx.flips, ctx.mirrors = students, teachers, masks, den, flips, mirrors
+        ctx.n_terms, ctx.S, ctx.nt = nt * S * L, S, nt
+        return (acc[:, :S * nt] / den[:, None]).reshape(-1).mean()
+
+    @staticmethod
+    def backward(ctx, g):
+        S, nt, L = ctx.S, ctx.nt, len(ctx.students)
+        coef = (g / ctx.n_terms / ctx.den)[:, None].expand(-1, S * nt).contiguous()   # [level][student * nt + teacher]
+        grads = [H.mgd_views_backward(ss, ctx.mirrors, ts, ctx.flips, m, coef[l])
+                 for l, (ss, ts, m) in enumerate(zip(ctx.students, ctx.teachers, ctx.masks))]
+        return (None, None, None, None) + tuple(grads[l][j] for j in range(S) for l in range(L)) + (None,) * (nt * L)
+
+
 class ReluGradMaskFn(torch.autograd.Function):
     """identity whose backward applies (x > 0): the adapter between a fused-ReLU output and consumers that are
     NOT nodes of this file (index / cat / library ops), so that the producer still receives a pre-masked gradient"""

@@ -269,12 +269,25 @@ class GeneralizedRCNN(nn.Module):
         the teacher, so the trainer launches them before it waits for the teacher)"""
         images = [to_image_list(im) for im in images] if isinstance(images, list) else [to_image_list(images)]
         feat_list = features if features is not None else self.extract_aug_feat(images, teacher=False)
+        # AUG_S > 1: the views of one batched pass (view_slices) go through the box head as one batch too
+        bp = self.__dict__.get("_batched_pyr")
+        if bp is not None and not (len(feat_list) == bp[2] and feat_list[0][0].data_ptr() == bp[0][0].data_ptr()):
+            bp = None
         loss_dict = {}
         if self.cfg.MT.FG_HINT:
             emb = embeddings if embeddings is not None else self.get_emb_feature(feat_list)
             loss_dict.update(mt_fg_loss=fg_hint_loss(result_t["embedding"], emb, result_t["seg_mask"]))
+        if bp is not None:
+            self._batched_pyr = None
         if self.cfg.MT.CLS_LOSS:
-            loss_dict.update(self.box_heads.forward_student(feat_list, result_t["result_t"], result_t["class_logit_t"]))
+            box = self.box_heads.box
+            if bp is not None:
+                box.batched_pyramid = bp
+            try:
+                loss_dict.update(self.box_heads.forward_student(feat_list, result_t["result_t"], result_t["class_logit_t"]))
+            finally:
+                if bp is not None:
+                    box.batched_pyramid = None
         return loss_dict
 
     def extract_aug_feat(self, imglist, teacher=True):
@@ -303,8 +316,20 @@ class GeneralizedRCNN(nn.Module):
             for i, img in enumerate(imglist):
                 if i % 2 == 1:
                     img.hflip()
+            if len(imglist) > 1 and all(img.tensors.shape == imglist[0].tensors.shape for img in imglist):
+                # AUG_S > 1: the student views (odd ones mirrored) as ONE backbone pass; the hint adaptor and the box head run
+                # once over the batched levels as well (get_emb_feature, forward_student)
+                pyr = tuple(self.backbone(torch.cat([img.tensors for img in imglist], 0)))
+                return self.view_slices(pyr, imglist[0].tensors.shape[0], len(imglist))
+            for img in imglist:
                 feats.append(self.backbone(img.tensors))
         return feats
+
+    def view_slices(self, pyr, n, nv):
+        """the per-view pyramids of a pyramid computed for nv views of n images each; the batched pyramid is remembered for
+        get_emb_feature and the box head, which then run once over all views"""
+        self._batched_pyr = (pyr, n, nv)
+        return [tuple(fused.batch_slice(level, i * n, (i + 1) * n) for level in pyr) for i in range(nv)]
 
     def get_emb_feature(self, feature_list):
         bp = getattr(self, "_batched_pyr", None)
@@ -322,13 +347,16 @@ class GeneralizedRCNN(nn.Module):
 
 def fg_hint_loss(teachers, students, masks):
     """MGD (generalized_rcnn.py:243-282): teachers = list over views of 5-level embeddings (odd views were
-    computed on mirrored inputs and are un-mirrored inside the kernel), students = [5-level embeddings]."""
-    if len(students) != 1:
-        raise NotImplementedError("MT.AUG_S > 1: the mirrored student views of the reference (generalized_rcnn.py:253-255, 274-280; "
-                                  "forward_student's per-view loop, :164-205) are not built -- every shipped recipe has AUG_S = 1")
+    computed on mirrored inputs and are un-mirrored inside the kernel), students = list over the AUG_S student views of
+    5-level embeddings (odd views mirrored likewise, generalized_rcnn.py:253-255, 274-280)."""
+    from maskrcnn_benchmark import _hip as H
     seg = torch.stack([m.to(torch.int32) for m in masks]).contiguous()
-    s = students[0]
-    nl = len(s)
+    nl = len(students[0])
     flips = [i % 2 == 1 for i in range(len(teachers))]
     flat_t = [t[l].detach() for t in teachers for l in range(nl)]
-    return fused.MGDLossFn.apply(seg, flips, nl, *s, *flat_t)
+    if len(students) == 1:
+        return fused.MGDLossFn.apply(seg, flips, nl, *students[0], *flat_t)
+    if not H.mgd_views_supported(len(students), len(teachers)):
+        raise NotImplementedError("MT.AUG_S = %d with %d teacher views: the MGD kernel holds at most %d student views and %d "
+                                  "(student, teacher) pairs" % (len(students), len(teachers), H.MGD_MAX_STUDENTS, H.MGD_MAX_TERMS))
+    return fused.MGDViewsLossFn.apply(seg, flips, nl, len(students), *[s[l] for s in students for l in range(nl)], *flat_t)

@@ -90,7 +90,9 @@ class FPN2MLPFeatureExtractor(nn.Module):
         if k in sd:
             sd[k] = self._perm(sd[k], False).contiguous()
 
-    def forward(self, x, proposals, filp=False, istrain=False):
+    def forward(self, x, proposals, filp=False, istrain=False, views=1):
+        """`views`: the proposals are those of `views` views in a row (ROIBoxHead._forward_single's batched form); a replayed
+        run takes one recorded dropout mask per view, as the reference draws them"""
         pooled = self.pooler(x, proposals)                 # (R, C, 7, 7) NHWC-dense
         x = pooled.permute(0, 2, 3, 1).reshape(pooled.shape[0], -1)  # (R, 7*7*C) view
         fused._carry_stats(pooled, x)                      # (the statistics slot of the pooled tensor: fc6's scale, no reduction pass)
@@ -98,6 +100,8 @@ class FPN2MLPFeatureExtractor(nn.Module):
         mul = None
         if self.p_drop > 0 and istrain:
             rec = self.replay("dropout") if self.replay is not None else None
+            if rec is not None and views > 1:
+                rec = torch.cat([rec.to(x.device)] + [self.replay("dropout").to(x.device) for _ in range(views - 1)], 0)
             keep = rec.to(x.device) if rec is not None else torch.empty(
                 (x.shape[0], self.fc7.out_features), device=x.device).bernoulli_(1 - self.p_drop, generator=self.generator)
             mul = keep / (1 - self.p_drop)
@@ -249,15 +253,25 @@ class FastRCNNLossComputation(object):
             raise NotImplementedError("MT.CLS_LOSS_TYPE=%s: the MI355X path implements 'bce'/'ce', 'kl' and 'mse'" % typ)
         pos, neg = labels > 0, labels == 0
         n_pos, n_neg = pos.sum(), neg.sum()
+        per_view = False
         if cfg.MT.RANK_FILTER > 0:
             if cfg.MT.HARD_NEG:
                 v = H.psm_variance(teacher, use_softmax=(typ == "bce"))
+            elif len(class_logits) > 1:
+                # AUG_S > 1: one random negative subset per student view, drawn inside the per-view loop as the reference does
+                # (box_head/loss.py:201,211); the S = 1 case keeps its single draw below
+                per_view = True
+                v = torch.rand((len(class_logits),) + tuple(labels.shape), device=labels.device,
+                               generator=self.fg_bg_sampler.generator)
             else:
                 v = torch.rand(labels.shape, device=labels.device, generator=self.fg_bg_sampler.generator)
             vn = torch.where(neg, v, torch.full_like(v, -1.0))
-            order = torch.argsort(vn, descending=True, stable=True)
+            order = torch.argsort(vn, dim=-1, descending=True, stable=True)
             rank = torch.empty_like(order)
-            rank[order] = torch.arange(order.numel(), device=order.device)
+            if per_view:
+                rank.scatter_(1, order, torch.arange(order.shape[1], device=order.device).expand_as(order).contiguous())
+            else:
+                rank[order] = torch.arange(order.numel(), device=order.device)
             n_keep = torch.minimum(n_neg, n_pos // 2)
             keep_neg = neg & (rank < n_keep)
             wneg = cfg.MT.CLS_BALANCE_WEIGHT if (cfg.MT.HARD_NEG and kind == 0) else 1.0
@@ -273,8 +287,8 @@ class FastRCNNLossComputation(object):
             S = roww.sum()
         nc = teacher.shape[2]
         norm = 1.0 / (S * (3.0 if kind == 0 else float(nc)))
-        losses = [fused.PSMLossFn.apply(cl, teacher, roww, norm, cfg.MT.TEMP, 1 if cfg.MT.SHARPEN else 0, kind)
-                  for cl in class_logits]
+        losses = [fused.PSMLossFn.apply(cl, teacher, roww[j] if per_view else roww, norm, cfg.MT.TEMP, 1 if cfg.MT.SHARPEN else 0, kind)
+                  for j, cl in enumerate(class_logits)]
         return torch.mean(torch.stack(losses), dim=0)
 
 
@@ -409,7 +423,7 @@ class ROIBoxHead(nn.Module):
             boxes = []
             for i in range(nv):
                 boxes += list(proposals if i % 2 == 0 else proposals_b)
-            x = self.feature_extractor(pyr, boxes, istrain=istrain)
+            x = self.feature_extractor(pyr, boxes, istrain=istrain, views=nv)
             cl, br = self.predictor(x, self._scale(istrain))
             R = x.shape[0] // nv
             return (list(x.split(R, 0)), list(cl.split(R, 0)), list(br.split(R, 0)), proposals)
