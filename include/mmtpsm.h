@@ -315,18 +315,6 @@ typedef struct {
   const void* f16_guard_dy;
   const void* w_src;
   const void* w_src_scale;
-  /* mmt_conv_wgrad on the fp16 split only, optional (round 4): a SECOND (x, dy) pair of the same shapes whose weight gradient
-   * is accumulated by the same launch -- the labeled and the unlabeled student pass of a mean-teacher step share every weight
-   * (engine/MTtrainer.py): dW = dY1^T im2col(X1) + dY2^T im2col(X2) as one launch over both pixel ranges instead of two
-   * half-sized ones (half the launches, twice the pixels per block).  x2 / dy2 with their own maxima f16_x_amax2 / f16_dy_amax2
-   * (and optional statistics slots f16_guard_x2 / f16_guard_dy2): every block works on one segment with that segment's
-   * scales.  mmt_conv_wgrad_splits counts the slices of the two-segment launch when x2 is set. */
-  const void* x2;
-  const void* dy2;
-  const void* f16_x_amax2;
-  const void* f16_dy_amax2;
-  const void* f16_guard_x2;
-  const void* f16_guard_dy2;
   /* mmt_conv_forward_pg AND mmt_conv3x3_strip_f16x2 (the host side passes 1 to both by default; every other entry point refuses a
    * non-zero value): 0 = x_planes indexed like x ([N][H][W][Cin]); 1 = ROW-BLOCKED planes
    * [N * H][Cin / 16][W][16] (mmt_split_planes_f16_rb): the 16 channels of a 16-k step of consecutive pixels of an image row are
@@ -379,12 +367,12 @@ int mmt_conv_wants_planes(const mmt_conv_args* a /*[host]*/);
  * Tensors stay fp32 in HBM in every mode.  Shapes the split kernels do not cover (Cin % 16 != 0 or Cout <= 32 forward,
  * Cout % 4 != 0 weight gradient) always run in mode 0.  Returns MMT_EINVAL for an unknown mode. */
 int mmt_set_conv_precision(int mode);
-/* EXPERIMENT (not used by the product path; mmt-psm_amd/tools/bench_f16x2.py): the tap-strip 3x3 kernel on
- * a TWO-term fp16 split -- x * s = h + l, 22 significant bits, 3 matrix products per multiply instead of 6.  The caller
- * scales each operand tensor by a power of two (largest magnitude near 2^14), passes the two fp16 planes of the input
- * (mmt_split_planes_f16) and of the packed weight (mmt_pack_weight_f16 / _flipped_f16) in x_planes / w_planes; the scales are
- * device scalars derived on the device from mmt_amax (no host round trip), the epilogue divides the sum by s_x s_w.
- * Strip shapes only (mmt_conv_wants_planes).  Opt-in from Python with MMT_F16X2=1. */
+/* The default arithmetic of mode 3 (MMT_F16X2=0 in Python selects the 3-term bf16 split instead): the tap-strip
+ * 3x3 kernel on a TWO-term fp16 split -- x * s = h + l, 22 significant bits, 3 matrix products per multiply instead of 6.  The
+ * caller scales each operand tensor by a power of two (largest magnitude near 2^14), passes the two fp16 planes of the input
+ * (mmt_split_planes_f16 / _rb, or a producer's y_rb) and of the packed weight (mmt_pack_weight_f16 / _flipped_f16) in x_planes /
+ * w_planes; the scales are device scalars derived on the device from mmt_amax (no host round trip), the epilogue divides the sum
+ * by s_x s_w.  Strip shapes only (mmt_conv_wants_planes). */
 int mmt_amax(const float* x, long n, const float* rowscale, long inner, int rows, float* amax /*device, zeroed*/, void* stream);
 /* the same reduction into a 33-float statistics slot (device, zeroed): slot[0] = max |x|, slot[1..16] += sums of |x| over a
  * sample of the tensor, slot[17..32] += the sample's element counts
@@ -473,10 +461,10 @@ int mmt_conv_writes_rb(const mmt_conv_args* a /*[host]*/);
  * rpn/rpn.py:39-46 and the heads.  Every job is what mmt_conv_wgrad takes (a, dy, rowscale, dw, dbias; a.f16_x_amax / f16_dy_amax and
  * the guards set for the fp16-split arithmetic) plus, optionally, both operands' row-blocked planes (mmt_conv_wgrad_planes' arguments).
  * Plane-fed jobs go out in groups of <= 12, fp16-split jobs without planes in groups of <= 6 per pixel-decode form, every slab of the
- * batch is summed by ONE reduce launch; a job no group takes (other arithmetic, a two-segment job, a group of one) is launched as
+ * batch is summed by ONE reduce launch; a job no group takes (other arithmetic, a group of one) is launched as
  * mmt_conv_wgrad(_planes) would launch it.  Inside a group the tiles of all layers fill the chip together: a layer is cut into a
- * quarter of the pixel ranges it would use alone (MMT_WGRAD_GROUP_DIV; 0 = as few as fill the chip as a group: measured slower in the
- * training step, whose latency-bound data-gradient chain shares the GPU with these launches).  workspace: *floats_out of mmt_conv_wgrad_group_workspace(jobs, n, &floats) floats (0: none needed), alive until the stream has
+ * quarter of the pixel ranges it would use alone (as few as fill the chip as a group was measured slower in the training step,
+ * whose latency-bound data-gradient chain shares the GPU with these launches).  workspace: *floats_out of mmt_conv_wgrad_group_workspace(jobs, n, &floats) floats (0: none needed), alive until the stream has
  * run the call.  n <= 96.  MMT_WGRAD_GROUP=0 (environment, read per call): every job as its single launch. */
 typedef struct mmt_wgrad_job {
   mmt_conv_args a;

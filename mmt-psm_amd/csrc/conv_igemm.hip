@@ -1786,8 +1786,6 @@ int fill(ConvP& p, const mmt_conv_args* a) {
   p.f16_ax = 0;
   p.guard_x = (const float*)a->f16_guard_x; p.guard_dy = (const float*)a->f16_guard_dy;
   p.w_src = (const float*)a->w_src; p.w_src_scale = (const float*)a->w_src_scale;
-  p.x2 = p.dy2 = p.f16_sx2 = p.f16_sw2 = p.guard_x2 = p.guard_dy2 = nullptr;
-  p.seg_z = 0;
   { const char* e = getenv("MMT_DIRECT_EPI"); p.staged_epilogue = e && atoi(e) == 0; }   // read per call (A/B timing)
   p.amax_out = (unsigned*)a->y_amax;
   p.amax_stats = a->y_amax_stats;
@@ -1952,19 +1950,17 @@ static int strip_ksplit(const ConvP& p, int tw) {
   return ks >= 2 ? ks : 0;
 }
 
-// 3x3 / stride 1 / pad 1 with both operands as planes: which strip width (0 = not taken)
-// K order of the tap-strip kernel (bits 24-30 of its ksplit argument = slabs per group, 0 = kh outermost as in rounds 2-5):
-// MMT_STRIP_KORDER = 0 | 1 | 2 | 4 | 8 (read per call: A/B timing).  Default 4 (tools/strip_korder.py, profiles/r06_strip_korder.txt):
-// the fabric reads of 1 (141 MB per launch instead of 278) at the cycle count of 0 -- every change of kh recomputes the copy slots'
-// row offsets, which costs 7 % of the kernel's cycles when it happens every super-step and 1 % every fourth
+// K order of the tap-strip kernel (bits 24-30 of its ksplit argument = slabs per group, 0 = kh outermost as in rounds 2-5): groups
+// of 4 slabs, fewer where Cin / 16 is not a multiple of 4 (profiles/r06_strip_korder.txt): the fabric reads of 1 (141 MB per launch
+// instead of 278) at the cycle count of 0 -- every change of kh recomputes the copy slots' row offsets, which costs 7 % of the
+// kernel's cycles when it happens every super-step and 1 % every fourth
 static int strip_korder(const ConvP& p) {
-  const char* e = getenv("MMT_STRIP_KORDER");
-  int g = e ? atoi(e) : 4;
-  if (g != 0 && g != 1 && g != 2 && g != 4 && g != 8) g = 4;
+  int g = 4;
   while (g > 1 && ((p.Cin >> 4) % g) != 0) g >>= 1;
   return g << 24;
 }
 
+// 3x3 / stride 1 / pad 1 with both operands as planes: which strip width (0 = not taken)
 static int strip_tw(const ConvP& p, bool need_planes = true) {
   if ((need_planes && !p.xpl) || !p.wpl || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.out_stride != 1 || p.Ho != p.H ||
       p.Wo != p.W || (p.Cin & 31) || p.Cout <= 32 || ((size_t)p.xpl & 15) || (p.xpl_stride & 7))
@@ -1972,8 +1968,7 @@ static int strip_tw(const ConvP& p, bool need_planes = true) {
   const char* e = getenv("MMT_STRIP");  // read per call (A/B timing)
   if (e && atoi(e) == 0) return 0;
   int tw = 0;
-  const char* w64 = getenv("MMT_STRIP_TW64");   // A/B: 4 image rows x 64 pixels per tile (6 input rows for 4: halo x 1.5) instead of 2 x 128 (4 for 2: x 2)
-  if (p.Wo % 128 == 0 && p.Ho % 2 == 0 && !(w64 && atoi(w64) && p.Ho % 4 == 0)) tw = 128;
+  if (p.Wo % 128 == 0 && p.Ho % 2 == 0) tw = 128;   // 2 image rows x 128 pixels per tile; 4 x 64 where Wo % 128 != 0
   else if (p.Wo % 64 == 0 && p.Ho % 4 == 0) tw = 64;
   constexpr int minc = 128;   // (tuned: profiles/r04_dispatch_sweep.txt)
   if (!tw || p.Cin < minc) return 0;  // K = 576 (the 64-channel layer1 convs): 12 super-steps do not amortise the fill

@@ -25,7 +25,7 @@
 //     every SIMD.  The copy waves issue every buffer_load ... lds (no MFMA wave computes an address or waits for vmcnt); ring of S
 //     stages, one raw s_barrier per 16-k step, counted vmcnt in the copy waves: the copies of step t + S go out while the matrix
 //     waves are in step t, the fragments of step t + 1 are read behind the MFMAs of step t (8 ds_read_b128 per 12 MFMAs per wave).
-//     What the loop waits for (tools/bench_pg.py --ablate, profiles/r05_pg_ablate.txt): copy time ADDS to fragment-read time on
+//     What the loop waits for (main-loop ablations, removed since: profiles/r05_pg_ablate.txt): copy time ADDS to fragment-read time on
 //     the LDS port whoever issues it (about 100 GB/s per CU of DMA writes) -- the bound of every plane-fed loop on this part;
 //   * epilogue straight from the accumulator registers (an accumulator register = one output row x 32 consecutive channels per
 //     half wave = complete 128-byte lines): no LDS staging, every residual / mask value of a 32 x 32 sub-tile requested before the
@@ -59,10 +59,7 @@ __device__ __forceinline__ void pg_unroll(F&& f) {
 // (2, 2), (1, 4)) work on KG consecutive K ranges of the same tile side by side and add their accumulators through LDS at the end --
 // split-K INSIDE the block: a few-tile shape keeps two waves on every SIMD and its tile count is 256 / (64 WM) per 256 rows without a
 // trip through memory.  ksplit > 1 adds K ranges across blocks (R = ksplit * KG ranges in all, range r = ks * KG + group).
-// AF: the A operand comes from the fp32 tensor itself (no plane-split pass in front of the launch): the copy waves fetch the raw rows
-// into registers, split them into the two fp16 terms of x * s_x there -- vector work on waves that have nothing else to do -- and
-// store the same LDS image; p.f16_sx then points to max |x| (p.f16_ax)
-template <int WM, int KG, int S, int DBG = 0, bool AF = false>   // DBG (tools/bench_pg.py --ablate): 1 A copies re-read one step, 2 B copies, 4 no copies, 8 no fragment reads
+template <int WM, int KG, int S>
 __global__ __launch_bounds__(768) void conv_pg_kernel(const ConvP p, const int ksplit, float* __restrict__ ws,
                                                       unsigned* __restrict__ tickets) {
   constexpr int BM = 64 * WM, BN = 128, GW = 2 * WM, NT = 512, GT = 64 * GW, NTALL = 768;
@@ -123,9 +120,8 @@ __global__ __launch_bounds__(768) void conv_pg_kernel(const ConvP p, const int k
     // ================================================================ copy wave
     const int sub = cw % PPG;                          // which part of the group's items
     // A: row blocks 2 sub, 2 sub + 1 of the group's tile (32 rows each), both planes; lane = (row r, physical 16-byte half)
-    // (DBG & 32 / & 64, timing only: 4 / 8 lanes share a row -- 64- / 128-byte contiguous pieces instead of 32-byte ones)
-    const int ar = (DBG & 64) ? lane >> 3 : (DBG & 32) ? lane >> 2 : lane >> 1;
-    const int alh = (DBG & 64) ? (lane & 7) : (DBG & 32) ? (lane & 3) : (lane & 1) ^ ((ar >> 3) & 1);      // logical 8-channel half this lane fetches
+    const int ar = lane >> 1;
+    const int alh = (lane & 1) ^ ((ar >> 3) & 1);      // logical 8-channel half this lane fetches
     int aih0[2], aiw0[2];
     unsigned apix[2];                                  // pixel index of the image's first pixel
     bool aok[2];
@@ -141,10 +137,8 @@ __global__ __launch_bounds__(768) void conv_pg_kernel(const ConvP p, const int k
       apix[t] = (unsigned)img * (unsigned)(p.H * p.W);
     }
     const long n_x = (long)p.N * p.H * p.W * p.Cin;
-    const __amdgpu_buffer_rsrc_t rs_a0 = AF ? __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)(n_x * 4), 0x00020000)
-                                            : __builtin_amdgcn_make_buffer_rsrc((void*)p.xpl, 0, (int)(n_x * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_a1 = AF ? rs_a0
-                                            : __builtin_amdgcn_make_buffer_rsrc((void*)(p.xpl + p.xpl_stride), 0, (int)(n_x * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.xpl, 0, (int)(n_x * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a1 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.xpl + p.xpl_stride), 0, (int)(n_x * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)p.wpl, 0, 0x7ffffff0, 0x00020000);
     // B: items NBP sub .. NBP sub + NBP - 1 of the group's eight: item t -> plane t / 4, 32-channel block t % 4 of the tile
     const int nb32 = (p.Cout + 31) >> 5;
@@ -169,7 +163,7 @@ __global__ __launch_bounds__(768) void conv_pg_kernel(const ConvP p, const int k
     }
     // bytes from one 16-channel step to the next inside a tap: 32 with planes indexed like x, one image row of the block (W x 32)
     // with row-blocked planes [N H][Cin / 16][W][16]
-    const int a_step = AF ? 64 : (p.xpl_rb ? p.W * 32 : 32);   // (AF: 16 fp32 channels)
+    const int a_step = p.xpl_rb ? p.W * 32 : 32;
     int soff_a = f_ci * a_step, soff_b = kt0 * b_step;
     unsigned vo_a[2] = {PG_OOB, PG_OOB};
     auto enter_tap = [&]() {   // per-lane offset of (row's pixel for tap (f_kh, f_kw), this lane's 8 channels); halo / past M: zeros
@@ -178,7 +172,6 @@ __global__ __launch_bounds__(768) void conv_pg_kernel(const ConvP p, const int k
         const int ih = aih0[t] + f_kh, iw = aiw0[t] + f_kw;
         const bool ok = aok[t] && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
         vo_a[t] = !ok ? PG_OOB
-                  : AF ? ((apix[t] + (unsigned)(ih * p.W + iw)) * (unsigned)p.Cin + (unsigned)(alh * 8)) * 4u
                   : p.xpl_rb ? (((apix[t] + (unsigned)(ih * p.W)) * (unsigned)spt + (unsigned)iw) * 16u + (unsigned)(alh * 8)) * 2u
                              : ((apix[t] + (unsigned)(ih * p.W + iw)) * (unsigned)p.Cin + (unsigned)(alh * 8)) * 2u;
       }
@@ -186,9 +179,8 @@ __global__ __launch_bounds__(768) void conv_pg_kernel(const ConvP p, const int k
     enter_tap();
     auto advance = [&]() {
       f_n++;
-      if constexpr (DBG & 1) { soff_b += (DBG & 2) ? 0 : b_step; return; }
       soff_a += a_step;
-      soff_b += (DBG & 2) ? 0 : b_step;
+      soff_b += b_step;
       if (++f_ci == spt) {
         f_ci = 0;
         soff_a = 0;
@@ -199,7 +191,7 @@ __global__ __launch_bounds__(768) void conv_pg_kernel(const ConvP p, const int k
     // the copies of one step into `stage`; steps past the end of the range copy zeros (every lane out of range): the counted waits
     // stay uniform
     auto copy_step = [&](int stage) {
-      const bool real = (DBG & 4) ? false : f_n < nkt;
+      const bool real = f_n < nkt;
       char* const st = gring + stage * STAGE;
 #pragma unroll
       for (int t = 0; t < 2; t++) {
@@ -215,70 +207,6 @@ __global__ __launch_bounds__(768) void conv_pg_kernel(const ConvP p, const int k
     auto wait_copies = [&]() {   // the newest S - 2 steps of this wave's copies may stay pending
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"((S - 2) * NI) : "memory");
     };
-    if constexpr (AF || (DBG & 16)) {
-      // ---- register-staged copies (experiment): the same LDS image, filled by buffer_load_b128 into a ring of S register sets and
-      // ds_write_b128 one step later instead of by LDS-DMA.  pump(n): store step n (set n % S) into stage n % S, then request step
-      // n + S into the freed set
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-      u32x4 rg[S][NI];
-      const float s_a = AF ? f16_scale_of(*p.f16_sx) : 1.f;
-      auto load_step = [&](auto setc) {
-        constexpr int set = decltype(setc)::value;
-        const bool real = f_n < nkt;
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-          const int va = (int)(real ? vo_a[t] : PG_OOB);
-          rg[set][2 * t] = __builtin_amdgcn_raw_buffer_load_b128(rs_a0, va, soff_a, 0);
-          rg[set][2 * t + 1] = __builtin_amdgcn_raw_buffer_load_b128(rs_a1, AF ? va + 16 : va, soff_a, 0);   // (AF: the lane's channels 4 .. 7)
-        }
-#pragma unroll
-        for (int i = 0; i < NBP; i++) rg[set][4 + i] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, (int)(real ? vo_b[i] : PG_OOB), soff_b, 0);
-        advance();
-      };
-      auto store_step = [&](auto setc, int stage) {
-        constexpr int set = decltype(setc)::value;
-        char* const st = gring + stage * STAGE + lane * 16;
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-          if constexpr (AF) {   // eight fp32 channels of the lane's row -> their (h, l) terms: the split of mmt_split_planes_f16, here
-            uint2 o0[2], o1[2];
-            split4h(__builtin_bit_cast(f32x4, rg[set][2 * t]), s_a, o0);
-            split4h(__builtin_bit_cast(f32x4, rg[set][2 * t + 1]), s_a, o1);
-            *(u32x4*)(st + (2 * sub + t) * 1024) = u32x4{o0[0].x, o0[0].y, o1[0].x, o1[0].y};
-            *(u32x4*)(st + PA + (2 * sub + t) * 1024) = u32x4{o0[1].x, o0[1].y, o1[1].x, o1[1].y};
-          } else {
-            *(u32x4*)(st + (2 * sub + t) * 1024) = rg[set][2 * t];
-            *(u32x4*)(st + PA + (2 * sub + t) * 1024) = rg[set][2 * t + 1];
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < NBP; i++) *(u32x4*)(st + dst_b[i]) = rg[set][4 + i];
-      };
-      auto pump = [&](auto setc) {
-        constexpr int set = decltype(setc)::value;
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((S - 1) * NI) : "memory");   // the set's loads (S slots old) have arrived
-        store_step(setc, set);
-        load_step(setc);
-      };
-      pg_unroll<0, S>([&](auto ic) { load_step(ic); });
-      if (!guard_bad()) {
-        pg_unroll<0, S - 1>([&](auto ic) { pump(ic); });   // steps 0 .. S - 2 into stages 0 .. S - 2
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                    // (0) step 0 has landed
-        pump(std::integral_constant<int, S - 1>{});
-        for (int kt = 0; kt < nkt_max; kt += S) {
-          pg_unroll<0, S>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            if (i == 0 || kt + i < nkt_max) {
-              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the stores of the previous slot are in LDS
-              __builtin_amdgcn_s_barrier();
-              pump(ic);
-            }
-          });
-        }
-      }
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    } else {
 #pragma unroll
     for (int t = 0; t < S - 1; t++) copy_step(t);      // prologue: steps 0 .. S - 2 into stages 0 .. S - 2
     if (!guard_bad()) {
@@ -299,7 +227,6 @@ __global__ __launch_bounds__(768) void conv_pg_kernel(const ConvP p, const int k
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the zero copies of the tail steps land before LDS is reused
-    }
   } else {
     // ================================================================ matrix wave
     // fragment reads: row = lane & 31 of a 32-row block, 16-byte half (lane >> 5) ^ ((row >> 3) & 1)
@@ -336,7 +263,7 @@ __global__ __launch_bounds__(768) void conv_pg_kernel(const ConvP p, const int k
 #pragma unroll
             for (int b = 0; b < 2; b++) {
               acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[qa][a], fb[qb][b], acc[a][b], 0, 0, 0);
-              if (j < 8) { if constexpr (!(DBG & 8)) fread(j, st_next, fan, fbn); }
+              if (j < 8) fread(j, st_next, fan, fbn);
               j++;
               __builtin_amdgcn_sched_barrier(0);
             }
@@ -348,10 +275,6 @@ __global__ __launch_bounds__(768) void conv_pg_kernel(const ConvP p, const int k
       f16x8 faP[2][2], fbP[2][2], faQ[2][2], fbQ[2][2];
 #pragma unroll
       for (int i = 0; i < 8; i++) fread(i, 0, faP, fbP);
-      if constexpr (DBG & 8) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) fread(i, 1, faQ, fbQ);
-      }
       for (int kt = 0; kt < nkt_max; kt += U) {
         pg_unroll<0, U>([&](auto ic) {
           constexpr int i = decltype(ic)::value;
@@ -660,7 +583,7 @@ void pg_plan(const ConvP& p, int& rows, int& ksplit) {
   if (e && atoi(e) == 0) ksplit = 1;
 }
 
-template <int WM, int KG, int S, int DBG = 0, bool AF = false>
+template <int WM, int KG, int S>
 int launch_pg(const ConvP& p, hipStream_t s, int ksplit) {
   constexpr int BM = 64 * WM;
   const int tiles = mmt_cdiv(p.M, BM) * mmt_cdiv(p.Cout, 128);
@@ -672,7 +595,7 @@ int launch_pg(const ConvP& p, hipStream_t s, int ksplit) {
   constexpr size_t ring = (size_t)S * KG * (BM * 64 + 2 * 128 * 32), xch = KG > 1 ? (size_t)4 * (KG - 1) * 4 * (128 * WM) * 16 : 0;
   constexpr size_t lds = ring > xch ? ring : xch;
   static_assert(lds <= 160 * 1024, "LDS");
-  auto kern = conv_pg_kernel<WM, KG, S, DBG, AF>;
+  auto kern = conv_pg_kernel<WM, KG, S>;
   static bool done = false;   // per instantiation
   if (!done) {
     const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -761,61 +684,15 @@ extern "C" int mmt_conv_forward_pg(const mmt_conv_args* a, const float* s_x, con
   ConvP p;
   int e = fill(p, a);
   if (e) return e;
-  // x_planes null: the A operand is read from x itself and split by the kernel's copy waves; s_x then points to max |x|
-  const bool af = p.xpl == nullptr;
-  if (af) {
-    if (!p.x || ((size_t)p.x & 15)) return MMT_EINVAL;
-    p.xpl = (const unsigned short*)p.x; p.xpl_stride = 0; p.xpl_rb = 0;   // (the shape test below wants an aligned pointer)
-  }
-  if (!p.y || !s_x || !s_w || precision() != 3 || !pg_shape(p)) return MMT_EINVAL;
+  if (!p.xpl || !p.y || !s_x || !s_w || precision() != 3 || !pg_shape(p)) return MMT_EINVAL;
   if (p.M == 0 || p.Cout == 0) return 0;
-  p.f16_sx = s_x; p.f16_sw = s_w; p.f16_ax = af ? 1 : 0;
+  p.f16_sx = s_x; p.f16_sw = s_w;
   int rows, ks;
   pg_plan(p, rows, ks);
   if (tile_rows == 64 || tile_rows == 128 || tile_rows == 256) rows = tile_rows; else if (tile_rows != 0) return MMT_EINVAL;
   if (ksplit > 0) ks = ksplit;
   if (ks < 1 || ks * (256 / rows) > (p.K >> 4)) return MMT_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-#ifdef MMT_PG_ABLATE   // (tools only: `make ablate` -> libmmtpsm_ablate.so for tools/bench_pg.py --ablate; the product library carries no DBG arm)
-  if (const char* d = af ? nullptr : getenv("MMT_PG_DBG")) {   // ablations of the main loop (wrong results; tools/bench_pg.py --ablate)
-    const int dbg = atoi(d);
-    if (dbg == 32 || dbg == 64) {
-      if (rows == 256) return dbg == 32 ? launch_pg<4, 1, 4, 32>(p, s, ks) : launch_pg<4, 1, 4, 64>(p, s, ks);
-      if (rows == 64) return dbg == 32 ? launch_pg<1, 4, 3, 32>(p, s, ks) : launch_pg<1, 4, 3, 64>(p, s, ks);
-    }
-    if (dbg == 16) {
-      if (rows == 256) return launch_pg<4, 1, 4, 16>(p, s, ks);
-      if (rows == 128) return launch_pg<2, 2, 4, 16>(p, s, ks);
-      return launch_pg<1, 4, 3, 16>(p, s, ks);
-    }
-    if (rows == 64) switch (dbg) {
-      case 1: return launch_pg<1, 4, 3, 1>(p, s, ks);
-      case 2: return launch_pg<1, 4, 3, 2>(p, s, ks);
-      case 3: return launch_pg<1, 4, 3, 3>(p, s, ks);
-      case 4: return launch_pg<1, 4, 3, 4>(p, s, ks);
-      case 8: return launch_pg<1, 4, 3, 8>(p, s, ks);
-      case 12: return launch_pg<1, 4, 3, 12>(p, s, ks);
-      default: break;
-    }
-    if (rows == 256) switch (dbg) {
-      case 1: return launch_pg<4, 1, 4, 1>(p, s, ks);
-      case 2: return launch_pg<4, 1, 4, 2>(p, s, ks);
-      case 4: return launch_pg<4, 1, 4, 4>(p, s, ks);
-      case 8: return launch_pg<4, 1, 4, 8>(p, s, ks);
-      case 12: return launch_pg<4, 1, 4, 12>(p, s, ks);
-      default: break;
-    }
-  }
-#endif
-  if (af) {
-#ifdef MMT_PG_ABLATE   // (round-5 experiment, slower than planes + a split pass and 144 live registers of copy ring: tools build only)
-    if (rows == 256) return launch_pg<4, 1, 4, 0, true>(p, s, ks);
-    if (rows == 128) return launch_pg<2, 2, 4, 0, true>(p, s, ks);
-    return launch_pg<1, 4, 3, 0, true>(p, s, ks);
-#else
-    return MMT_EINVAL;
-#endif
-  }
   if (rows == 256) return launch_pg<4, 1, 4>(p, s, ks);
   if (rows == 128) return launch_pg<2, 2, 4>(p, s, ks);
   return launch_pg<1, 4, 3>(p, s, ks);

@@ -29,11 +29,6 @@ struct ConvP {
   // w_src / w_src_scale: where the fp32 weights of a planes-only (data-gradient) call come from (see conv_slow_tile)
   const float* guard_x; const float* guard_dy;
   const float* w_src; const float* w_src_scale;
-  // weight gradient over TWO segments of pixels (round 4: the two student passes of a step share every weight; their activations
-  // and gradients are separate tensors of one shape): blocks with z >= seg_z work on (x2, dy2) with that segment's own scales /
-  // statistics slots; seg_z == 0: one segment
-  const float* x2; const float* dy2; const float* f16_sx2; const float* f16_sw2; const float* guard_x2; const float* guard_dy2;
-  int seg_z;
   int staged_epilogue;   // (A/B timing: MMT_DIRECT_EPI=0) the tiled and tap-strip kernels leave through the LDS-staged epilogue
   int xpl_rb;            // xpl is row-blocked: [N * H][Cin / 16][W][16] per plane (conv_pg_kernel only; mmt_conv_args.x_planes_layout)
   // round 6: y also as two row-blocked fp16 planes of y * *yrb_s ([N Ho][Cout / 16][Wo][16]), written by the epilogue for a plane-fed

@@ -37,12 +37,6 @@ __device__ __forceinline__ f16x8 tr_pair(const char* p) {   // 8 consecutive pix
   return __builtin_bit_cast(f16x8, v);
 }
 
-#ifdef MMT_PG_ABLATE
-#define WGPL_DBG(p) ((p).dbg)
-#else
-#define WGPL_DBG(p) 0
-#endif
-
 struct WgP {
   const float* x; const float* dy;                       // fp32 tensors (the slow, exact path)
   const unsigned short* xpl; long xpl_stride;            // row-blocked planes of x * s_x
@@ -51,8 +45,6 @@ struct WgP {
   const float* guard_x; const float* guard_dy;           // statistics slots (range guard) or null
   const float* rowscale; float* dw; float* ws; float* dbias;
   int N, H, W, Cin, Cout, KH, KW, pad, ksplit;
-  int dbg;   // (tools build only, -DMMT_PG_ABLATE = `make ablate`: 1 = every copy out of range -- zeros, no memory traffic; 2 = no fragment
-             // reads.  Wrong results; the product library compiles the arms out, WGPL_DBG below)
   int lag;   // round 6: bit 0 / bit 1 -- the planes of x / of dy were written by their producer's epilogue with a scale fixed beforehand
 };
 
@@ -111,7 +103,7 @@ __device__ __forceinline__ void wgrad_pl_body(const WgP& p, const int bid_in, co
     const int px = lane >> 1;
     int f_t = 0;                                       // super-steps issued so far
     auto copy_step = [&](int stage) {
-      const bool real = f_t < nt && !(WGPL_DBG(p) & 1);
+      const bool real = f_t < nt;
       const int t = t0 + (real ? f_t : 0);
       const int row = t / segs, w0 = (t - row * segs) << 5;   // image row (n H + h), first pixel
       unsigned vo = (unsigned)lane * 16u;
@@ -163,7 +155,6 @@ __device__ __forceinline__ void wgrad_pl_body(const WgP& p, const int bid_in, co
           for (int q = 0; q < 2; q++)
 #pragma unroll
             for (int a = 0; a < 2; a++) {
-              if ((WGPL_DBG(p) & 2) && t > 0) continue;
               fa[q][a] = tr_pair(sa + (q * 8 + a * 2) * WG_BLK + k2 * 512);
               fb[q][a] = tr_pair(sb + (q * 8 + a * 2) * WG_BLK + k2 * 512);
             }
@@ -369,7 +360,7 @@ int wgpl_splits(const mmt_conv_args* a) {
   if (e && atoi(e) == 0) return 0;
   const long T = ((long)a->N * a->H * a->W) >> 5;
   const long tiles = (long)(a->Cout >> 7) * ((long)a->KH * a->KW * a->Cin >> 7);
-  static const long target = getenv("MMT_WGPL_BLOCKS") ? atol(getenv("MMT_WGPL_BLOCKS")) : 256;   // (blocks per launch the pixel ranges aim at; the switch: profiles/r06_history.md)
+  constexpr long target = 256;   // (blocks per launch the pixel ranges aim at: profiles/r06_history.md)
   long ks = target / tiles;
   if (ks > T / 8) ks = T / 8;     // >= 4 super-steps per group and range
   if (ks < 1) ks = 1;
@@ -420,7 +411,7 @@ int launch_wgpl_group(const WgPlJob* jobs, int n, hipStream_t s) {
     p.s_x = j.s_x; p.s_dy = j.s_dy;
     p.guard_x = (const float*)a->f16_guard_x; p.guard_dy = (const float*)a->f16_guard_dy;
     p.rowscale = j.rowscale; p.dw = j.dw; p.ws = j.ws; p.dbias = j.dbias;
-    p.dbg = 0; p.lag = a->x_planes_lag;
+    p.lag = a->x_planes_lag;
     p.N = a->N; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.KH = a->KH; p.KW = a->KW; p.pad = a->pad; p.ksplit = j.ksplit;
     g.first[i] = nb;
     const int blocks = (a->Cout >> 7) * ((a->KH * a->KW * a->Cin) >> 7) * j.ksplit;
@@ -458,11 +449,6 @@ extern "C" int mmt_conv_wgrad_planes(const mmt_conv_args* a, const float* dy, co
   p.s_x = s_x; p.s_dy = s_dy;
   p.guard_x = (const float*)a->f16_guard_x; p.guard_dy = (const float*)a->f16_guard_dy;
   p.rowscale = rowscale; p.dw = dw; p.ws = workspace; p.dbias = dbias;
-#ifdef MMT_PG_ABLATE
-  p.dbg = getenv("MMT_WGPL_DBG") ? atoi(getenv("MMT_WGPL_DBG")) : 0;
-#else
-  p.dbg = 0;
-#endif
   p.lag = a->x_planes_lag;
   p.N = a->N; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.KH = a->KH; p.KW = a->KW; p.pad = a->pad; p.ksplit = ks;
   const int NP = a->KH * a->KW * a->Cin;

@@ -422,7 +422,7 @@ __device__ __forceinline__ void wgrad_slow_fill(const float* __restrict__ x, con
 // tile is divided by s_x s_dy where it is stored (directly, or in wgrad_reduce_kernel for the split form)
 // (tx, ty, tz, lin: the grid of this launch and the block's linear index in it -- or, in a grouped launch, of its ITEM)
 template <int NS, int MODE, bool VEC4, int BF = 0, bool F16 = false>
-__device__ __forceinline__ void conv_wgrad_pipe_body(const ConvP& p_in, const float* __restrict__ dy_in,
+__device__ __forceinline__ void conv_wgrad_pipe_body(const ConvP& p_in, const float* __restrict__ dy,
                                                      const float* __restrict__ rowscale,
                                                      float* __restrict__ dw, int m_per_split,
                                                      float* __restrict__ ws, float* __restrict__ dbias,
@@ -447,20 +447,10 @@ __device__ __forceinline__ void conv_wgrad_pipe_body(const ConvP& p_in, const fl
     by = t % ty;
     bz = t / ty;
   }
-  // two-segment form (p_in.seg_z > 0): slices z >= seg_z belong to the second (x, dy) pair -- same shapes, its own scales
-  ConvP p = p_in;
-  const float* __restrict__ dy = dy_in;
-  int bzl = bz;
-  if constexpr (F16) {
-    if (p_in.seg_z > 0 && bz >= p_in.seg_z) {
-      p.x = p_in.x2; dy = p_in.dy2; p.f16_sx = p_in.f16_sx2; p.f16_sw = p_in.f16_sw2;
-      p.guard_x = p_in.guard_x2; p.guard_dy = p_in.guard_dy2;
-      bzl = bz - p_in.seg_z;
-    }
-  }
+  const ConvP p = p_in;   // (a copy: in a grouped launch p_in is an item of the kernel arguments picked by a run-time index)
   const int co0 = by * 128, n0 = bx * 128;
   const int NP = p.KH * p.KW * p.Cin;
-  const int ms = bzl * m_per_split;
+  const int ms = bz * m_per_split;
   const int me = min(p.M, ms + m_per_split);
   if (ms >= me) return;
   const int HoWo = p.Ho * p.Wo;
@@ -799,11 +789,11 @@ __device__ __forceinline__ void conv_wgrad_pipe_body(const ConvP& p_in, const fl
 }
 
 template <int NS, int MODE, bool VEC4, int BF = 0, bool F16 = false>
-__global__ __launch_bounds__(256, 2) void conv_wgrad_pipe_kernel(const ConvP p_in, const float* __restrict__ dy_in,
+__global__ __launch_bounds__(256, 2) void conv_wgrad_pipe_kernel(const ConvP p, const float* __restrict__ dy,
                                                                  const float* __restrict__ rowscale,
                                                                  float* __restrict__ dw, int m_per_split,
                                                                  float* __restrict__ ws, float* __restrict__ dbias) {
-  conv_wgrad_pipe_body<NS, MODE, VEC4, BF, F16>(p_in, dy_in, rowscale, dw, m_per_split, ws, dbias, (int)gridDim.x, (int)gridDim.y,
+  conv_wgrad_pipe_body<NS, MODE, VEC4, BF, F16>(p, dy, rowscale, dw, m_per_split, ws, dbias, (int)gridDim.x, (int)gridDim.y,
                                                 (int)gridDim.z, (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)));
 }
 
@@ -880,18 +870,9 @@ extern "C" int mmt_conv_wgrad_splits(const mmt_conv_args* a) {
   // all blocks of a launch run equally long: fill the 512 resident slots (256 CUs x 2 blocks) ONCE.  (640 = 1.25
   // rounds cost a second, 20 %-full round: 92 -> 105 TFLOP/s fp32, 103 -> 136 split-bf16 on the FPN 3x3 shapes)
   const long tiles = (long)tx * ty;
-  static const int slots = getenv("MMT_WG_SLOTS") ? atoi(getenv("MMT_WG_SLOTS")) : 512;   // (tuned: profiles/r04_dispatch_sweep.txt; in the step: r04 / r06 history; the switch is for that sweep)
+  constexpr int slots = 512;    // (tuned: profiles/r04_dispatch_sweep.txt; in the step: r04 / r06 history)
   constexpr int min_px = 512;   // (tuned: profiles/r04_dispatch_sweep.txt; in the step: profiles/r04_history.md)
   int split = (int)(tiles >= slots ? 1 : slots / tiles);
-  if (a->x2) {   // two segments of p.M pixels each: the same number of blocks reduces twice the pixels; an even number of slices
-    const int max2 = mmt_cdiv(2 * p.M, min_px);
-    if (split > max2) split = max2;
-    int half = split / 2;
-    if (half < 1) half = 1;
-    int mps2 = mmt_cdiv(p.M, half);
-    mps2 = (mps2 + 31) / 32 * 32;
-    return 2 * mmt_cdiv(p.M, mps2);
-  }
   const int max_split = mmt_cdiv(p.M, min_px);  // at least min_px / 16 k-tiles per block
   if (split > max_split) split = max_split;
   if (split < 1) split = 1;
@@ -911,11 +892,8 @@ extern "C" int mmt_conv_wgrad(const mmt_conv_args* a, const float* dy, const flo
   const int NP = p.KH * p.KW * p.Cin;
   const int tx = mmt_cdiv(NP, 128), ty = mmt_cdiv(p.Cout, 128);
   const int split = mmt_conv_wgrad_splits(a);
-  const bool two = a->x2 != nullptr;
-  int mps = mmt_cdiv(p.M, two ? split / 2 : split);
+  int mps = mmt_cdiv(p.M, split);
   mps = (mps + 31) / 32 * 32;
-  if (two && (!a->dy2 || !a->f16_x_amax || !a->f16_dy_amax || !a->f16_x_amax2 || !a->f16_dy_amax2 || split != 2 * mmt_cdiv(p.M, mps)))
-    return MMT_EINVAL;   // the two-segment form exists on the fp16 split only
   if (split > 1 && !workspace) return MMT_EINVAL;
   float* ws = split > 1 ? workspace : nullptr;
   const bool fast = (p.Cout & 3) == 0 && p.Wo >= 8 && p.Ho >= 8;
@@ -929,12 +907,6 @@ extern "C" int mmt_conv_wgrad(const mmt_conv_args* a, const float* dy, const flo
       return MMT_EINVAL;
     p.f16_sx = (const float*)a->f16_x_amax;
     p.f16_sw = (const float*)a->f16_dy_amax;
-    if (two) {
-      p.x2 = (const float*)a->x2; p.dy2 = (const float*)a->dy2;
-      p.f16_sx2 = (const float*)a->f16_x_amax2; p.f16_sw2 = (const float*)a->f16_dy_amax2;
-      p.guard_x2 = (const float*)a->f16_guard_x2; p.guard_dy2 = (const float*)a->f16_guard_dy2;
-      p.seg_z = split / 2;
-    }
     const dim3 grid(tx, ty, split);
     const int mode = !(p.Wo >= 8 && p.Ho >= 8) ? 0 : ((p.Wo & 3) == 0 ? 2 : 1);
 #define WGF(MODE) hipLaunchKernelGGL((conv_wgrad_pipe_kernel<2, MODE, true, 0, true>), grid, dim3(256), (size_t)65536, s, p, dy, rowscale, dw, mps, ws, dbias)   /* 3 stages of 16 KB <= the 64 KB epilogue tile */
@@ -1003,22 +975,17 @@ extern "C" int mmt_conv_wgrad(const mmt_conv_args* a, const float* dy, const flo
 // <= 12 on wgrad_pl_group_kernel, the fp16-split jobs without planes in groups of <= 6 per pixel-decode mode on
 // conv_wgrad_pipe_group_kernel, ONE reduce launch for every slab of the batch; whatever fits neither (and any group of one) goes out
 // as the single launch it always was.  Inside a group the tiles of all layers fill the chip together, so a layer needs fewer pixel
-// ranges than alone -- a quarter of them by default (see wg_plan): longer reductions per block, a quarter of the slab traffic.
+// ranges than alone -- a quarter of them (see wg_plan): longer reductions per block, a quarter of the slab traffic.
 // Summation order: fixed by (the batch's composition, shapes) -- repeatable, but not the single launches' order when ranges differ.
 namespace {
-// jobs per grouped launch (MMT_WGRAD_GROUP_CAP_PL / _PIPE: the sweep of profiles/r06_history.md; at most what the kernel-argument segment holds)
-static int wg_cap(int k) {
-  const char* e = getenv(k == 1 ? "MMT_WGRAD_GROUP_CAP_PL" : "MMT_WGRAD_GROUP_CAP_PIPE");
-  const int mx = k == 1 ? 12 : WGP_MAXG;
-  const int v = e ? atoi(e) : mx;
-  return v < 1 ? 1 : (v > mx ? mx : v);
-}
+// jobs per grouped launch: at most what the kernel-argument segment holds (the sweep of profiles/r06_history.md)
+constexpr int WG_CAP_PL = 12, WG_CAP_PIPE = WGP_MAXG;
 struct WgJobPlan { int kind; int split; int mps; long ws_off; };   // kind 0: single launch (mmt_conv_wgrad / _planes); 1: plane-fed group; 2 + mode: pipe group
 constexpr int WGJ_MAX = 96;
 
 static bool wg_job_pipe_ok(const mmt_wgrad_job& j, ConvP& p) {
   if (fill(p, &j.a) || !j.dy || !j.dw || !p.cin4 || p.M == 0 || p.Cout == 0) return false;
-  if (!j.a.f16_x_amax || !j.a.f16_dy_amax || j.a.x2 || precision() != 3 || p.io || (p.Cout & 3)) return false;
+  if (!j.a.f16_x_amax || !j.a.f16_dy_amax || precision() != 3 || p.io || (p.Cout & 3)) return false;
   return (long)p.N * p.H * p.W * p.Cin * 4 < (1L << 31) && (long)p.M * p.Cout * 4 < (1L << 31);
 }
 
@@ -1026,20 +993,16 @@ static bool wg_job_pipe_ok(const mmt_wgrad_job& j, ConvP& p) {
 static long wg_plan(const mmt_wgrad_job* jobs, int n, WgJobPlan* plan) {
   const char* e = getenv("MMT_WGRAD_GROUP");   // read per call (A/B timing, the bit-equality tests of the schedules)
   const bool on = !(e && atoi(e) == 0);
-  // Pixel ranges per job inside a group: 1 / WG_DIV of what the job would use ALONE (MMT_WGRAD_GROUP_DIV; 0 = as few as fill the chip
-  // as a group).  Measured in the step (profiles/r06_history.md section 7): filling the chip as a group makes blocks that own a CU for
-  // ~150 us and hold up the step stream's latency-bound chain (+2 ms); the jobs' own ranges only save launches and reduces (-0.3 ms);
-  // a quarter of them is the optimum (-0.5 ... -0.75 ms): blocks four times as long, a quarter of the slab traffic, still short
-  const char* dv = getenv("MMT_WGRAD_GROUP_DIV");
-  const int sdiv = dv ? atoi(dv) : 4;
-  const bool solo = sdiv > 0;
-  const int sdiv_pl = getenv("MMT_WGRAD_GROUP_PL") ? atoi(getenv("MMT_WGRAD_GROUP_PL")) : sdiv;       // (sweep: the two kinds apart)
-  const int sdiv_pipe = getenv("MMT_WGRAD_GROUP_PIPE") ? atoi(getenv("MMT_WGRAD_GROUP_PIPE")) : sdiv;
+  // Pixel ranges per job inside a group: 1 / WG_DIV of what the job would use ALONE.  Measured in the step (profiles/r06_history.md
+  // section 7): filling the chip as a group makes blocks that own a CU for ~150 us and hold up the step stream's latency-bound chain
+  // (+2 ms); the jobs' own ranges only save launches and reduces (-0.3 ms); a quarter of them is the optimum (-0.5 ... -0.75 ms):
+  // blocks four times as long, a quarter of the slab traffic, still short
+  constexpr int WG_DIV = 4;
   int kind[WGJ_MAX];
   for (int i = 0; i < n; i++) {
     ConvP p;
     kind[i] = 0;
-    if (on && jobs[i].x_planes && jobs[i].dy_planes && !jobs[i].a.x2 && wgpl_eligible_splits(&jobs[i].a) > 0) kind[i] = 1;
+    if (on && jobs[i].x_planes && jobs[i].dy_planes && wgpl_eligible_splits(&jobs[i].a) > 0) kind[i] = 1;
     else if (on && wg_job_pipe_ok(jobs[i], p)) kind[i] = 2 + (!(p.Wo >= 8 && p.Ho >= 8) ? 0 : ((p.Wo & 3) == 0 ? 2 : 1));
   }
   // a weight shared by several jobs of the batch (the RPN head over the pyramid levels): only its FIRST job may ride in a group -- the
@@ -1054,56 +1017,40 @@ static long wg_plan(const mmt_wgrad_job* jobs, int n, WgJobPlan* plan) {
     if (cnt == 1) kind[last] = 0;
   }
   long ws = 0;
-  for (int k = 1; k <= 4; k++) {
-    const int cap = wg_cap(k), target = k == 1 ? 256 : 512;
-    int idx[WGJ_MAX], m = 0;
-    for (int i = 0; i < n; i++) if (kind[i] == k) idx[m++] = i;
-    for (int c0 = 0; c0 < m; c0 += cap) {
-      const int c1 = c0 + cap < m ? c0 + cap : m;   // (the launcher cuts its groups at the same counts)
-      long tiles = 0;
-      for (int c = c0; c < c1; c++) {
-        const mmt_conv_args& a = jobs[idx[c]].a;
-        const int NP = a.KH * a.KW * a.Cin;
-        tiles += k == 1 ? (long)(a.Cout >> 7) * (NP >> 7) : (long)mmt_cdiv(NP, 128) * mmt_cdiv(a.Cout, 128);
+  for (int k = 1; k <= 4; k++)
+    for (int i = 0; i < n; i++) {
+      if (kind[i] != k) continue;
+      const mmt_conv_args& a = jobs[i].a;
+      const int NP = a.KH * a.KW * a.Cin;
+      WgJobPlan& pl = plan[i];
+      pl.kind = k; pl.mps = 0;
+      if (k == 1) {
+        long ks = (wgpl_eligible_splits(&a) + WG_DIV - 1) / WG_DIV;
+        const long T = wgpl_super_steps(&a);
+        if (ks > T / 8) ks = T / 8;
+        if (ks < 1) ks = 1;
+        pl.split = (int)ks;
+      } else {
+        const int M = a.N * a.Ho * a.Wo;
+        long sp = (mmt_conv_wgrad_splits(&a) + WG_DIV - 1) / WG_DIV;
+        const long mx = mmt_cdiv(M, 512);
+        if (sp > mx) sp = mx;
+        if (sp < 1) sp = 1;
+        int mps = mmt_cdiv(M, (int)sp);
+        mps = (mps + 31) / 32 * 32;
+        pl.mps = mps;
+        pl.split = mmt_cdiv(M, mps);
       }
-      long f = target / (tiles > 0 ? tiles : 1);
-      if (f < 1) f = 1;
-      if (solo) f = 1L << 20;
-      for (int c = c0; c < c1; c++) {
-        const int i = idx[c];
-        const mmt_conv_args& a = jobs[i].a;
-        const int NP = a.KH * a.KW * a.Cin;
-        WgJobPlan& pl = plan[i];
-        pl.kind = k; pl.mps = 0;
-        if (k == 1) {
-          long ks = f, T = wgpl_super_steps(&a);
-          if (solo) ks = (wgpl_eligible_splits(&a) + sdiv_pl - 1) / sdiv_pl;
-          if (ks > T / 8) ks = T / 8;
-          if (ks < 1) ks = 1;
-          pl.split = (int)ks;
-        } else {
-          const int M = a.N * a.Ho * a.Wo;
-          long sp = solo ? (mmt_conv_wgrad_splits(&a) + sdiv_pipe - 1) / sdiv_pipe : f;
-          const long mx = mmt_cdiv(M, 512);
-          if (sp > mx) sp = mx;
-          if (sp < 1) sp = 1;
-          int mps = mmt_cdiv(M, (int)sp);
-          mps = (mps + 31) / 32 * 32;
-          pl.mps = mps;
-          pl.split = mmt_cdiv(M, mps);
-        }
-        pl.ws_off = ws;
-        if (pl.split > 1) ws += (long)pl.split * a.Cout * NP;
-      }
+      pl.ws_off = ws;
+      if (pl.split > 1) ws += (long)pl.split * a.Cout * NP;
     }
-  }
   for (int i = 0; i < n; i++) {
     if (kind[i] != 0) continue;
     WgJobPlan& pl = plan[i];
     const mmt_conv_args& a = jobs[i].a;
     pl.kind = 0; pl.mps = 0;
     int sp = 0;
-    if (jobs[i].x_planes && jobs[i].dy_planes && !a.x2) sp = wgpl_eligible_splits(&a);
+    if (jobs[i].x_planes && jobs[i].dy_planes) sp = wgpl_eligible_splits(&a);
     if (sp <= 0) sp = mmt_conv_wgrad_splits(&a);
     pl.split = sp < 1 ? 1 : sp;
     pl.ws_off = ws;
@@ -1131,7 +1078,7 @@ extern "C" int mmt_conv_wgrad_group(const mmt_wgrad_job* jobs, int n, float* wor
   int nred = 0;
   // plane-fed groups
   {
-    WgPlJob g[12];
+    WgPlJob g[WG_CAP_PL];
     int m = 0;
     auto flush = [&]() -> int {
       if (m == 0) return 0;
@@ -1147,7 +1094,7 @@ extern "C" int mmt_conv_wgrad_group(const mmt_wgrad_job* jobs, int n, float* wor
                        plan[i].split};
       if (plan[i].split > 1)
         red[nred++] = WgReduceItem{ws, j.rowscale, j.dw, plan[i].split, j.a.Cout, j.a.KH * j.a.KW * j.a.Cin, 0};
-      if (m == wg_cap(1)) { const int e = flush(); if (e) return e; }
+      if (m == WG_CAP_PL) { const int e = flush(); if (e) return e; }
     }
     const int e = flush();
     if (e) return e;
@@ -1183,7 +1130,7 @@ extern "C" int mmt_conv_wgrad_group(const mmt_wgrad_job* jobs, int n, float* wor
       g.first[g.n] = nb;
       nb += (it.tx * it.ty * it.tz + 7) & ~7;
       g.n++;
-      if (g.n == wg_cap(2)) { const int e = flush(); if (e) return e; }
+      if (g.n == WG_CAP_PIPE) { const int e = flush(); if (e) return e; }
     }
     const int e = flush();
     if (e) return e;
@@ -1195,7 +1142,7 @@ extern "C" int mmt_conv_wgrad_group(const mmt_wgrad_job* jobs, int n, float* wor
     const mmt_wgrad_job& j = jobs[i];
     float* ws = plan[i].split > 1 ? workspace + plan[i].ws_off : nullptr;
     int e = 1;
-    if (j.x_planes && j.dy_planes && !j.a.x2)
+    if (j.x_planes && j.dy_planes)
       e = mmt_conv_wgrad_planes(&j.a, j.dy, j.x_planes, j.x_plane_stride, j.dy_planes, j.dy_plane_stride, j.s_x, j.s_dy, j.rowscale, j.dw,
                                 j.dbias, ws, stream);
     if (e == 1) e = mmt_conv_wgrad(&j.a, j.dy, j.rowscale, j.dw, j.dbias, ws, stream);

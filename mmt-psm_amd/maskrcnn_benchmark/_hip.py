@@ -33,8 +33,7 @@ class ConvArgs(ctypes.Structure):
                 ("y_planes", c_void_p), ("y_plane_stride", ctypes.c_long), ("io_bf16", c_int), ("y_amax", c_void_p),
                 ("f16_x_amax", c_void_p), ("f16_dy_amax", c_void_p), ("y_amax_stats", c_int),
                 ("f16_guard_x", c_void_p), ("f16_guard_dy", c_void_p), ("w_src", c_void_p), ("w_src_scale", c_void_p),
-                ("x2", c_void_p), ("dy2", c_void_p), ("f16_x_amax2", c_void_p), ("f16_dy_amax2", c_void_p),
-                ("f16_guard_x2", c_void_p), ("f16_guard_dy2", c_void_p), ("x_planes_layout", c_int),
+                ("x_planes_layout", c_int),
                 ("y_rb", c_void_p), ("y_rb_stride", ctypes.c_long), ("y_rb_scale", c_void_p), ("y_amax_next", c_void_p),
                 ("x_planes_lag", c_int), ("y_rb_rows", c_int)]
 
@@ -187,8 +186,6 @@ _lib = None
 # tool only) extends that to every conv / wgrad launch.
 PROFILE = None
 PROFILE_ALL = False
-# eligible 3x3 convolutions split their input into bf16 planes first and run on conv3x3_strip_kernel (csrc/conv_igemm.hip)
-AUTO_PLANES = True
 # bf16 STORAGE of the ResNet body's activations and activation gradients (BASELINE configs[4] "bf16 MFMA path"): only with
 # the bf16 arithmetic (mode 1).  The producers in layers/fused.py ask `bf16_storage()`; every consumer goes by the dtype
 # of the tensor it is handed.
@@ -202,7 +199,6 @@ _BF16_STORAGE = os.environ.get("MMT_BF16_STORAGE", "0") != "0"
 F16X2_DEFAULT = os.environ.get("MMT_F16X2", "1") != "0"
 F16X2 = F16X2_DEFAULT
 F16X2_TILED = True   # also the tiled kernel (1x1, small-map 3x3, fc), not only the strip kernel
-F16X2_DELAYED = False   # (tools) scale from the previous tensor of the role: one pass less, but the scale lags the data
 F16_STATS = {"wgrad": 0, "conv": 0, "tiled": 0, "pg": 0, "amax_pass": 0, "fallback": 0, "weight_pack": 0}   # launches that took the fp16 path (tools, tests)
 WGRAD_F16_MIN_ELEMS = 1 << 22
 _F16W = {}   # weight address -> (key, planes, device scale)
@@ -1411,7 +1407,7 @@ def split_planes(x, out=None):
 def planes_wanted_3x3(N, C, H, W, Cout):
     """would a 3x3 / stride 1 / pad 1 convolution (C -> Cout) over an (N, C, H, W) tensor run on the all-planes kernel?
     (asked by the PRODUCER of that tensor, which then writes the planes from its epilogue: conv_forward(want_planes=True))"""
-    if not AUTO_PLANES or get_conv_precision() != 3 or F16X2:   # (on the fp16 split no epilogue writes bf16 planes: consumers scale
+    if get_conv_precision() != 3 or F16X2:   # (on the fp16 split no epilogue writes bf16 planes: consumers scale
         return False                                              # the tensor themselves, conv_forward ignores the request)
     a = ConvArgs()
     a.x, a.w_planes = 16, 16  # placeholders: only the shape is looked at
@@ -1449,23 +1445,12 @@ def _plan_key(x, w, f16_src, stride, pad, relu, res, res_mode, mask):
              _PLAN_EPOCH[0]), src, src if base is None else base)
 
 
-RB_PG1X1 = os.environ.get("MMT_RB_WIDE", "0") != "0"   # 1x1 layers with K >= 512 on the plane-fed GEMM when their input carries a producer's planes
-
-
-def _epi_planes(x):
-    """does x carry row-blocked planes its producer's epilogue wrote for the whole tensor?"""
-    rb = getattr(x, "_mmt_rb", None)
-    return (rb is not None and len(rb) > 3 and rb[2] == x._version and rb[3] == "epi" and (len(rb) < 5 or rb[4] is None))
-
-
 def _conv_fast(x, w, scale, shift, stride, pad, relu, res, res_mode, mask, mask_scale, f16_src, rb_site=None):
     key, src, owner = _plan_key(x, w, f16_src, stride, pad, relu, res, res_mode, mask)
     plan = _PLAN.get(key) if key is not None else None
     if plan is None:
         return None
-    tmpl, kind, Cout, Ho, Wo, wref = plan[:6]
-    if kind == 0 and len(plan) > 6 and plan[6] and RB_PG1X1 and _epi_planes(x):
-        kind = 2   # (round 6: a long-K 1x1 layer whose input came with planes: the plane-fed GEMM, no split pass)
+    tmpl, kind, Cout, Ho, Wo, wref = plan
     if wref() is not owner or x.dtype != torch.float32 or (res is not None and res.dtype != torch.float32) or (
             mask is not None and mask.dtype != torch.float32):
         return None
@@ -1507,10 +1492,7 @@ def _conv_fast(x, w, scale, shift, stride, pad, relu, res, res_mode, mask, mask_
         _check(lib().mmt_conv_forward_pg(ctypes.byref(a), sx.data_ptr(), sw.data_ptr(), 0, 0, _stream()), "mmt_conv_forward_pg")
     else:             # tap-strip kernel: the same
         F16_STATS["conv"] += 1
-        if F16X2_DELAYED:
-            xp16, sx = f16_split(x, (wsrc.data_ptr(), flipped))
-        else:
-            xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x)
+        xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x)
         a.x_planes, a.x_plane_stride = xp16.data_ptr(), xp16.stride(0)
         _check(lib().mmt_conv3x3_strip_f16x2(ctypes.byref(a), sx.data_ptr(), sw.data_ptr(), _stream()), "mmt_conv3x3_strip_f16x2")
     y._mmt_amax = (slot, y._version)
@@ -1533,10 +1515,7 @@ def _plan_record(x, w, f16_src, stride, pad, relu, res, res_mode, mask, a, kind,
     t.mask_scale, t.io_bf16, t.y_amax_stats = 1.0, 0, 1
     if len(_PLAN) > 4096:
         _PLAN.clear()
-    # (7th: a 1x1 / stride-1 layer with K >= 512 the plane-fed GEMM takes -- chosen per call, when the input carries planes)
-    pg1 = bool(kind == 0 and t.KH == 1 and t.KW == 1 and t.stride == 1 and t.Cin >= 512 and t.res_mode <= 1 and t.N <= 4
-               and conv_pg_plan(t.N, t.Cin, t.H, t.W, t.Cout, 1, 1, 1, 0)[0] > 0)
-    _PLAN[key] = (bytes(t), kind, Cout, Ho, Wo, weakref.ref(owner), pg1)
+    _PLAN[key] = (bytes(t), kind, Cout, Ho, Wo, weakref.ref(owner))
 
 
 def _epilogue_bytes(y, res, res_mode, mask, mul):
@@ -1641,16 +1620,12 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
     if (f16t is not None and f16 is None and mul is None and out_stride == 1 and res_mode <= 1 and KH * KW >= 4
             and lib().mmt_conv_pg_wanted(ctypes.byref(a)) == 1):
         pg, f16t = f16t, None
-    elif (RB_PG1X1 and f16t is not None and f16 is None and mul is None and out_stride == 1 and res_mode <= 1 and KH == 1 and KW == 1
-          and stride == 1 and Cin >= 512 and N <= 4 and _epi_planes(x) and y_out is None
-          and conv_pg_plan(N, Cin, H, W, Cout, 1, 1, 1, 0)[0] > 0):
-        pg, f16t = f16t, None   # (round 6: a long-K 1x1 layer whose input came with its producer's planes)
     if f16 is not None:
         x_planes = None
     if want_planes and out_stride == 1 and y_out is None and Cout % 4 == 0 and not io:
         y_planes = torch.empty((3, y.numel()), dtype=torch.bfloat16, device=x.device)
         a.y_planes, a.y_plane_stride = y_planes.data_ptr(), y_planes.stride(0)
-    auto_split = x_planes is None and AUTO_PLANES and strip and f16 is None
+    auto_split = x_planes is None and strip and f16 is None
     if auto_split:
         # one pass over x; the 3x3 kernel then reads bf16 planes (9 taps x Cout/128 re-reads).  Allocated here, filled
         # below INSIDE the profiling bracket: the pass is part of this convolution's cost
@@ -1687,8 +1662,7 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
             ev[0].record()
         F16_STATS["pg"] += 1
         if fast_ok and not io:
-            # (a 1x1 layer is here because THIS input carried planes: its plan is the tiled kernel's, the plane-fed form chosen per call)
-            _plan_record(x, w, f16_src, stride, pad, relu, res, res_mode, mask, a, 2 if KH * KW >= 4 else 0, Cout, Ho, Wo)
+            _plan_record(x, w, f16_src, stride, pad, relu, res, res_mode, mask, a, 2, Cout, Ho, Wo)
         a.f16_guard_x = _guard(_amax_of(x))
         if pg[1]:
             a.w_src, a.w_src_scale = pg[0].data_ptr(), _p(pg[2])
@@ -1744,14 +1718,10 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
         F16_STATS["conv"] += 1
         if fast_ok and not io:
             _plan_record(x, w, f16_src, stride, pad, relu, res, res_mode, mask, a, 1, Cout, Ho, Wo)
-        if not F16X2_DELAYED:
-            a.f16_guard_x = _guard(_amax_of(x))
+        a.f16_guard_x = _guard(_amax_of(x))
         if f16[1]:
             a.w_src, a.w_src_scale = f16[0].data_ptr(), _p(f16[2])
-        if F16X2_DELAYED:
-            xp16, sx = f16_split(x, (f16[0].data_ptr(), f16[1]))
-        else:
-            xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x)
+        xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x)
         wp16, sw = f16_weight_planes(f16[0], f16[2], f16[1])
         a.x_planes, a.x_plane_stride = xp16.data_ptr(), xp16.stride(0)
         a.w_planes, a.w_plane_stride = wp16.data_ptr(), wp16.stride(0)
@@ -1841,11 +1811,8 @@ def conv_forward_pg(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, r
         a.w = wsrc.data_ptr()
     a.f16_guard_x = _guard(_amax_of(x))
     wp16, sw = f16_weight_planes(wsrc, fscale, flipped)
-    if xp == "fp32":   # no planes: the kernel's copy waves split the fp32 rows themselves (tools build of the library only: `make ablate`)
-        sx = _amax_of(x)[0]
-    else:
-        xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x) if xp is None else (tuple(xp) + (0, 0))[:4]
-        a.x_planes, a.x_plane_stride = xp16.data_ptr(), xp16.stride(0)
+    xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x) if xp is None else (tuple(xp) + (0, 0))[:4]
+    a.x_planes, a.x_plane_stride = xp16.data_ptr(), xp16.stride(0)
     a.w_planes, a.w_plane_stride = wp16.data_ptr(), wp16.stride(0)
     _check(lib().mmt_conv_forward_pg(ctypes.byref(a), sx.data_ptr(), sw.data_ptr(), int(tile_rows), int(ksplit), _stream()),
            "mmt_conv_forward_pg")
@@ -2008,18 +1975,6 @@ def wgrad_prepare(x, dy):
         _amax_of(nhwc(dy))
 
 
-def wgrad_pair_ok(x, dy, x2, dy2):
-    """can the weight gradients of (x, dy) and (x2, dy2) -- same layer, two passes -- go out as ONE two-segment launch?  fp16 split
-    only, equal shapes, every operand with a recorded maximum (what the producing launches attach)"""
-    if not (F16X2 and get_conv_precision() == 3) or x.shape != x2.shape or dy.shape != dy2.shape:
-        return False
-    for t in (x, dy, x2, dy2):
-        am = getattr(t, "_mmt_amax", None)
-        if t.dtype != torch.float32 or am is None or am[1] != t._version:
-            return False
-    return dy.shape[1] % 4 == 0
-
-
 def _conv_wgrad_planes(x, dy, xr, dr, w_shape, stride, pad, dw, rowscale, dbias):
     """the weight gradient from the row-blocked fp16 planes both operands already have (include/mmtpsm.h: mmt_conv_wgrad_planes;
     csrc/conv_wgpl.hip) -> False when the library does not take the layer"""
@@ -2063,16 +2018,15 @@ def _conv_wgrad_planes(x, dy, xr, dr, w_shape, stride, pad, dw, rowscale, dbias)
     return True
 
 
-def conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale=None, dbias=None, side=None, keep=None, pair=None):
+def conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale=None, dbias=None, side=None, keep=None):
     """accumulates into dw (same memory layout as the weight) and dbias.  `side`: a torch stream to launch on instead of the
     current one (the caller orders it against the producers of x / dy and joins it later) -- cheaper than entering a stream
     context per call; the split-K workspace is handed to it with record_stream, or -- `keep`, a list -- simply kept alive by
-    the caller until it has joined the side stream.  `pair` = (x2, dy2): a second pass through the same layer whose gradient
-    the SAME launch accumulates (include/mmtpsm.h: mmt_conv_args.x2; the caller checked `wgrad_pair_ok`)"""
+    the caller until it has joined the side stream."""
     if side is not None:
         _TLS.stream = side.cuda_stream
         try:
-            return conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale, dbias, pair=pair)
+            return conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale, dbias)
         finally:
             _TLS.stream = None
             ws = getattr(_TLS, "last_ws", None)
@@ -2086,16 +2040,14 @@ def conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale=None, dbias=None, side=
     dy = nhwc(dy)
     Cout, Cin, KH, KW = w_shape
     N, _, H, W = x.shape
-    if WG_PLANES and pair is None and F16X2 and x.dtype == torch.float32 and dy.dtype == torch.float32:
+    if WG_PLANES and F16X2 and x.dtype == torch.float32 and dy.dtype == torch.float32:
         xr, dr = getattr(x, "_mmt_rb", None), getattr(dy, "_mmt_rb", None)
         if (xr is not None and dr is not None and xr[2] == x._version and dr[2] == dy._version and get_conv_precision() == 3
                 and (len(xr) < 5 or xr[4] is None) and (len(dr) < 5 or dr[4] is None)
                 and _conv_wgrad_planes(x, dy, xr, dr, w_shape, stride, pad, dw, rowscale, dbias)):
             return
     # the shape half of the argument block and the split count depend on the shapes only: kept after the first call
-    if pair is not None:
-        x2, dy2 = nhwc(pair[0]), nhwc(pair[1])
-    key = (x.shape, dy.shape, w_shape, stride, pad, x.dtype, dy.dtype, pair is not None)
+    key = (x.shape, dy.shape, w_shape, stride, pad, x.dtype, dy.dtype)
     plan = _WPLAN.get(key)
     if plan is None:
         a = ConvArgs()
@@ -2104,9 +2056,8 @@ def conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale=None, dbias=None, side=
         a.out_stride = 1
         a.io_bf16 = (IO_X if x.dtype == torch.bfloat16 else 0) | (IO_DY if dy.dtype == torch.bfloat16 else 0)
         a.x = x.data_ptr()
-        a.x2 = x.data_ptr() if pair is not None else None   # (the split count of the two-segment form)
         splits = lib().mmt_conv_wgrad_splits(ctypes.byref(a))
-        a.x = a.x2 = None
+        a.x = None
         if len(_WPLAN) > 4096:
             _WPLAN.clear()
         _WPLAN[key] = (bytes(a), splits)
@@ -2126,17 +2077,6 @@ def conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale=None, dbias=None, side=
             a.f16_x_amax, a.f16_dy_amax = ax[0].data_ptr(), ad[0].data_ptr()
             a.f16_guard_x, a.f16_guard_dy = _guard(ax), _guard(ad)
             F16_STATS["wgrad"] += 1
-            if pair is not None:
-                ax2, ad2 = x2._mmt_amax, dy2._mmt_amax
-                a.x2, a.dy2 = x2.data_ptr(), dy2.data_ptr()
-                a.f16_x_amax2, a.f16_dy_amax2 = ax2[0].data_ptr(), ad2[0].data_ptr()
-                a.f16_guard_x2, a.f16_guard_dy2 = _guard(ax2), _guard(ad2)
-                F16_STATS["wgrad_pairs"] = F16_STATS.get("wgrad_pairs", 0) + 1
-    if pair is not None and not a.x2:
-        # (a site that fell back to the 3-term bf16 split, an operand without a recorded maximum: two launches after all)
-        conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale, dbias)
-        conv_wgrad(x2, dy2, w_shape, stride, pad, dw, rowscale, dbias)
-        return
     ws = torch.empty((splits * Cout * KH * KW * Cin,), dtype=torch.float32, device=x.device) if splits > 1 else None
     _TLS.last_ws = ws
     if PROFILE is not None and PROFILE_ALL:
@@ -2144,8 +2084,7 @@ def conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale=None, dbias=None, side=
         e0.record()
         _check(lib().mmt_conv_wgrad(ctypes.byref(a), _p(dy), _p(rowscale), _p(dw), _p(dbias), _p(ws), _stream()), "mmt_conv_wgrad")
         e1.record()
-        n2 = 2 * N if pair is not None else N
-        PROFILE.append((2.0 * n2 * a.Ho * a.Wo * Cout * Cin * KH * KW, e0, e1, ("wgrad", n2, H, W, Cin, Cout, KH, stride, 1)))
+        PROFILE.append((2.0 * N * a.Ho * a.Wo * Cout * Cin * KH * KW, e0, e1, ("wgrad", N, H, W, Cin, Cout, KH, stride, 1)))
         return
     _check(lib().mmt_conv_wgrad(ctypes.byref(a), _p(dy), _p(rowscale), _p(dw), _p(dbias), _p(ws), _stream()), "mmt_conv_wgrad")
 
@@ -2197,7 +2136,7 @@ def _wgrad_group_job(x, dy, w_shape, stride, pad, dw, rowscale, dbias, keep):
 
 
 def conv_wgrad_group(jobs, side=None, keep=None):
-    """the weight gradients of a batch of layers -- jobs: (x, dy, w_shape, stride, pad, dw, rowscale, dbias[, pair]) -- through
+    """the weight gradients of a batch of layers -- jobs: (x, dy, w_shape, stride, pad, dw, rowscale, dbias) -- through
     mmt_conv_wgrad_group (include/mmtpsm.h: grouped launches); jobs it does not take go out through conv_wgrad, in order.  `side`,
     `keep` as in conv_wgrad."""
     if side is not None:
@@ -2210,12 +2149,9 @@ def conv_wgrad_group(jobs, side=None, keep=None):
     grouped, single = [], []
     if WGRAD_GROUP and not (PROFILE is not None and PROFILE_ALL):
         for job in jobs:
-            x, dy, w_shape, stride, pad, dw, rowscale, dbias = job[:8]
-            pair = job[8] if len(job) > 8 else None
-            wj = None
-            if pair is None:
-                x, dy = nhwc(x), nhwc(dy)
-                wj = _wgrad_group_job(x, dy, w_shape, stride, pad, dw, rowscale, dbias, keep_)
+            x, dy, w_shape, stride, pad, dw, rowscale, dbias = job
+            x, dy = nhwc(x), nhwc(dy)
+            wj = _wgrad_group_job(x, dy, w_shape, stride, pad, dw, rowscale, dbias, keep_)
             if wj is None:
                 single.append(job)
             else:
@@ -2238,8 +2174,7 @@ def conv_wgrad_group(jobs, side=None, keep=None):
                 keep.append(ws)
             # (callers without `keep` launch on the current stream: the caching allocator orders the buffer's reuse behind it)
     for job in single:
-        x, dy, w_shape, stride, pad, dw, rowscale, dbias = job[:8]
-        conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale, dbias, pair=job[8] if len(job) > 8 else None)
+        conv_wgrad(*job)
         ws = getattr(_TLS, "last_ws", None)
         if ws is not None and keep is not None:
             keep.append(ws)

@@ -19,16 +19,11 @@ from maskrcnn_benchmark.layers import fused
 from maskrcnn_benchmark.utils.miscellaneous import sigmoid_rampdown, sigmoid_rampup
 
 
-# The two student passes' weight gradients of a layer as ONE two-segment launch (mmt_conv_args.x2).  Built, tested
-# (tests/test_f16x2_gpu.py::test_wgrad_two_segments, test_train_step_gpu.py::test_paired_weight_gradients_equal_separate) and
-# measured: 119 -> 68 weight-gradient launches per step, but the step is SLOWER, 35.7 -> 37.5 ms in three same-box alternations
-# (profiles/r04_history.md): the supervised pass's jobs used to run in the ~4 ms between the supervised backward and the
-# consistency backward, where the device waits for the teacher and the host; paired, they wait for their partner and all
-# weight-gradient work lands beside the consistency backward, the most contended stretch of the step.  Off.
-_WGRAD_PAIR = os.environ.get("MMT_WGRAD_PAIR", "0") != "0"
-_LOSS_ROOTS = os.environ.get("MMT_LOSS_ROOTS", "1") != "0"   # backward from the losses as roots with the weights as seeds (see _backward_roots)
-_WGRAD_GATE = os.environ.get("MMT_WGRAD_GATE", "0") != "0"     # ... or as they come, behind the end of the teacher's backbone (round 5: +0.3 .. +0.8 ms, off)
-_WGRAD_DEFER = os.environ.get("MMT_WGRAD_DEFER", "1") != "0"   # supervised weight gradients in one batch after the supervised backward (0: interleaved, the A/B alternative)
+# priority -1: HIP maps streams of one priority onto a few hardware queues round-robin; once RCCL has created its own
+# streams (torch.distributed initialised) a default-priority side stream lands on the SAME hardware queue as the
+# main stream and the overlap silently disappears (measured: 63.7 vs 59.9 ms/step).  A different priority class
+# has its own queues.
+_TEACHER_PRIO = -1
 
 
 def get_world_size():
@@ -201,16 +196,14 @@ class BucketedAllReduce(object):
         side-waits-for-step-stream edge -- RCCL's stream then orders itself behind both, and the step stream is never made to wait
         (round 3 joined the side stream into the step stream here: four stalls of the data-gradient chain per backward pass, part of
         the +2.4 ms a process group cost at world size 1)."""
-        from maskrcnn_benchmark.layers import fused as F_
         g = self.flat.grad
-        F_.release_parked(g.data_ptr() + 4 * lo, g.data_ptr() + 4 * hi)   # supervised-pass jobs still waiting for a partner that will not come
-        side = F_.side_stream_for_exchange(g.device) if g.is_cuda else None
+        side = fused.side_stream_for_exchange(g.device) if g.is_cuda else None
         if getattr(self, "tracing", False):   # when backward reached this hook, on the STEP stream's clock (ADVICE r4: the mark used
             e = torch.cuda.Event(enable_timing=True)   # to be recorded inside the side-stream context and measured that queue)
             e.record()
             self._marks.append([lo, hi, e, None, time.perf_counter()])
         if side is None:
-            F_.join_wgrads()   # no side stream in this configuration: the piece is final on the step stream
+            fused.join_wgrads()   # no side stream in this configuration: the piece is final on the step stream
             self._issue(lo, hi)
             return
         with torch.cuda.stream(side):
@@ -350,13 +343,8 @@ class MTtrainer(object):
         # "pair" (one N = 4 forward, two autograd graphs: the default) | "split" (two passes) | "batched" (one pass, one graph):
         # the alternatives are what tests/test_train_step_gpu.py compares the default schedule with
         self.student_passes = "pair"
-        self.pair_wgrads = None   # tests: True / False overrides MMT_WGRAD_PAIR
         self.skipped_pairs = 0  # steps whose consistency branch was skipped (no pseudo box on some image)
-        # priority -1: HIP maps streams of one priority onto a few hardware queues round-robin; once RCCL has created its own
-        # streams (torch.distributed initialised) a default-priority side stream lands on the SAME hardware queue as the
-        # main stream and the overlap silently disappears (measured: 63.7 vs 59.9 ms/step).  A different priority class
-        # has its own queues.
-        self.t_stream = torch.cuda.Stream(device=self.device, priority=int(os.environ.get("MMT_TEACHER_PRIO", "-1"))) if self.overlap_teacher else None
+        self.t_stream = torch.cuda.Stream(device=self.device, priority=_TEACHER_PRIO) if self.overlap_teacher else None
         self._bucketed = None  # BucketedAllReduce, built lazily when enabled (see _bucketed_allreduce)
         # One random stream per model: the teacher's forward runs in a helper thread beside the student's, and with the
         # global generator the interleaving of their draws (fg/bg sampler keys, dropout) would depend on thread timing.
@@ -379,7 +367,6 @@ class MTtrainer(object):
     # ---- one iteration (the unit bench.py times)
     def train_step(self, iteration, data_s, target_s, data_u_list=None):
         use_mt = iteration > self.start_mt and self.lambda_value > 0 and data_u_list is not None
-        fused._WG_PARKED.clear()   # (jobs a failed step left parked must not meet this step's)
         H.WEIGHTS_GEN[0] += 1      # (what _hip derived from loose weights during the last step is not trusted across steps)
         bucketed = self._bucketed_allreduce()
         if bucketed is not None:
@@ -435,43 +422,23 @@ class MTtrainer(object):
                 self.optimizer.zero_grad()
             loss_dict = self.forward_source(data_s, target_s, feats_s)
             if early:
-                defer = _WGRAD_DEFER and use_mt and job is not None
-                pairing = (_WGRAD_PAIR if self.pair_wgrads is None else self.pair_wgrads) and use_mt
-                from maskrcnn_benchmark.layers import fused as _fused
-                gated = defer and _WGRAD_GATE and not pairing
-                if gated:
-                    defer = False
-                    _fused.gate_wgrads(lambda j=job: j.get("backbone_done"))
+                # the supervised pass's weight gradients are collected while its backward is issued and go to the side stream in
+                # one batch behind it (layers/fused.py), beside the consistency branch
+                defer = use_mt and job is not None
                 if defer:
-                    _fused.defer_wgrads(True)
-                if pairing:
-                    # the supervised pass's weight-gradient jobs are PARKED: those of layers the consistency branch runs through
-                    # too (ResNet body, FPN, box head) leave with their partner as one two-segment launch (layers/fused.py)
-                    _fused.wgrad_pair_phase("first")
+                    fused.defer_wgrads(True)
                 try:
                     self._backward_roots(loss_dict, iteration)
                     losses_dict = self._weighted_detached(loss_dict, iteration)   # (for the log: behind the backward's launches)
                 finally:
-                    _fused.wgrad_pair_phase(None)
-                    if gated:
-                        _fused.gate_wgrads(None)
-                        _fused.flush_deferred_wgrads()   # (jobs collected while the teacher's backbone had not been issued yet)
                     if defer:
-                        _fused.defer_wgrads(False)
-                        _fused.flush_deferred_wgrads()   # one batch, behind the supervised backward, beside the consistency branch
-                unl_raw = self.forward_unlabel(data_u_list, feats_u, job)
-                unl = unl_raw
+                        fused.defer_wgrads(False)
+                        fused.flush_deferred_wgrads()   # one batch, behind the supervised backward, beside the consistency branch
+                unl = self.forward_unlabel(data_u_list, feats_u, job)
                 job = None
                 if unl:
-                    if pairing:
-                        _fused.wgrad_pair_phase("second")
-                    try:
-                        self._backward_roots(unl_raw, iteration)
-                        unl = self._weighted_detached(unl_raw, iteration)
-                    finally:
-                        _fused.wgrad_pair_phase(None)
-                if pairing:
-                    _fused.finish_wgrad_pairs()   # jobs that found no partner (RPN / mask head; a skipped consistency branch)
+                    self._backward_roots(unl, iteration)
+                    unl = self._weighted_detached(unl, iteration)
                 losses_dict.update(unl)
                 self._pad_mt_keys(losses_dict)
                 if cut is not None:
@@ -493,8 +460,7 @@ class MTtrainer(object):
                 torch.cuda.current_stream().wait_stream(self.t_stream)
             if bucketed is not None:
                 bucketed.finish()
-        from maskrcnn_benchmark.layers.fused import join_wgrads
-        join_wgrads()   # the weight gradients of this step (side stream) before anything reads the flat gradient
+        fused.join_wgrads()   # the weight gradients of this step (side stream) before anything reads the flat gradient
         if bucketed is None:
             allreduce_gradients(self.flat_s)
         sync_touched(self.flat_s)   # every step: a degenerate route on one rank touches another set than its peers'
@@ -596,9 +562,6 @@ class MTtrainer(object):
         losses are the roots, the weights their seed gradients.  `sum(weighted.values()).backward()` put ~20 scalar launches (the
         weighting multiplies, the chain of adds, their backward nodes) in front of the first kernel of each backward pass -- on the
         step's critical chain, at a point where the host is not ahead of the device."""
-        if not _LOSS_ROOTS:   # (A/B timing: the sum formed by tensor arithmetic, as the reference writes it)
-            sum(v for v in self.weight_sum_loss(loss_dict, iteration).values()).backward()
-            return
         w = mt_weight(iteration, self.cfg.MT.RAMPUP_STEP, self.cfg.MT.RAMPDOWN_STEP, self.max_iter, self.lambda_value, self.start_mt)
         roots, seeds = [], []
         cache = self.__dict__.setdefault("_seed_cache", {})
@@ -627,15 +590,9 @@ class MTtrainer(object):
         self.t_stream.wait_stream(torch.cuda.current_stream())
         job = {}
 
-        def mark():   # called by the teacher when its K x flip backbone pass has been issued (on the teacher's stream)
-            ev = torch.cuda.Event()
-            ev.record(self.t_stream)
-            job["backbone_done"] = ev
-
         def run():
             try:
                 torch.cuda.set_device(self.device)
-                self.teacher.on_backbone_issued = mark
                 with torch.cuda.stream(self.t_stream), torch.no_grad():
                     job["result"] = self.teacher.forward_teacher(teacher_list)
             except BaseException as e:  # re-raised (or handled) by the step thread

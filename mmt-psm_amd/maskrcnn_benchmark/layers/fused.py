@@ -56,18 +56,18 @@ def _touch(*slots):
 # of three record_stream calls per job.
 import os as _os
 _WG_ON = _os.environ.get("MMT_WGRAD_STREAM", "1") != "0"
-_WG_BF16 = True   # bf16 configuration: only the DEFERRED (supervised-pass) jobs go to the side stream
-_WG_BATCH = int(_os.environ.get("MMT_WG_BATCH", "8"))   # jobs handed over behind one stream wait (round 3, single launches: 1 / 4 / 8 / 16 = 36.8 / 36.6 / 36.4 / 36.4 ms per step; round 6, grouped launches: profiles/r06_history.md)
+_WG_BATCH = 8   # jobs handed over behind one stream wait (round 3, single launches: 1 / 4 / 8 / 16 = 36.8 / 36.6 / 36.4 / 36.4 ms per step; round 6, grouped launches: profiles/r06_history.md)
+# priority -1 like the teacher's stream (engine/MTtrainer.py): HIP deals the streams of a priority class onto a few hardware
+# queues, and once RCCL has created its own a default-priority side stream shares one with the step stream -- under a process
+# group the step cost 37.9 ms with this stream at priority 0 and 36.3 at -1 (world size 1, same box); without one 35.5 either way
+_WG_PRIO = -1
 _WG = {}   # device -> [side stream, launches since the last join, end-of-backward callback queued, pending jobs, kept-alive tensors]
 
 
 def _wg_stream(dev):
     ent = _WG.get(dev)
     if ent is None:
-        # priority -1 like the teacher's stream (engine/MTtrainer.py): HIP deals the streams of a priority class onto a few hardware
-        # queues, and once RCCL has created its own a default-priority side stream shares one with the step stream -- under a process
-        # group the step cost 37.9 ms with this stream at priority 0 and 36.3 at -1 (world size 1, same box); without one 35.5 either way
-        ent = _WG[dev] = [torch.cuda.Stream(device=dev, priority=int(_os.environ.get("MMT_WG_PRIO", "-1"))), 0, False, [], []]
+        ent = _WG[dev] = [torch.cuda.Stream(device=dev, priority=_WG_PRIO), 0, False, [], []]
     return ent
 
 
@@ -78,12 +78,6 @@ def flush_wgrads(ent, dev):
     if not jobs:
         return
     side, keep = ent[0], ent[4]
-    gate = _WG_GATE[0]
-    if gate is not None:
-        ev = gate()
-        if ev is None:
-            return            # the gate's event does not exist yet: the jobs stay collected (the end of the pass hands them over)
-        side.wait_event(ev)
     side.wait_stream(torch.cuda.current_stream(dev))
     # round 6: the batch as grouped launches (include/mmtpsm.h: mmt_conv_wgrad_group) -- the tiles of all its layers fill the chip
     # together, so a layer is cut into fewer pixel ranges than alone; jobs no group takes go out one by one as before
@@ -91,30 +85,15 @@ def flush_wgrads(ent, dev):
     for job in jobs:
         keep.append(job[0])    # autograd frees the saved activation / the gradient when the node returns: not before the side
         keep.append(job[1])    # stream has been joined
-        if len(job) > 8 and job[8] is not None:
-            keep.extend(job[8])
     ent[1] += len(jobs)
     jobs.clear()
-
-
-# Two passes through the same weights in one step (the labeled and the unlabeled student pass: engine/MTtrainer.py): a layer's two
-# weight gradients go out as ONE two-segment launch (mmt_conv_args.x2: half the launches, twice the pixels per block -- the N = 2
-# launches were the least efficient group of the step).  Phase "first" (the supervised backward): jobs are parked by the address of
-# their gradient slot instead of being handed over; phase "second" (the consistency backward): a job that finds its partner takes
-# it along; `finish_wgrad_pairs` hands over whatever found none (a layer only one pass runs through, a skipped consistency branch).
-_WG_PAIR = [None]     # None | "first" | "second"
-_WG_PARKED = {}       # (address of dw, shapes) -> [parked jobs]
-
-
-def wgrad_pair_phase(phase):
-    _WG_PAIR[0] = phase
 
 
 def side_stream_for_exchange(dev):
     """the weight-gradient side stream, with every job collected so far handed over and ordered behind the current stream -- what
     a piece of the data-parallel exchange is issued from (engine/MTtrainer.py::BucketedAllReduce._send); None when this
     configuration runs its weight gradients on the step stream"""
-    if not _WG_ON or not (H.get_conv_precision() == 3 or _WG_BF16):
+    if not _WG_ON:
         return None
     ent = _wg_stream(dev)
     flush_wgrads(ent, dev)
@@ -123,47 +102,15 @@ def side_stream_for_exchange(dev):
     return ent[0]
 
 
-def release_parked(lo_ptr, hi_ptr):
-    """a range of the flat gradient buffer is about to be read (a piece of the data-parallel exchange goes out: everything the
-    second pass contributes to it has been issued): parked jobs writing into it will find no partner any more -- issue them now"""
-    hit = [k for k in _WG_PARKED if lo_ptr <= k[0] < hi_ptr]
-    for k in hit:
-        for job in _WG_PARKED.pop(k):
-            _wg_stream(job[0].device)[3].append(job)
-
-
-def finish_wgrad_pairs():
-    """after the second pass (or instead of it): the parked jobs that found no partner go to the side stream on their own"""
-    _WG_PAIR[0] = None
-    if not _WG_PARKED:
-        return
-    for lst in _WG_PARKED.values():
-        for job in lst:
-            _wg_stream(job[0].device)[3].append(job)   # (the trainer joins the side stream before the optimiser step)
-    _WG_PARKED.clear()
-    for dev, ent in _WG.items():
-        flush_wgrads(ent, dev)
-
-
-# Deferral (MMT_WGRAD_DEFER=1, engine/MTtrainer.py): while it is on, jobs are collected but not handed over, and the end-of-backward
+# Deferral (engine/MTtrainer.py): while it is on, jobs are collected but not handed over, and the end-of-backward
 # join does nothing -- the supervised pass's weight gradients then go to the side stream in one batch when the trainer says so
 # (before it waits for the teacher), behind the whole supervised backward, and run beside the consistency branch, where the GPU
 # has room, instead of beside the teacher's backbone, where it has none.
 _WG_DEFER = [False]
-# Gate (round 5, MMT_WGRAD_GATE=1): instead of holding the supervised pass's jobs back until its backward has been issued, they are
-# handed over as they come -- to a side stream that first waits for an EVENT: the end of the teacher's backbone.  From there to the
-# teacher's last result the teacher runs latency-bound selection / head kernels and the GPU has room (profiles/r05_phases.txt:
-# T.backbone ends at 15.5 ms, the supervised backward at 23.3 ms, and all of its weight gradients used to start only then, beside
-# the consistency backward, which is the step's critical chain).  gate() -> the event, or None while it does not exist yet.
-_WG_GATE = [None]
 
 
 def defer_wgrads(on):
     _WG_DEFER[0] = bool(on)
-
-
-def gate_wgrads(fn):
-    _WG_GATE[0] = fn
 
 
 def flush_deferred_wgrads():
@@ -172,11 +119,6 @@ def flush_deferred_wgrads():
 
 
 def _join_wgrads_cb():
-    if _WG_GATE[0] is not None:
-        for dev, ent in _WG.items():
-            ent[2] = False
-            flush_wgrads(ent, dev)  # what is left of the pass; NO join: the step stream meets the side stream before the optimiser
-        return
     if _WG_DEFER[0]:
         for ent in _WG.values():
             ent[2] = False          # the next backward pass queues its own callback
@@ -206,26 +148,16 @@ def _wgrad(x, g, w, stride, pad, rowscale=None, with_bias=False, dst_w=None, dst
     if with_bias:
         db = dst_b if dst_b is not None else torch.zeros((w.shape[0],), dtype=torch.float32, device=w.device)
     if (_WG_ON and dst_w is not None and (dst_b is not None or not with_bias) and not (H.PROFILE is not None and H.PROFILE_ALL)
-            and (H.get_conv_precision() == 3 or (_WG_BF16 and _WG_DEFER[0]))):   # (the bf16 configuration is bound by its host threads:
-            # 28.5 vs 33.6 ms with the side stream for every job; MMT_WGRAD_BF16=1: only the DEFERRED jobs, handed over while the main thread waits for the teacher)
+            and (H.get_conv_precision() == 3 or _WG_DEFER[0])):   # (the bf16 configuration is bound by its host threads: 28.5 vs
+            # 33.6 ms with the side stream for every job; there only the DEFERRED jobs, handed over while the main thread waits for the teacher)
         ent = _wg_stream(x.device)
         H.wgrad_prepare(x, g)            # reduction passes for operands nobody recorded a maximum of: on THIS stream
         if not ent[2]:
             ent[2] = True
             torch.autograd.Variable._execution_engine.queue_callback(_join_wgrads_cb)
-        job = (x, g, tuple(w.shape), stride, pad, dw, rowscale, db)
-        phase = _WG_PAIR[0]
-        if phase == "first" and H.F16X2 and H.get_conv_precision() == 3:   # (the two-segment launch exists on the fp16 split only)
-            _WG_PARKED.setdefault((dw.data_ptr(), x.shape, g.shape, stride, pad), []).append(job)
-        else:
-            if phase == "second":
-                lst = _WG_PARKED.get((dw.data_ptr(), x.shape, g.shape, stride, pad))
-                if lst and H.wgrad_pair_ok(lst[0][0], lst[0][1], x, g):
-                    first = lst.pop(0)
-                    job = first + ((x, g),)     # (the parked pass first: its operands are segment one)
-            ent[3].append(job)
-            if len(ent[3]) >= _WG_BATCH and not _WG_DEFER[0]:
-                flush_wgrads(ent, x.device)
+        ent[3].append((x, g, tuple(w.shape), stride, pad, dw, rowscale, db))
+        if len(ent[3]) >= _WG_BATCH and not _WG_DEFER[0]:
+            flush_wgrads(ent, x.device)
     else:
         H.conv_wgrad(x, g, tuple(w.shape), stride, pad, dw, rowscale, db)
     _touch(dst_w, dst_b if with_bias else None)
@@ -367,17 +299,6 @@ def batch_slice(t, lo, hi):
     return v
 
 
-# Round 6, second stage (MMT_RB_WIDE=1, off unless measured faster: profiles/r06_history.md): planes ALSO for the operands of the 1x1
-# layers' weight gradients and long-K forward / data-gradient launches -- the block outputs and conv2 outputs of a pass that will be
-# back-propagated, the gradients that flow between blocks -- so that those launches run plane-fed (wgrad_pl_kernel, conv_pg_kernel).
-RB_WIDE = _os.environ.get("MMT_RB_WIDE", "0") != "0"
-_PAIR_FWD = [False]   # inside backbone.forward_pair's no-grad forward (its results are back-propagated through `pre=` nodes)
-
-
-def _wide():
-    return RB_WIDE and (torch.is_grad_enabled() or _PAIR_FWD[0])
-
-
 def bottleneck_forward(x, w1, w2, w3, wd, bn, stride):
     """the 3-4 launches of a bottleneck -> (o1, o2, out)"""
     s1, b1, s2, b2, s3, b3, sd, bd = bn
@@ -390,11 +311,9 @@ def bottleneck_forward(x, w1, w2, w3, wd, bn, stride):
     # kernel from layer2 on, and its weight gradient takes o1's planes too)
     o1 = H.conv_forward(x, w1, s1, b1, stride, 0, relu=True, want_planes=wp, out_dtype=od,
                         rb_site=("o1", w2.data_ptr()) if mid >= 128 else None)
-    wide = _wide() and mid >= 128
-    o2 = H.conv_forward(o1, w2, s2, b2, 1, 1, relu=True, out_dtype=od, rb_site=("o2", w3.data_ptr()) if wide else None)
+    o2 = H.conv_forward(o1, w2, s2, b2, 1, 1, relu=True, out_dtype=od)
     r = x if wd is None else H.conv_forward(x, wd, sd, bd, stride, 0, out_dtype=od)
-    out = H.conv_forward(o2, w3, s3, b3, 1, 0, relu=True, res=r, res_mode=1, out_dtype=od,
-                         rb_site=("out", w3.data_ptr()) if wide else None)
+    out = H.conv_forward(o2, w3, s3, b3, 1, 0, relu=True, res=r, res_mode=1, out_dtype=od)
     return o1, o2, out
 
 
@@ -428,8 +347,7 @@ class BottleneckFn(torch.autograd.Function):
                       want_planes=H.planes_wanted_3x3(o2.shape[0], o2.shape[1], o2.shape[2], o2.shape[3], w2.shape[1]),
                       rb_site=("d_o2", w2.data_ptr()) if o2.shape[1] >= 128 else None)
         dw2, _ = _wgrad(o1, d_o2, w2, 1, 1, s2, dst_w=d2)
-        wide = RB_WIDE and o1.shape[1] >= 128
-        d_o1 = _dgrad(d_o2, w2, o1.shape, 1, 1, s2, mask=o1, out_dtype=o1.dtype, rb_site=("d_o1", w1.data_ptr()) if wide else None)
+        d_o1 = _dgrad(d_o2, w2, o1.shape, 1, 1, s2, mask=o1, out_dtype=o1.dtype)
         dw1, _ = _wgrad(x, d_o1, w1, stride, 0, s1, dst_w=d1)
         dwd = dx = None
         if ctx.has_ds:
@@ -440,8 +358,7 @@ class BottleneckFn(torch.autograd.Function):
                 dx = _dgrad(g, wd, x.shape, stride, 0, sd, mask=x, res=t, res_mode=1, out_dtype=x.dtype) if stride > 1 else \
                     _dgrad(g, wd, x.shape, 1, 0, sd, mask=x, res=t, res_mode=1, out_dtype=x.dtype)
             else:
-                dx = _dgrad(d_o1, w1, x.shape, 1, 0, s1, mask=x, res=g, res_mode=1, out_dtype=x.dtype,
-                            rb_site=("dx", w1.data_ptr()) if wide else None)
+                dx = _dgrad(d_o1, w1, x.shape, 1, 0, s1, mask=x, res=g, res_mode=1, out_dtype=x.dtype)
         return dx, dw1, dw2, dw3, dwd, None, None, None
 
 
@@ -494,13 +411,12 @@ class FPNFn(torch.autograd.Function):
         dwl, dbl, dwi, dbi, dcs = [None] * 4, [None] * 4, [None] * 4, [None] * 4, [None] * 4
         for k in range(4):  # finest first: d_inner_k = dgrad(layer_k) + 2x2-sum(d_inner_{k-1})
             d_in[k] = _dgrad(gs[k], wl[k], inner[k].shape, 1, 1, None, res=d_in[k - 1] if k > 0 else None,
-                             res_mode=3 if k > 0 else 0, rb_site=("d_in", wi[k].data_ptr()) if RB_WIDE else None)
+                             res_mode=3 if k > 0 else 0)
             dwl[k], dbl[k] = _wgrad(inner[k], gs[k], wl[k], 1, 1, None, True, *ctx.dst[1][k])
         for k in range(4):
             dwi[k], dbi[k] = _wgrad(cs[k], d_in[k], wi[k], 1, 0, None, True, *ctx.dst[0][k])
             if ctx.needs_input_grad[k]:
-                dcs[k] = _dgrad(d_in[k], wi[k], cs[k].shape, 1, 0, None, mask=cs[k], out_dtype=cs[k].dtype,  # C_k is a ReLU output
-                                rb_site=("dC", wi[k].data_ptr()) if RB_WIDE and k == 3 else None)
+                dcs[k] = _dgrad(d_in[k], wi[k], cs[k].shape, 1, 0, None, mask=cs[k], out_dtype=cs[k].dtype)  # C_k is a ReLU output
         out = list(dcs)
         for k in range(4):
             out += [dwi[k], dbi[k]]

@@ -69,37 +69,6 @@ def timed(fn, reps, stream):
     return best, mode
 
 
-def ablate(args, stream):
-    """what the main loop waits for: the same launch with parts of it compiled out (results are wrong by construction)"""
-    names = {0: "as shipped", 1: "A copies re-read one step", 2: "B copies re-read one step", 3: "A and B re-read", 4: "no copies (zeros)",
-             8: "no fragment reads", 12: "neither", 16: "register-staged copies (correct results)", 32: "A pieces of 64 B", 64: "A pieces of 128 B"}
-    for sh, rows in [((2, 256, 64, 64, 256, 3, 1, 1), 64), ((2, 1024, 64, 64, 256, 1, 1, 0), 64), ((400, 256, 14, 14, 256, 3, 1, 1), 256),
-                     ((8, 256, 64, 64, 256, 3, 1, 1), 256), ((4, 256, 64, 64, 256, 3, 1, 1), 128), ((2, 512, 32, 32, 512, 3, 1, 1), 128)]:
-        N, C, Hh, W, Co, k, s, p = sh
-        g = torch.Generator().manual_seed(1)
-        x = cl(torch.randn(N, C, Hh, W, generator=g).relu().cuda())
-        w = cl((torch.randn(Co, C, k, k, generator=g) * (2.0 / (k * k * C)) ** 0.5).cuda())
-        b = torch.randn(Co, generator=g).cuda()
-        with torch.cuda.stream(stream):
-            H._amax_of(x)
-            xp = H.f16_split_pg(x)
-        out = []
-        y0 = H.conv_forward_pg(x, w, None, b, s, p, relu=True, tile_rows=rows, ksplit=1, xp=xp)
-        os.environ["MMT_PG_DBG"] = "16"
-        y16 = H.conv_forward_pg(x, w, None, b, s, p, relu=True, tile_rows=rows, ksplit=1, xp=xp)
-        os.environ.pop("MMT_PG_DBG")
-        torch.cuda.synchronize()
-        out.append("register-staged == shipped: %s" % bool(torch.equal(y0, y16)))
-        for dbg in ((0, 16, 4) if rows == 128 else (0, 16, 32, 64, 1, 2, 3, 4, 8, 12)):
-            if rows == 256 and dbg == 3:
-                continue
-            os.environ["MMT_PG_DBG"] = str(dbg)
-            t, _ = timed(lambda: H.conv_forward_pg(x, w, None, b, s, p, relu=True, tile_rows=rows, ksplit=1, xp=xp), args.reps, stream)
-            out.append("%s %.1f" % (names[dbg], t * 1e3))
-        os.environ.pop("MMT_PG_DBG", None)
-        print("%s rows %d: %s" % (sh, rows, " | ".join(out)), flush=True)
-
-
 def split_passes(args, stream):
     """the plane-split pass in the two orders (indexed like x / row-blocked): us per launch, GB/s of 8 bytes per element"""
     for sh in [(8, 256, 256, 256), (4, 256, 256, 256), (2, 256, 256, 256), (8, 128, 128, 128), (2, 256, 64, 64), (2, 512, 32, 32),
@@ -143,7 +112,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--ablate", action="store_true", help="main-loop ablations (MMT_PG_DBG) of the 64- and 256-row forms on a few shapes")
     ap.add_argument("--split", action="store_true", help="time the plane-split pass in both plane orders")
     ap.add_argument("--wgrad", action="store_true", help="weight gradient of the 3x3 layers: register-splitting vs plane-fed kernel")
     args = ap.parse_args()
@@ -156,8 +124,6 @@ def main():
         return split_passes(args, stream)
     if args.wgrad:
         return wgrads(args, stream)
-    if args.ablate:
-        return ablate(args, stream)
     print("# us per launch (graph replay of %d calls, best of 5); TF = algorithmic TFLOP/s; peak 833" % args.reps)
     print("%-40s %5s | %8s %6s | %s" % ("shape (N,Cin,H,W,Cout,k,s,p)", "calls", "old us", "TF", "pg variants: rows/ks: us [+split us] TF"))
     tot_old = tot_new = tot_new_split = 0.0
@@ -191,14 +157,13 @@ def main():
                 res.append((rows, ks, None, str(e)[:40]))
                 continue
             res.append((rows, ks, t, None))
-        t_af, _ = timed(lambda: H.conv_forward_pg(x, w, None, b, s, p, relu=True, xp="fp32"), args.reps, stream)
         ok = [r for r in res if r[2] is not None]
         best = min(ok, key=lambda r: r[2]) if ok else None
         line = "%-40s %5d | %8.1f %6.1f | " % (str(sh[:8]), calls, t_old * 1e3, flop / t_old / 1e9)
         line += " ".join("%d/%d:%.1f" % (r[0], r[1], r[2] * 1e3) if r[2] is not None else "%d/%d:ERR" % (r[0], r[1]) for r in res)
         if best:
-            line += "  || plan %d/%d best %d/%d %.1f us %.0f TF, split pass %.1f us, FP32 ROWS (plan, no split pass) %.1f us (%s)" % (
-                rows0, ks0, best[0], best[1], best[2] * 1e3, flop / best[2] / 1e9, t_split * 1e3, t_af * 1e3, mode)
+            line += "  || plan %d/%d best %d/%d %.1f us %.0f TF, split pass %.1f us (%s)" % (
+                rows0, ks0, best[0], best[1], best[2] * 1e3, flop / best[2] / 1e9, t_split * 1e3, mode)
             tot_old += calls * t_old
             tot_new += calls * min(best[2], t_old)
             tot_new_split += calls * min(best[2] + t_split, t_old)

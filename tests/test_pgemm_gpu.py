@@ -331,11 +331,29 @@ def test_row_blocked_planes_equal_planes_indexed_like_x(hip, case):
     assert torch.equal(y2, y3), case
 
 
-def test_product_library_has_no_copy_wave_split_form(hip):
+def test_forward_pg_refuses_null_x_planes(hip):
     """round 6: the x_planes = NULL form (copy waves split fp32 rows themselves; round-5 experiment, slower, 144 registers of copy
-    ring = spills) is compiled into the tools build only (`make ablate`): the product library refuses it loudly"""
+    ring = spills) is not built: the library refuses a call without x_planes loudly (MMT_EINVAL), everything else being valid"""
+    import ctypes
     H = hip
     x, w, sc, sh, kw = _make(CASES[0])
     N, C, Hh, W, Co, k, stride, pad, opts = CASES[0]
-    with pytest.raises(RuntimeError):
-        H.conv_forward_pg(x, w, sc, sh, stride, pad, xp="fp32", **kw)
+    Ho, Wo = (Hh + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    a = H.ConvArgs()
+    a.x, a.w = x.data_ptr(), w.data_ptr()
+    a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = N, Hh, W, C, Co, k, k
+    a.stride, a.pad, a.Ho, a.Wo = stride, pad, Ho, Wo
+    a.out_stride, a.mask_scale = 1, 1.0
+    y = H.empty_nhwc(N, Co, Ho, Wo, x.device)
+    a.y = y.data_ptr()
+    wp16, sw = H.f16_weight_planes(w)
+    a.w_planes, a.w_plane_stride = wp16.data_ptr(), wp16.stride(0)
+    sx = H._amax_of(x)[0]
+    assert not a.x_planes
+    rc = H.lib().mmt_conv_forward_pg(ctypes.byref(a), sx.data_ptr(), sw.data_ptr(), 0, 0, H._stream())
+    assert rc == -22, rc   # MMT_EINVAL (include/mmtpsm.h)
+    # the same call with planes is taken (the refusal above is about the NULL planes alone)
+    xp16, sx2, a.x_planes_layout, a.x_planes_lag = H.f16_split_pg(x)
+    a.x_planes, a.x_plane_stride = xp16.data_ptr(), xp16.stride(0)
+    assert H.lib().mmt_conv_forward_pg(ctypes.byref(a), sx2.data_ptr(), sw.data_ptr(), 0, 0, H._stream()) == 0
+    torch.cuda.synchronize()
