@@ -552,6 +552,25 @@ int mmt_maxpool3x3s2(const float* x, float* y, int N, int H, int W, int C, int H
 /* the same on bf16 tensors (bf16 activation storage, see mmt_conv_args.io_bf16) */
 int mmt_maxpool3x3s2_bf16(const void* x, void* y, int N, int H, int W, int C, int Ho, int Wo, void* stream);
 
+/* ---------------------------------------------------------------- grouped 3x3 convolution (csrc/conv_group.hip)
+ * ResNeXt's conv2 (reference backbone/resnet.py:226-237, `groups=num_groups`): C = G * Cg channels in and out, 3x3, pad 1, stride 1
+ * or 2, NHWC fp32 activations [N][H][W][C] -> [N][Ho][Wo][C] with Ho = (H - 1) / stride + 1, weight (C, Cg, 3, 3) in the layout
+ * [C][3][3][Cg].  Cg in {8, 16, 32, 64}, C % 32 == 0; anything else is refused (MMT_EINVAL).  Exact fp32 products and fp32
+ * accumulation on the fp32-input MFMA (v_mfma_f32_16x16x4_f32) whatever mmt_set_conv_precision says; fp32 tensors only.
+ *   forward  y = relu?( conv_g(x, w) * scale[co] + shift[co] )                  (scale / shift NULL: 1 / 0); writes every element of y
+ *   dgrad    dx[n,h,w,g Cg + ci] = (mask[n,h,w,g Cg + ci] > 0) * sum_{co in g, kh, kw} dy[n,ho,wo,co] * scale[co] * w[co,kh,kw,ci]
+ *            with ho * stride - 1 + kh == h, wo * stride - 1 + kw == w (scale / mask NULL: without them); H, W are dx's, dy is
+ *            [N][Ho][Wo][C].  Gather form: every element of dx is written by its one owner (zeros where no tap reaches), no atomics,
+ *            nothing to clear.  wt: workspace of C * 9 * Cg floats (the transformed weights), alive until the stream has run the call.
+ *   wgrad    dw[co,kh,kw,ci] += rowscale[co] * sum_{n,ho,wo} dy[n,ho,wo,co] * x[n, ho*stride-1+kh, wo*stride-1+kw, g Cg + ci]
+ *            (H, W are x's; rowscale NULL: 1); accumulates into dw with fp32 atomics like mmt_conv_wgrad's split form. */
+int mmt_gconv3x3_forward(const float* x, const float* w, const float* scale, const float* shift, float* y, int N, int H, int W,
+                         int C, int Cg, int stride, int relu, void* stream);
+int mmt_gconv3x3_dgrad(const float* dy, const float* w, const float* scale, const float* mask, float* wt, float* dx, int N, int H,
+                       int W, int C, int Cg, int stride, void* stream);
+int mmt_gconv3x3_wgrad(const float* x, const float* dy, const float* rowscale, float* dw, int N, int H, int W, int C, int Cg,
+                       int stride, void* stream);
+
 /* ---------------------------------------------------------------- losses (forward value + gradient in one launch)
  * mask-logit BCE (mask_head/loss.py:177-179): logits [P,28*28,NC] NHWC, labels int32 [P], targets [P,28*28] {0,1};
  * loss (1 float, accumulated; zero it first) = mean BCEWithLogits(logits[p,:,label_p], target); grad [P,28*28,NC]

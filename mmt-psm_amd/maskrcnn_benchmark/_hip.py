@@ -163,6 +163,9 @@ _SIGS = {
     "mmt_stem_fused": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_void_p, c_void_p],
     "mmt_maxpool3x3s2_bf16": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "mmt_gconv3x3_forward": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "mmt_gconv3x3_dgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "mmt_gconv3x3_wgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "mmt_mask_bce": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "mmt_mgd_level_forward": [c_void_p, ctypes.POINTER(MgdTeachers), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_mgd_level_backward": [c_void_p, ctypes.POINTER(MgdTeachers), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
@@ -2221,6 +2224,85 @@ def maxpool3x3s2(x):
     else:
         _check(lib().mmt_maxpool3x3s2(_p(x), _p(y), N, H, W, C, Ho, Wo, _stream()), "mmt_maxpool3x3s2")
     return y
+
+
+# ------------------------------------------------------------------------------------------ grouped 3x3 convolution (ResNeXt conv2)
+GCONV_WIDTHS = (8, 16, 32, 64)   # channels per group csrc/conv_group.hip takes
+
+
+def _gconv_args(x, w, stride):
+    """checked (x, w, N, C, H, W, Cg) of a grouped 3x3 call: x (N, C, H, W), w (C, Cg, 3, 3), both fp32"""
+    if bf16_storage():
+        raise NotImplementedError("grouped 3x3 convolutions (ResNeXt) are not offered with bf16 activation storage: "
+                                  "set_bf16_storage(False)")
+    x, w = nhwc(_dev(x)), nhwc(_dev(w, "weight"))
+    if x.dtype != torch.float32 or w.dtype != torch.float32:
+        raise RuntimeError("grouped 3x3 convolution: fp32 tensors only")
+    N, C, H, W = x.shape
+    Cg = w.shape[1]
+    if tuple(w.shape) != (C, Cg, 3, 3) or Cg not in GCONV_WIDTHS or C % Cg or C % 32 or stride not in (1, 2):
+        raise RuntimeError("grouped 3x3 convolution: weight (C, Cg, 3, 3) with Cg in %s, C %% 32 == 0, stride 1 or 2; got x %s, w %s, "
+                           "stride %s" % (GCONV_WIDTHS, tuple(x.shape), tuple(w.shape), stride))
+    return x, w, N, C, H, W, Cg
+
+
+def _gconv_vec(t, C, name):
+    if t is None:
+        return None
+    if not (t.is_cuda and t.dtype == torch.float32 and t.numel() == C and t.is_contiguous()):
+        raise RuntimeError("grouped 3x3 convolution: %s is a dense fp32 GPU vector of C elements" % name)
+    return t
+
+
+def gconv3x3_forward(x, w, scale=None, shift=None, stride=1, relu=False):
+    """include/mmtpsm.h: mmt_gconv3x3_forward.  y = relu?(conv(x, w, pad 1, stride, groups = C / Cg) * scale[co] + shift[co])"""
+    x, w, N, C, H, W, Cg = _gconv_args(x, w, stride)
+    y = empty_nhwc(N, C, (H - 1) // stride + 1, (W - 1) // stride + 1, x.device)
+    _check(lib().mmt_gconv3x3_forward(_p(x), _p(w), _p(_gconv_vec(scale, C, "scale")), _p(_gconv_vec(shift, C, "shift")), _p(y),
+                                      N, H, W, C, Cg, stride, 1 if relu else 0, _stream()), "mmt_gconv3x3_forward")
+    return y
+
+
+def gconv3x3_dgrad(dy, w, x_hw, stride=1, scale=None, mask=None, out=None):
+    """include/mmtpsm.h: mmt_gconv3x3_dgrad.  The gradient w.r.t. the (H, W) = x_hw input of gconv3x3_forward for the output gradient
+    dy, times scale[co] on the way in and (mask > 0) on the way out; every element is written (out: a destination to fill)"""
+    dy, w, N, C, Ho, Wo, Cg = _gconv_args(dy, w, stride)
+    H, W = int(x_hw[0]), int(x_hw[1])
+    if ((H - 1) // stride + 1, (W - 1) // stride + 1) != (Ho, Wo):
+        raise RuntimeError("grouped 3x3 data gradient: dy %s is not the output of a stride-%d convolution over %s" % (tuple(dy.shape), stride, (H, W)))
+    if mask is not None:
+        mask = nhwc(_dev(mask, "mask"))
+        if tuple(mask.shape) != (N, C, H, W) or mask.dtype != torch.float32:
+            raise RuntimeError("grouped 3x3 data gradient: the mask has the shape and type of dx")
+    if out is None:
+        out = empty_nhwc(N, C, H, W, dy.device)
+    elif tuple(out.shape) != (N, C, H, W) or out.dtype != torch.float32 or not out.is_cuda or nhwc(out) is not out:
+        raise RuntimeError("grouped 3x3 data gradient: `out` is an NHWC-dense fp32 GPU tensor of dx's shape")
+    wt = torch.empty((C * 9 * Cg,), dtype=torch.float32, device=dy.device)   # (stream-ordered allocator: alive for the launch)
+    _check(lib().mmt_gconv3x3_dgrad(_p(dy), _p(w), _p(_gconv_vec(scale, C, "scale")), _p(mask), _p(wt), _p(out), N, H, W, C, Cg, stride,
+                                    _stream()), "mmt_gconv3x3_dgrad")
+    return out
+
+
+def gconv3x3_wgrad(x, dy, w_shape, stride, dw, rowscale=None):
+    """include/mmtpsm.h: mmt_gconv3x3_wgrad.  dw (C, Cg, 3, 3 in the weight's layout) += rowscale[co] * the weight gradient"""
+    if bf16_storage():
+        raise NotImplementedError("grouped 3x3 convolutions (ResNeXt) are not offered with bf16 activation storage: "
+                                  "set_bf16_storage(False)")
+    x, dy = nhwc(_dev(x)), nhwc(_dev(dy, "dy"))
+    N, C, H, W = x.shape
+    Cg = int(w_shape[1])
+    if (tuple(w_shape) != (C, Cg, 3, 3) or Cg not in GCONV_WIDTHS or C % Cg or C % 32 or stride not in (1, 2)
+            or tuple(dy.shape) != (N, C, (H - 1) // stride + 1, (W - 1) // stride + 1)
+            or x.dtype != torch.float32 or dy.dtype != torch.float32):
+        raise RuntimeError("grouped 3x3 weight gradient: fp32 x (N, C, H, W), dy of the stride-%s output, weight (C, Cg, 3, 3) with Cg in "
+                           "%s; got x %s, dy %s, w %s" % (stride, GCONV_WIDTHS, tuple(x.shape), tuple(dy.shape), tuple(w_shape)))
+    _dev(dw, "dw")
+    if dw.dtype != torch.float32 or dw.numel() != C * Cg * 9 or (dw.dim() == 4 and nhwc(dw) is not dw) or (dw.dim() != 4 and not dw.is_contiguous()):
+        raise RuntimeError("grouped 3x3 weight gradient: dw is a dense fp32 tensor in the weight's layout")
+    _check(lib().mmt_gconv3x3_wgrad(_p(x), _p(dy), _p(_gconv_vec(rowscale, C, "rowscale")), _p(dw), N, H, W, C, Cg, stride, _stream()),
+           "mmt_gconv3x3_wgrad")
+    return dw
 
 
 # ------------------------------------------------------------------------------------------ losses

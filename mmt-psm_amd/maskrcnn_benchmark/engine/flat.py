@@ -83,6 +83,8 @@ class FlatParams(object):
             for n, p in self._named:
                 if p.dim() < 2 or p.shape[0] <= 32 or (p.numel() // p.shape[0]) % 16:
                     continue  # such layers always run on the fp32 kernel
+                if getattr(p, "_mmt_grouped", False):
+                    continue  # conv2 of a grouped bottleneck: csrc/conv_group.hip reads the fp32 weight, nobody reads dense planes
                 cout, k = p.shape[0], p.numel() // p.shape[0]
                 o, _ = self.index[n]
                 elems = H.packed_elems(cout, k)

@@ -45,12 +45,13 @@ class Conv2d(nn.Module):
     """Drop-in for layers.Conv2d / nn.Conv2d on the path (layers/misc.py:30-43): parameter `weight`
     (Cout,Cin,KH,KW) -- kept in channels_last memory = the kernel's [Cout][KH][KW][Cin] -- and optional `bias`."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, groups=1):
         super().__init__()
         k = _pair(kernel_size)
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride, self.padding = k, _pair(stride), _pair(padding)
-        w = torch.empty(out_channels, in_channels, k[0], k[1])
+        self.groups = groups   # > 1: only as conv2 of a bottleneck (layers/fused.py: bottleneck_forward), weight (Cout, Cin // groups, k, k)
+        w = torch.empty(out_channels, in_channels // groups, k[0], k[1])
         nn.init.kaiming_uniform_(w, a=5 ** 0.5)
         self.weight = nn.Parameter(w.contiguous(memory_format=torch.channels_last))
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
@@ -60,6 +61,8 @@ class Conv2d(nn.Module):
             h = (x.shape[2] + 2 * self.padding[0] - self.kernel_size[0]) // self.stride[0] + 1
             w = (x.shape[3] + 2 * self.padding[1] - self.kernel_size[1]) // self.stride[1] + 1
             return x.new_empty((x.shape[0], self.out_channels, h, w))
+        if self.groups != 1:
+            raise NotImplementedError("a grouped convolution runs as conv2 of a bottleneck only (layers/fused.py)")
         pr = self._parameters   # (not through nn.Module.__getattr__: once per launch on the issuing thread)
         return fused.conv(x, pr["weight"], pr.get("bias"), self.stride[0], self.padding[0], relu, input_relu, out_rb, din_rb)
 

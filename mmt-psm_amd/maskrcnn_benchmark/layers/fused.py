@@ -299,9 +299,31 @@ def batch_slice(t, lo, hi):
     return v
 
 
-def bottleneck_forward(x, w1, w2, w3, wd, bn, stride):
+def _grouped(w2):
+    """conv2 of a ResNeXt block: weight (width, width // num_groups, 3, 3) with num_groups > 1"""
+    return w2.shape[1] != w2.shape[0]
+
+
+def _strides(stride, in_3x3):
+    """(stride of conv1, stride of conv2): reference backbone/resnet.py:221"""
+    return (1, stride) if in_3x3 else (stride, 1)
+
+
+def bottleneck_forward(x, w1, w2, w3, wd, bn, stride, in_3x3=False):
     """the 3-4 launches of a bottleneck -> (o1, o2, out)"""
     s1, b1, s2, b2, s3, b3, sd, bd = bn
+    if _grouped(w2):
+        # ResNeXt: conv2 on the grouped kernels (csrc/conv_group.hip), exact fp32.  o1 feeds no dense plane-fed 3x3: no planes asked
+        if H.bf16_storage():
+            raise NotImplementedError("grouped bottlenecks (NUM_GROUPS > 1) are not offered with bf16 activation storage")
+        s1x1, s3x3 = _strides(stride, in_3x3)
+        o1 = H.conv_forward(x, w1, s1, b1, s1x1, 0, relu=True)
+        o2 = H.gconv3x3_forward(o1, w2, s2, b2, s3x3, relu=True)
+        r = x if wd is None else H.conv_forward(x, wd, sd, bd, stride, 0)
+        out = H.conv_forward(o2, w3, s3, b3, 1, 0, relu=True, res=r, res_mode=1)
+        return o1, o2, out
+    if in_3x3 and stride != 1:
+        raise NotImplementedError("NUM_GROUPS=1 with STRIDE_IN_1X1=False: the dense strided 3x3 data gradient is not built")
     # o1 feeds one 3x3 convolution: where that runs on bf16 planes, conv1's epilogue writes them (no split pass)
     mid = w1.shape[0]
     ho, wo = (x.shape[2] + stride - 1) // stride, (x.shape[3] + stride - 1) // stride
@@ -324,10 +346,11 @@ class BottleneckFn(torch.autograd.Function):
     passes of a step): the node then only records what its backward needs."""
 
     @staticmethod
-    def forward(ctx, x, w1, w2, w3, wd, bn, stride, pre=None):
+    def forward(ctx, x, w1, w2, w3, wd, bn, stride, pre=None, in_3x3=False):
         s1, b1, s2, b2, s3, b3, sd, bd = bn
         x = H.nhwc(x)
-        o1, o2, out = pre if pre is not None else bottleneck_forward(x, w1, w2, w3, wd, bn, stride)
+        o1, o2, out = pre if pre is not None else bottleneck_forward(x, w1, w2, w3, wd, bn, stride, in_3x3)
+        ctx.in_3x3 = in_3x3
         ctx.save_for_backward(x, o1, o2, w1, w2, w3, wd if wd is not None else _none_like(x))
         ctx.bn = (s1, s2, s3, sd)
         ctx.stride = stride
@@ -342,6 +365,8 @@ class BottleneckFn(torch.autograd.Function):
         stride = ctx.stride
         g = H.nhwc(g)  # masked by (out > 0) by the consumer
         d1, d2, d3, dd = ctx.dst
+        if _grouped(w2):
+            return BottleneckFn._backward_grouped(ctx, g)
         dw3, _ = _wgrad(o2, g, w3, 1, 0, s3, dst_w=d3)
         d_o2 = _dgrad(g, w3, o2.shape, 1, 0, s3, mask=o2, out_dtype=o2.dtype,
                       want_planes=H.planes_wanted_3x3(o2.shape[0], o2.shape[1], o2.shape[2], o2.shape[3], w2.shape[1]),
@@ -359,7 +384,39 @@ class BottleneckFn(torch.autograd.Function):
                     _dgrad(g, wd, x.shape, 1, 0, sd, mask=x, res=t, res_mode=1, out_dtype=x.dtype)
             else:
                 dx = _dgrad(d_o1, w1, x.shape, 1, 0, s1, mask=x, res=g, res_mode=1, out_dtype=x.dtype)
-        return dx, dw1, dw2, dw3, dwd, None, None, None
+        return dx, dw1, dw2, dw3, dwd, None, None, None, None
+
+    @staticmethod
+    def _backward_grouped(ctx, g):
+        """the same chain with conv2 on the grouped kernels.  Its weight gradient goes out on the current stream (ordered before
+        everything a later join_wgrads() waits for); neither d_o2 nor o1 is asked for planes: no dense 3x3 reads them."""
+        x, o1, o2, w1, w2, w3, wd = ctx.saved_tensors
+        s1, s2, s3, sd = ctx.bn
+        stride = ctx.stride
+        s1x1, s3x3 = _strides(stride, ctx.in_3x3)
+        d1, d2, d3, dd = ctx.dst
+        dw3, _ = _wgrad(o2, g, w3, 1, 0, s3, dst_w=d3)
+        d_o2 = _dgrad(g, w3, o2.shape, 1, 0, s3, mask=o2, out_dtype=o2.dtype)
+        dw2 = d2 if d2 is not None else torch.zeros_like(H.nhwc(w2))
+        H.gconv3x3_wgrad(o1, d_o2, tuple(w2.shape), s3x3, dw2, s2)
+        _touch(d2)
+        if d2 is not None:
+            dw2 = None
+        d_o1 = H.gconv3x3_dgrad(d_o2, w2, o1.shape[2:], s3x3, s2, mask=o1)
+        dw1, _ = _wgrad(x, d_o1, w1, s1x1, 0, s1, dst_w=d1)
+        dwd = dx = None
+        if ctx.has_ds:
+            dwd, _ = _wgrad(x, g, wd, stride, 0, sd, dst_w=dd)
+        if ctx.needs_input_grad[0]:
+            if not ctx.has_ds:
+                dx = _dgrad(d_o1, w1, x.shape, 1, 0, s1, mask=x, res=g, res_mode=1, out_dtype=x.dtype)
+            elif s1x1 == stride:   # the stride (if any) sits in conv1: compact Ho x Wo, then the downsample's scatter adds it
+                t = _dgrad(d_o1, w1, (x.shape[0], x.shape[1], g.shape[2], g.shape[3]), 1, 0, s1, out_dtype=x.dtype)
+                dx = _dgrad(g, wd, x.shape, stride, 0, sd, mask=x, res=t, res_mode=1, out_dtype=x.dtype)
+            else:                  # the stride sits in conv2: d_o1 is full resolution -- the strided downsample gradient first, as the
+                t = _dgrad(g, wd, x.shape, stride, 0, sd, out_dtype=x.dtype)   # residual operand of conv1's data gradient
+                dx = _dgrad(d_o1, w1, x.shape, 1, 0, s1, mask=x, res=t, res_mode=1, out_dtype=x.dtype)
+        return dx, dw1, dw2, dw3, dwd, None, None, None, None
 
 
 def fpn_forward(cs, wi, bi, wl, bl, out_planes=True):

@@ -1,4 +1,4 @@
-"""R-50-FPN backbone (reference: modeling/backbone/backbone.py:19-44, resnet.py:61-307, fpn.py:7-74).
+"""R-50 / R-101 / ResNeXt FPN backbone (reference: modeling/backbone/backbone.py:19-44, resnet.py:61-307, fpn.py:7-74).
 
 Same attribute tree / state-dict keys (backbone.body.stem.*, backbone.body.layerK.N.convM / bnM /
 downsample.{0,1}, backbone.fpn.fpn_inner{1-4} / fpn_layer{1-4}).  Execution differs: the whole body is NHWC,
@@ -90,19 +90,31 @@ def _pool_keep_stats(y):
 class BottleneckWithFixedBatchNorm(nn.Module):
     def __init__(self, in_channels, bottleneck_channels, out_channels, num_groups=1, stride_in_1x1=True, stride=1):
         super().__init__()
-        if num_groups != 1 or not stride_in_1x1:
-            raise NotImplementedError("R-50 hot path: NUM_GROUPS=1, STRIDE_IN_1X1=True")
+        if num_groups == 1 and not stride_in_1x1:
+            raise NotImplementedError("NUM_GROUPS=1 with STRIDE_IN_1X1=False: the data gradient of a dense strided 3x3 convolution is "
+                                      "not built (grouped blocks, NUM_GROUPS > 1, take the stride in either place)")
+        if num_groups > 1 and (bottleneck_channels % num_groups or bottleneck_channels // num_groups not in H.GCONV_WIDTHS
+                               or bottleneck_channels % 32):
+            raise NotImplementedError("grouped 3x3 convolution: %d channels in %d groups -- the kernels take %s channels per group"
+                                      % (bottleneck_channels, num_groups, "/".join(map(str, H.GCONV_WIDTHS))))
+        if stride == 1:
+            stride_in_1x1 = True   # (nothing to place)
+        stride_1x1, stride_3x3 = (stride, 1) if stride_in_1x1 else (1, stride)   # reference resnet.py:221
         self.downsample = None
         if in_channels != out_channels:
             self.downsample = nn.Sequential(Conv2d(in_channels, out_channels, kernel_size=1, stride=stride, bias=False),
                                             FrozenBatchNorm2d(out_channels))
-        self.conv1 = Conv2d(in_channels, bottleneck_channels, kernel_size=1, stride=stride, bias=False)
+        self.conv1 = Conv2d(in_channels, bottleneck_channels, kernel_size=1, stride=stride_1x1, bias=False)
         self.bn1 = FrozenBatchNorm2d(bottleneck_channels)
-        self.conv2 = Conv2d(bottleneck_channels, bottleneck_channels, kernel_size=3, stride=1, padding=1, bias=False)
+        self.conv2 = Conv2d(bottleneck_channels, bottleneck_channels, kernel_size=3, stride=stride_3x3, padding=1, bias=False,
+                            groups=num_groups)
+        if num_groups > 1:
+            self.conv2.weight._mmt_grouped = True   # (engine/flat.py: no dense planes for it, nobody would read them)
         self.bn2 = FrozenBatchNorm2d(bottleneck_channels)
         self.conv3 = Conv2d(bottleneck_channels, out_channels, kernel_size=1, bias=False)
         self.bn3 = FrozenBatchNorm2d(out_channels)
         self.stride = stride
+        self.in_3x3 = not stride_in_1x1
 
     def _args(self):
         # (once per block and pass, on the launch-issuing thread: sub-modules and parameters straight from the module dicts)
@@ -119,12 +131,12 @@ class BottleneckWithFixedBatchNorm(nn.Module):
                 (s1, b1, s2, b2, s3, b3, sd, bd), self.stride)
 
     def forward(self, x, pre=None):
-        return fused.BottleneckFn.apply(x, *self._args(), pre)
+        return fused.BottleneckFn.apply(x, *self._args(), pre, self.in_3x3)
 
     def forward_raw(self, x):
         """no autograd: (o1, o2, out) of this block for `x` (forward_pair)"""
         w1, w2, w3, wd, bn, stride = self._args()
-        return fused.bottleneck_forward(H.nhwc(x), w1, w2, w3, wd, bn, stride)   # (the caller runs this under no_grad)
+        return fused.bottleneck_forward(H.nhwc(x), w1, w2, w3, wd, bn, stride, self.in_3x3)   # (the caller runs this under no_grad)
 
 
 class ResNet(nn.Module):
@@ -141,7 +153,7 @@ class ResNet(nn.Module):
             f = 2 ** (i - 1)
             blocks, stride = [], (2 if i > 1 else 1)
             for _ in range(n):
-                blocks.append(BottleneckWithFixedBatchNorm(in_ch, width * f, out2 * f, 1,
+                blocks.append(BottleneckWithFixedBatchNorm(in_ch, width * f, out2 * f, cfg.MODEL.RESNETS.NUM_GROUPS,
                                                            cfg.MODEL.RESNETS.STRIDE_IN_1X1, stride))
                 stride, in_ch = 1, out2 * f
             self.add_module("layer%d" % i, nn.Sequential(*blocks))
