@@ -201,7 +201,7 @@ _BF16_STORAGE = os.environ.get("MMT_BF16_STORAGE", "0") != "0"
 # against fp64 no larger than the 3-term bf16 split's (tools/bench_f16x2.py, profiles/r03_precision_f16x2.txt).
 F16X2_DEFAULT = os.environ.get("MMT_F16X2", "1") != "0"
 F16X2 = F16X2_DEFAULT
-F16X2_TILED = True   # also the tiled kernel (1x1, small-map 3x3, fc), not only the strip kernel
+F16X2_TILED = True   # (constant, read by bench.py: the tiled kernel -- 1x1, small-map 3x3, fc -- runs on the fp16 split like the strip kernel)
 F16_STATS = {"wgrad": 0, "conv": 0, "tiled": 0, "pg": 0, "amax_pass": 0, "fallback": 0, "weight_pack": 0}   # launches that took the fp16 path (tools, tests)
 WGRAD_F16_MIN_ELEMS = 1 << 22
 _F16W = {}   # weight address -> (key, planes, device scale)
@@ -312,6 +312,67 @@ def f16_flush_stats():
     torch.cuda.synchronize()
 
 
+# ---- what a producer leaves on a tensor object (plain attributes; each carries the tensor's version counter at the time and is
+# void once the tensor has been modified):
+#   _mmt_amax   (statistics slot -- anything with a data_ptr() --, version)
+#   _mmt_rb     (row-blocked fp16 planes, device view of their scale, version, "epi" | "split", images covered or None = all)
+#   _mmt_planes (bf16 planes of the 3-term split, version)
+def _recorded(x):
+    """the current (statistics slot, version) of x, or None"""
+    am = getattr(x, "_mmt_amax", None)
+    return am if am is not None and am[1] == x._version else None
+
+
+def _rb_of(x):
+    """the current row-blocked planes record of x, or None"""
+    rb = getattr(x, "_mmt_rb", None)
+    return rb if rb is not None and rb[2] == x._version else None
+
+
+def _rb_attach(x, planes, scale, kind, images=None):
+    """kind "epi": written by the epilogue of the launch that produced x, with the site's scale of the step before (a consumer's guard
+    tests it: lag); "split": by a pass over x.  images: planes for the first n images of the batch only"""
+    x._mmt_rb = (planes, scale, x._version, kind, images)
+
+
+def carry(src, dst, rb=True, planes=True, images=None):
+    """dst holds the same values as src (a view, an alias) or, images=(lo, hi), is that batch slice of it: what the producer of src
+    left on it goes along -- the statistics always (a maximum over more elements is an upper bound: all the fp16 split's scale
+    needs), the planes unless switched off (a reshaped or subsampled tensor has another plane order)"""
+    am = _recorded(src)
+    if am is not None:
+        dst._mmt_amax = (am[0], dst._version)
+    if planes:
+        pl = planes_of(src)
+        if pl is not None:
+            if images is not None:
+                per = src.numel() // src.shape[0]
+                pl = pl[:, images[0] * per:images[1] * per]
+            dst._mmt_planes = (pl, dst._version)
+    if rb:
+        r = _rb_of(src)
+        if r is not None:
+            if images is None:
+                _rb_attach(dst, r[0], r[1], r[3], r[4])
+            elif r[4] is None or images[1] <= r[4]:   # (image-major planes: a batch slice is a slice, also inside planes of the leading images)
+                per = src.numel() // src.shape[0]
+                _rb_attach(dst, r[0][:, images[0] * per:images[1] * per], r[1], r[3])
+
+
+def carry_stats(src, dst):
+    """the statistics alone: dst is a reshaped view of src, or holds a subset / the window maxima of its non-negative values"""
+    am = getattr(src, "_mmt_amax", None)
+    if am is not None and am[1] == src._version:
+        dst._mmt_amax = (am[0], dst._version)
+
+
+def drop(x):
+    """x was modified through raw pointers: what its producer recorded about it no longer holds"""
+    for a in ("_mmt_amax", "_mmt_rb", "_mmt_planes"):
+        if getattr(x, a, None) is not None:
+            setattr(x, a, None)
+
+
 def _site_ok(site, x, count=True):
     """may the consumer `site` take `x` on the two-term fp16 split?  (lagged crest-factor test, see above)"""
     ent = _SITES.get(site)
@@ -334,8 +395,8 @@ def _site_ok(site, x, count=True):
         elif pool.gen > gen + 1:
             ent[1] = None    # overwritten before anybody looked
     if ent[1] is None:
-        am = getattr(x, "_mmt_amax", None)
-        if am is not None and am[1] == x._version and type(am[0]) is _Slot and type(am[0].pool) is _StatPool:
+        am = _recorded(x)
+        if am is not None and type(am[0]) is _Slot and type(am[0].pool) is _StatPool:
             ent[1] = am[0]   # (a launch plan's slots never travel to the host: they would sit here for ever and switch the lagged
                              # test off for the site -- replayed passes rely on the kernels' device-side guard alone)
     if not ent[0] and count:
@@ -351,8 +412,8 @@ def _guard(am):
 
 def _amax_of(x):
     """the recorded (statistics slot, version) of x, taking one reduction pass when nobody recorded it"""
-    am = getattr(x, "_mmt_amax", None)
-    if am is None or am[1] != x._version:
+    am = _recorded(x)
+    if am is None:
         F16_STATS["amax_pass"] += 1
         if AMAX_LOG is not None:   # tools/f16_stats.py: who needed a reduction pass of its own
             import sys
@@ -374,8 +435,8 @@ def stats_of_convex_combination(out, sources):
     over `out`; the (at most 8) slot addresses are kernel arguments.  Nothing happens unless every source carries a recorded slot."""
     slots = []
     for t in sources:
-        am = getattr(t, "_mmt_amax", None)
-        if am is None or am[1] != t._version or type(am[0]) is not _Slot:
+        am = _recorded(t)
+        if am is None or type(am[0]) is not _Slot:
             return
         slots.append(am[0].ptr)
     if not slots or len(slots) > 8:
@@ -418,7 +479,7 @@ def sum_stats(ts, rb_site=None):
                 _check(lib().mmt_sum_stats_rb(p[0], p[1], p[2], p[3], y.data_ptr(), N * Hh, W, C, slot.ptr, pl.data_ptr(), n,
                                               t.base + 8 * i, nxt, _stream()), "mmt_sum_stats_rb")
                 y._mmt_amax = (slot, y._version)
-                y._mmt_rb = (pl, _rb_scale_view(t, i), y._version, "epi")
+                _rb_attach(y, pl, _rb_scale_view(t, i), "epi")
                 return y
             # no scale yet: the sum alone (planes NULL); its maximum becomes the site's first pending maximum
             N, C, Hh, W = a.shape
@@ -443,8 +504,8 @@ def f16_split(x, site=None):
     saturating beyond."""
     n = x.numel()
     xp = torch.empty((2, n), dtype=torch.float16, device=x.device)
-    am = getattr(x, "_mmt_amax", None)
-    if am is not None and am[1] == x._version:
+    am = _recorded(x)
+    if am is not None:
         # the convolution that produced x recorded max |x| in its epilogue (mmt_conv_args.y_amax): the split pass alone
         st = torch.empty((1,), dtype=torch.float32, device=x.device)
         _check(lib().mmt_split_planes_f16(x.data_ptr(), xp.data_ptr(), xp.stride(0), n, 1.0, am[0].data_ptr(), st.data_ptr(),
@@ -596,8 +657,8 @@ def f16_split_pg(x):
     if not PG_RB:
         xp, st = f16_split(x)
         return xp, st, 0, 0
-    rb = getattr(x, "_mmt_rb", None)
-    if rb is not None and len(rb) > 3 and rb[2] == x._version and rb[3] == "epi" and (len(rb) < 5 or rb[4] is None or rb[4] >= x.shape[0]):
+    rb = _rb_of(x)
+    if rb is not None and rb[3] == "epi" and (rb[4] is None or rb[4] >= x.shape[0]):
         F16_STATS["rb_epi"] = F16_STATS.get("rb_epi", 0) + 1
         return rb[0], rb[1], 1, 1
     F16_STATS["rb_split"] = F16_STATS.get("rb_split", 0) + 1
@@ -618,7 +679,7 @@ def f16_split_pg(x):
     # keep them only where a weight gradient can follow; a backward pass runs with autograd's grad mode OFF like the teacher's forward,
     # so that test would drop the gradients' planes too -- the RPN head's weight gradients would fall back to the slower kernel.  Since
     # round 6 few tensors are split here at all: 10 per step, 0.57 GB)
-    x._mmt_rb = (xp, st, x._version, "split")
+    _rb_attach(x, xp, st, "split")
     return xp, st, 1, 0
 
 
@@ -1385,17 +1446,23 @@ def box_decode(codes, boxes, weights, clip, row_off=None, lim=None):
 
 
 # ------------------------------------------------------------------------------------------ conv
-def _conv_args(x, w, stride, pad, Ho, Wo):
-    a = ConvArgs()
-    N, Cin, H, W = x.shape
-    Cout, Cin_w, KH, KW = w.shape
-    if Cin_w != Cin:
-        raise RuntimeError("conv channel mismatch: x has %d, w has %d" % (Cin, Cin_w))
-    a.x, a.w = x.data_ptr(), w.data_ptr()
+def _conv_out_hw(H, W, KH, KW, stride, pad):
+    return (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+
+
+def _conv_shape(a, N, H, W, Cin, Cout, KH, KW, stride, pad, Ho, Wo):
+    """the shape half of a mmt_conv_args (everything else in a fresh block is null / zero)"""
     a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = N, H, W, Cin, Cout, KH, KW
     a.stride, a.pad, a.Ho, a.Wo = stride, pad, Ho, Wo
     a.out_stride, a.mask_scale = 1, 1.0
     return a
+
+
+def _weight_dims(Cin, w_shape):
+    Cout, Cin_w, KH, KW = w_shape
+    if Cin_w != Cin:
+        raise RuntimeError("conv channel mismatch: x has %d, w has %d" % (Cin, Cin_w))
+    return Cout, KH, KW
 
 
 def split_planes(x, out=None):
@@ -1412,10 +1479,8 @@ def planes_wanted_3x3(N, C, H, W, Cout):
     (asked by the PRODUCER of that tensor, which then writes the planes from its epilogue: conv_forward(want_planes=True))"""
     if get_conv_precision() != 3 or F16X2:   # (on the fp16 split no epilogue writes bf16 planes: consumers scale
         return False                                              # the tensor themselves, conv_forward ignores the request)
-    a = ConvArgs()
+    a = _conv_shape(ConvArgs(), N, H, W, C, Cout, 3, 3, 1, 1, H, W)
     a.x, a.w_planes = 16, 16  # placeholders: only the shape is looked at
-    a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = N, H, W, C, Cout, 3, 3
-    a.stride, a.pad, a.Ho, a.Wo, a.out_stride = 1, 1, H, W, 1
     return lib().mmt_conv_wants_planes(ctypes.byref(a)) == 1
 
 
@@ -1437,6 +1502,97 @@ _PLAN = {}
 _WPLAN = {}   # weight gradient: (shapes, stride, pad, dtypes) -> (shape half of mmt_conv_args, split count)
 _PLAN_EPOCH = [0]
 FAST_PLANS = True
+# the path of a convolution call: the library's own dispatch (fp32 MFMA, bf16, the bf16 splits), or the two-term fp16 split on the
+# tiled / row-resident kernels (x split in registers), on the tap-strip kernel, on the plane-fed implicit GEMM (x as fp16 planes)
+K_LIB, K_TILED, K_STRIP, K_PG = -1, 0, 1, 2
+_F16_STAT = {K_TILED: "tiled", K_STRIP: "conv", K_PG: "pg"}
+
+
+def _conv_kind(a, x, w, f16_src, io, y_out, mul, out_stride, res_mode, prec):
+    """which path the call with the argument block `a` (x, the weight or its planes, the shape and the output stride filled in) takes
+    -> (kind, is the shape one of the tap-strip kernel's, the fp16 split's weight source (tensor, flipped?, row scale) or None).
+    The strip kernel wins over the plane-fed GEMM, that over the tiled kernels; a site whose input defeats fp16 (lagged crest-factor
+    test, counted in F16_STATS["fallback"]) stays on the library's 3-term bf16 split."""
+    # would this shape run on the tap-strip kernel?  (asked once: the answer depends on the shape only)
+    strip = bool(a.KH == 3 and a.w_planes and not io and lib().mmt_conv_wants_planes(ctypes.byref(a)) == 1)
+    if not (F16X2 and not io and prec == 3) or (w is None and f16_src is None):
+        return K_LIB, strip, None
+    if strip and out_stride == 1 and y_out is None and mul is None:
+        kind = K_STRIP
+    elif a.w_planes and a.Cout > 32 and a.Cin % 16 == 0 and y_out is None:
+        kind = K_TILED   # 1x1 layers, 3x3 on small maps, fc
+    else:
+        return K_LIB, strip, None
+    src = (w, False, None) if w is not None else (nhwc(f16_src[0]), True, f16_src[1])
+    if not _site_ok((src[0].data_ptr(), src[1]), x):
+        return K_LIB, strip, None
+    if (kind == K_TILED and mul is None and out_stride == 1 and res_mode <= 1 and a.KH * a.KW >= 4
+            and lib().mmt_conv_pg_wanted(ctypes.byref(a)) == 1):
+        kind = K_PG
+    return kind, strip, src
+
+
+def _ev():
+    e = torch.cuda.Event(enable_timing=True)
+    e.record()
+    return e
+
+
+def _profiled(a, e0, tag, ksplit, pre, ebytes):
+    """closes the bracket e0 = _ev() opened around a launch of the block `a`: one PROFILE record (bench.py, tools/conv_table.py) --
+    (algorithmic FLOPs, start, stop, (tag, shape ...), K split, the event pair around the launch's pre-pass or None, the bytes of the
+    fused epilogue's operands)"""
+    PROFILE.append((2.0 * a.N * a.Ho * a.Wo * a.Cout * a.Cin * a.KH * a.KW, e0, _ev(),
+                    (tag, a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.stride, a.out_stride), ksplit, pre, ebytes))
+
+
+def _conv_f16(a, kind, x, src, y, slot, rb_site, tile_rows=0, ksplit=0, xp=None, prof=None, counted=True):
+    """THE launch of the two-term fp16 split: `a` holds the shape, x, y and the epilogue; src = (weight, flipped?, row scale) names the
+    weight planes; slot: the statistics slot y's maximum goes to (a.y_amax) or None; rb_site: None, or the producing site whose
+    row-blocked planes of y this launch's epilogue writes (_rb_produce, asked with the block filled: the weight pointer, the mask and
+    the residual mode decide whether the kernel the launch takes has the plane store); tile_rows /
+    ksplit / xp = (planes, scale[, layout, lag]): conv_forward_pg's overrides; prof: None, or the fused epilogue's bytes -- the
+    launch is bracketed for PROFILE (the strip and plane-fed kinds with their input pass in a bracket of its own; the tiled kind
+    only where it runs the dominant 128 x 128 kernel, unless PROFILE_ALL); counted: F16_STATS counts what the DISPATCHER sent to a
+    kind (conv_forward and its plans), not the explicit conv_forward_pg of tools and tests"""
+    wsrc, flipped, fscale = src
+    e0 = _ev() if prof is not None and kind != K_TILED else None
+    am = _amax_of(x)
+    a.f16_guard_x = _guard(am)
+    # the fp32 weights for the kernels' slow, exact path (a tensor whose range defeats fp16: decided per block on the device)
+    if flipped:
+        a.w_src, a.w_src_scale = wsrc.data_ptr(), _p(fscale)
+    else:
+        a.w = wsrc.data_ptr()
+    wp16, sw = f16_weight_planes(wsrc, fscale, flipped)
+    a.w_planes, a.w_plane_stride = wp16.data_ptr(), wp16.stride(0)
+    yrb = _rb_produce(a, y, rb_site) if rb_site is not None else None
+    if counted:
+        F16_STATS[_F16_STAT[kind]] += 1
+    if kind == K_TILED:   # x is split in registers, its recorded maximum gives the scale
+        pre = None
+        if prof is not None:
+            var = lib().mmt_conv_variant(ctypes.byref(a))
+            if PROFILE_ALL or var == 1:
+                tag, ks, e0 = "fwd%d" % var, lib().mmt_conv_ksplit(ctypes.byref(a)), _ev()
+        _check(lib().mmt_conv_forward_f16x2(ctypes.byref(a), am[0].data_ptr(), sw.data_ptr(), _stream()), "mmt_conv_forward_f16x2")
+    else:                 # x's planes (its producer's, or one split pass), then the launch
+        xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x) if xp is None else (tuple(xp) + (0, 0))[:4]
+        a.x_planes, a.x_plane_stride = xp16.data_ptr(), xp16.stride(0)
+        if e0 is not None:
+            pre, tag, ks, e0 = (e0, _ev()), "fwd5" if kind == K_PG else "fwd4", 1, _ev()
+        if kind == K_PG:
+            _check(lib().mmt_conv_forward_pg(ctypes.byref(a), sx.data_ptr(), sw.data_ptr(), tile_rows, ksplit, _stream()),
+                   "mmt_conv_forward_pg")
+        else:
+            _check(lib().mmt_conv3x3_strip_f16x2(ctypes.byref(a), sx.data_ptr(), sw.data_ptr(), _stream()), "mmt_conv3x3_strip_f16x2")
+    if e0 is not None:
+        _profiled(a, e0, tag, ks, pre, prof)
+    if slot is not None:
+        y._mmt_amax = (slot, y._version)
+    if yrb is not None:   # (y's row-blocked planes came out of this launch's epilogue)
+        _rb_attach(y, yrb[0], yrb[1], "epi", yrb[2])
+    return y
 
 
 def _plan_key(x, w, f16_src, stride, pad, relu, res, res_mode, mask):
@@ -1470,38 +1626,16 @@ def _conv_fast(x, w, scale, shift, stride, pad, relu, res, res_mode, mask, mask_
         a.res = nhwc(res).data_ptr()
     if mask is not None:
         a.mask, a.mask_scale = nhwc(mask).data_ptr(), float(mask_scale)
+    if a.KH == 3:
+        # the library's choice between the strip, plane-fed and tiled kernels can be switched per call (MMT_STRIP, MMT_PG): the two
+        # questions _conv_kind asked, about the shape and about weight planes being there at all (a placeholder until the launch)
+        a.w_planes = 16
+        if (lib().mmt_conv_wants_planes(ctypes.byref(a)) == 1) != (kind == K_STRIP) or (
+                kind != K_STRIP and (lib().mmt_conv_pg_wanted(ctypes.byref(a)) == 1) != (kind == K_PG)):
+            return None   # re-plan
     slot = _amax_slot(x.device)
     a.y_amax = slot.ptr
-    wp16, sw = f16_weight_planes(wsrc, f16_src[1] if flipped else None, flipped)
-    a.w_planes, a.w_plane_stride = wp16.data_ptr(), wp16.stride(0)
-    if a.KH == 3 and ((lib().mmt_conv_wants_planes(ctypes.byref(a)) == 1) != (kind == 1) or (
-            kind != 1 and (lib().mmt_conv_pg_wanted(ctypes.byref(a)) == 1) != (kind == 2))):
-        return None   # the library's choice between the strip, plane-fed and tiled kernels can be switched per call (MMT_STRIP, MMT_PG): re-plan
-    # the fp32 weights for the kernels' slow, exact path (a tensor whose range defeats fp16: decided per block on the device)
-    if flipped:
-        a.w_src, a.w_src_scale = wsrc.data_ptr(), _p(f16_src[1])
-    else:
-        a.w = wsrc.data_ptr()
-    am = _amax_of(x)
-    a.f16_guard_x = _guard(am)
-    yrb = _rb_produce(a, y, rb_site) if rb_site is not None else None   # (round 6: y's row-blocked planes from this launch's epilogue)
-    if kind == 0:     # tiled / row-resident kernels: x is split in registers, its recorded maximum gives the scale
-        F16_STATS["tiled"] += 1
-        _check(lib().mmt_conv_forward_f16x2(ctypes.byref(a), am[0].data_ptr(), sw.data_ptr(), _stream()), "mmt_conv_forward_f16x2")
-    elif kind == 2:   # plane-fed implicit GEMM (3x3 on small maps, mask head): x's planes (its producer's, or one split pass), then the launch
-        F16_STATS["pg"] += 1
-        xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x)
-        a.x_planes, a.x_plane_stride = xp16.data_ptr(), xp16.stride(0)
-        _check(lib().mmt_conv_forward_pg(ctypes.byref(a), sx.data_ptr(), sw.data_ptr(), 0, 0, _stream()), "mmt_conv_forward_pg")
-    else:             # tap-strip kernel: the same
-        F16_STATS["conv"] += 1
-        xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x)
-        a.x_planes, a.x_plane_stride = xp16.data_ptr(), xp16.stride(0)
-        _check(lib().mmt_conv3x3_strip_f16x2(ctypes.byref(a), sx.data_ptr(), sw.data_ptr(), _stream()), "mmt_conv3x3_strip_f16x2")
-    y._mmt_amax = (slot, y._version)
-    if yrb is not None:
-        y._mmt_rb = (yrb[0], yrb[1], y._version, "epi", yrb[2])
-    return y
+    return _conv_f16(a, kind, x, (wsrc, flipped, f16_src[1] if flipped else None), y, slot, rb_site)
 
 
 def _plan_record(x, w, f16_src, stride, pad, relu, res, res_mode, mask, a, kind, Cout, Ho, Wo):
@@ -1509,11 +1643,10 @@ def _plan_record(x, w, f16_src, stride, pad, relu, res, res_mode, mask, a, kind,
     if key is None:
         return
     t = ConvArgs.from_buffer_copy(a)
-    # everything a call patches is cleared in the template (a stale pointer must never survive into a launch)
-    t.x = t.y = t.scale = t.shift = t.res = t.mask = t.mul = t.w = None
-    t.w_planes = t.x_planes = t.y_planes = t.y_amax = t.f16_x_amax = t.f16_dy_amax = None
-    t.f16_guard_x = t.f16_guard_dy = t.w_src = t.w_src_scale = None
-    t.y_rb = t.y_rb_scale = t.y_amax_next = None
+    # every pointer is cleared in the template (a stale one must never survive into a launch), and what a call sets with them
+    for name, typ in ConvArgs._fields_:
+        if typ is c_void_p:
+            setattr(t, name, None)
     t.w_plane_stride = t.x_plane_stride = t.y_plane_stride = t.x_planes_layout = t.y_rb_stride = t.x_planes_lag = t.y_rb_rows = 0
     t.mask_scale, t.io_bf16, t.y_amax_stats = 1.0, 0, 1
     if len(_PLAN) > 4096:
@@ -1562,32 +1695,24 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
     if out_dtype == torch.bfloat16:
         io |= IO_Y
     esz = 2 if out_dtype == torch.bfloat16 else 4
+    if w is not None:
+        w = nhwc(w)
+    Cout, KH, KW = _weight_dims(Cin, w_shape if w is None else w.shape)
+    Ho, Wo = _conv_out_hw(H, W, KH, KW, stride, pad)
+    if out_size is not None and w is not None:
+        if out_size[0] > Ho or out_size[1] > Wo or out_stride > 1:
+            raise RuntimeError("conv_forward: out_size can only trim the output")
+        Ho, Wo = out_size
+    a = _conv_shape(ConvArgs(), N, H, W, Cin, Cout, KH, KW, stride, pad, Ho, Wo)
+    a.x = x.data_ptr()
     if w is None:
-        Cout, Cin_w, KH, KW = w_shape
-        if Cin_w != Cin:
-            raise RuntimeError("conv channel mismatch: x has %d, w has %d" % (Cin, Cin_w))
-        Ho = (H + 2 * pad - KH) // stride + 1
-        Wo = (W + 2 * pad - KW) // stride + 1
-        a = ConvArgs()
-        a.x = x.data_ptr()
-        a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = N, H, W, Cin, Cout, KH, KW
-        a.stride, a.pad, a.Ho, a.Wo = stride, pad, Ho, Wo
-        a.out_stride, a.mask_scale = 1, 1.0
         a.w_planes, a.w_plane_stride = planes.data_ptr(), planes.stride(0)
         _TLS.bf16_owner = None
         if f16_src is not None:   # data-gradient planes of a flat model's weight: deferred like the forward planes
             ent = PLANES.get(f16_src[0].data_ptr())
             _TLS.bf16_owner = ent[0]() if ent is not None else None
     else:
-        w = nhwc(w)
-        Cout, _, KH, KW = w.shape
-        Ho = (H + 2 * pad - KH) // stride + 1
-        Wo = (W + 2 * pad - KW) // stride + 1
-        if out_size is not None:
-            if out_size[0] > Ho or out_size[1] > Wo or out_stride > 1:
-                raise RuntimeError("conv_forward: out_size can only trim the output")
-            Ho, Wo = out_size
-        a = _conv_args(x, w, stride, pad, Ho, Wo)
+        a.w = w.data_ptr()
         _keep = _weight_planes(w, a)  # noqa: F841  (keeps a per-call plane buffer alive until the launch is queued)
     if out_stride > 1:
         oh, ow = out_hw
@@ -1596,39 +1721,18 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
     else:
         y = y_out if y_out is not None else empty_nhwc(N, Cout, Ho, Wo, x.device, dtype=out_dtype)
     a.y = y.data_ptr() + esz * int(y_offset)
-    y_planes = None
     prec = get_conv_precision()
-    # would this shape run on the tap-strip kernel?  (asked once: the answer depends on the shape only)
-    strip = bool(a.KH == 3 and a.w_planes and not io and lib().mmt_conv_wants_planes(ctypes.byref(a)) == 1)
-    f16 = None   # (weight source, flipped?, row scale): this call runs on the two-term fp16 split (experiment)
-    if F16X2 and strip and out_stride == 1 and y_out is None and mul is None and prec == 3:
-        if w is not None:
-            f16 = (w, False, None)
-        elif f16_src is not None:
-            f16 = (nhwc(f16_src[0]), True, f16_src[1])
-    f16t = None   # the same arithmetic on the tiled DMA kernel (1x1 layers, 3x3 on small maps, fc): x split in registers
-    want_amax = False
-    if F16X2 and not io and prec == 3:
-        # consumers on the fp16 split scale y themselves: no bf16 planes from this epilogue, max |y| recorded on the way
-        want_amax, want_planes = True, False
-        if (f16 is None and F16X2_TILED and a.w_planes and Cout > 32 and Cin % 16 == 0 and y_out is None):
-            if w is not None:
-                f16t = (w, False, None)
-            elif f16_src is not None:
-                f16t = (nhwc(f16_src[0]), True, f16_src[1])
-        sel = f16 if f16 is not None else f16t
-        if sel is not None and not _site_ok((sel[0].data_ptr(), sel[1]), x):
-            f16 = f16t = None   # this input's dynamic range defeats fp16 (lagged crest-factor test): 3-term bf16 split
-    pg = None   # the same arithmetic on the plane-fed implicit GEMM (round 5): shapes the library wants there
-    if (f16t is not None and f16 is None and mul is None and out_stride == 1 and res_mode <= 1 and KH * KW >= 4
-            and lib().mmt_conv_pg_wanted(ctypes.byref(a)) == 1):
-        pg, f16t = f16t, None
-    if f16 is not None:
-        x_planes = None
+    kind, strip, src = _conv_kind(a, x, w, f16_src, io, y_out, mul, out_stride, res_mode, prec)
+    want_amax = bool(F16X2 and not io and prec == 3)
+    if want_amax:
+        want_planes = False   # consumers on the fp16 split scale y themselves: no bf16 planes from this epilogue, max |y| recorded on the way
+    if kind != K_LIB:
+        x_planes = None       # (the fp16 kinds split x in registers or read fp16 planes of their own)
+    y_planes = None
     if want_planes and out_stride == 1 and y_out is None and Cout % 4 == 0 and not io:
         y_planes = torch.empty((3, y.numel()), dtype=torch.bfloat16, device=x.device)
         a.y_planes, a.y_plane_stride = y_planes.data_ptr(), y_planes.stride(0)
-    auto_split = x_planes is None and strip and f16 is None
+    auto_split = x_planes is None and strip and kind == K_LIB
     if auto_split:
         # one pass over x; the 3x3 kernel then reads bf16 planes (9 taps x Cout/128 re-reads).  Allocated here, filled
         # below INSIDE the profiling bracket: the pass is part of this convolution's cost
@@ -1655,120 +1759,27 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
     if mul is not None:
         mul = nhwc(mul)
         a.mul = mul.data_ptr()
-    yrb = None
-    if rb_site is not None and (pg is not None or f16t is not None or f16 is not None) and amax_slot is not None and mul is None:
-        yrb = _rb_produce(a, y, rb_site)   # (round 6: y's row-blocked planes from this launch's epilogue, see f16_split_pg)
-    if pg is not None:
-        rec = PROFILE is not None
-        if rec:
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-            ev[0].record()
-        F16_STATS["pg"] += 1
+    ebytes = _epilogue_bytes(y, res, res_mode, mask, mul) if PROFILE is not None else None
+    if kind != K_LIB:
         if fast_ok and not io:
-            _plan_record(x, w, f16_src, stride, pad, relu, res, res_mode, mask, a, 2, Cout, Ho, Wo)
-        a.f16_guard_x = _guard(_amax_of(x))
-        if pg[1]:
-            a.w_src, a.w_src_scale = pg[0].data_ptr(), _p(pg[2])
-        wp16, sw = f16_weight_planes(pg[0], pg[2], pg[1])
-        xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x)
-        a.x_planes, a.x_plane_stride = xp16.data_ptr(), xp16.stride(0)
-        a.w_planes, a.w_plane_stride = wp16.data_ptr(), wp16.stride(0)
-        if rec:
-            ev[1].record()
-            ev[2].record()
-        _check(lib().mmt_conv_forward_pg(ctypes.byref(a), sx.data_ptr(), sw.data_ptr(), 0, 0, _stream()), "mmt_conv_forward_pg")
-        if rec:
-            ev[3].record()
-            PROFILE.append((2.0 * N * Ho * Wo * Cout * Cin * KH * KW, ev[2], ev[3],
-                            ("fwd5", N, H, W, Cin, Cout, KH, stride, out_stride), 1, (ev[0], ev[1]),
-                            _epilogue_bytes(y, res, res_mode, mask, mul)))
-        if amax_slot is not None:
-            y._mmt_amax = (amax_slot, y._version)
-        if yrb is not None:
-            y._mmt_rb = (yrb[0], yrb[1], y._version, "epi", yrb[2])
-        return y
-    if f16t is not None:
-        am = _amax_of(x)
-        wp16, sw = f16_weight_planes(f16t[0], f16t[2], f16t[1])
-        a.w_planes, a.w_plane_stride = wp16.data_ptr(), wp16.stride(0)
-        a.x_planes = None
-        a.f16_guard_x = _guard(am)
-        if f16t[1]:
-            a.w_src, a.w_src_scale = f16t[0].data_ptr(), _p(f16t[2])
-        F16_STATS["tiled"] += 1
-        if fast_ok and not io:
-            _plan_record(x, w, f16_src, stride, pad, relu, res, res_mode, mask, a, 0, Cout, Ho, Wo)
-        rec = PROFILE is not None and (PROFILE_ALL or lib().mmt_conv_variant(ctypes.byref(a)) == 1)
-        if rec:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _check(lib().mmt_conv_forward_f16x2(ctypes.byref(a), am[0].data_ptr(), sw.data_ptr(), _stream()), "mmt_conv_forward_f16x2")
-        if rec:
-            e1.record()
-            PROFILE.append((2.0 * N * Ho * Wo * Cout * Cin * KH * KW, e0, e1,
-                            ("fwd%d" % lib().mmt_conv_variant(ctypes.byref(a)), N, H, W, Cin, Cout, KH, stride, out_stride),
-                            lib().mmt_conv_ksplit(ctypes.byref(a)), None, _epilogue_bytes(y, res, res_mode, mask, mul)))
-        if amax_slot is not None:
-            y._mmt_amax = (amax_slot, y._version)
-        if yrb is not None:
-            y._mmt_rb = (yrb[0], yrb[1], y._version, "epi", yrb[2])
-        return y
-    if f16 is not None:
-        rec = PROFILE is not None
-        if rec:
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-            ev[0].record()
-        F16_STATS["conv"] += 1
-        if fast_ok and not io:
-            _plan_record(x, w, f16_src, stride, pad, relu, res, res_mode, mask, a, 1, Cout, Ho, Wo)
-        a.f16_guard_x = _guard(_amax_of(x))
-        if f16[1]:
-            a.w_src, a.w_src_scale = f16[0].data_ptr(), _p(f16[2])
-        xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x)
-        wp16, sw = f16_weight_planes(f16[0], f16[2], f16[1])
-        a.x_planes, a.x_plane_stride = xp16.data_ptr(), xp16.stride(0)
-        a.w_planes, a.w_plane_stride = wp16.data_ptr(), wp16.stride(0)
-        if rec:
-            ev[1].record()
-            ev[2].record()
-        _check(lib().mmt_conv3x3_strip_f16x2(ctypes.byref(a), sx.data_ptr(), sw.data_ptr(), _stream()),
-               "mmt_conv3x3_strip_f16x2")
-        if rec:
-            ev[3].record()
-            PROFILE.append((2.0 * N * Ho * Wo * Cout * Cin * KH * KW, ev[2], ev[3],
-                            ("fwd4", N, H, W, Cin, Cout, KH, stride, out_stride), 1, (ev[0], ev[1]),
-                            _epilogue_bytes(y, res, res_mode, mask, mul)))
-        if amax_slot is not None:
-            y._mmt_amax = (amax_slot, y._version)
-        if yrb is not None:
-            y._mmt_rb = (yrb[0], yrb[1], y._version, "epi", yrb[2])
-        return y
-    if PROFILE is not None:
-        var = lib().mmt_conv_variant(ctypes.byref(a))
-        if var in (1, 4) or PROFILE_ALL:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            pre = None
-            if auto_split:  # the plane-split pass of the input (when no producer wrote the planes): its own bracket
-                pre = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                pre[0].record()
-                split_planes(x, x_planes)
-                pre[1].record()
-            e0.record()
-            _ensure_bf16()
-            _check(lib().mmt_conv_forward(ctypes.byref(a), _stream()), "mmt_conv_forward")
-            e1.record()
-            PROFILE.append((2.0 * N * Ho * Wo * Cout * Cin * KH * KW, e0, e1,
-                            ("fwd%d" % var, N, H, W, Cin, Cout, KH, stride, out_stride),
-                            lib().mmt_conv_ksplit(ctypes.byref(a)), pre, _epilogue_bytes(y, res, res_mode, mask, mul)))
-            if y_planes is not None:
-                y._mmt_planes = (y_planes, y._version)
-            if amax_slot is not None:
-                y._mmt_amax = (amax_slot, y._version)
-            return y
-    if auto_split:
+            _plan_record(x, w, f16_src, stride, pad, relu, res, res_mode, mask, a, kind, Cout, Ho, Wo)
+        if amax_slot is None or mul is not None:
+            rb_site = None   # (y's row-blocked planes come out of an epilogue that also records max |y|, see f16_split_pg)
+        # (a, kind, x, src, y, slot, rb_site, tile_rows, ksplit, xp, prof = the epilogue's bytes when PROFILE is on)
+        return _conv_f16(a, kind, x, src, y, amax_slot, rb_site, 0, 0, None, ebytes)
+    var = lib().mmt_conv_variant(ctypes.byref(a)) if ebytes is not None else 0
+    rec = ebytes is not None and (var in (1, 4) or PROFILE_ALL)
+    pre = None
+    if auto_split:   # the plane-split pass of the input (when no producer wrote the planes): its own bracket
+        p0 = _ev() if rec else None
         split_planes(x, x_planes)
+        if rec:
+            pre = (p0, _ev())
+    e0 = _ev() if rec else None
     _ensure_bf16()
     _check(lib().mmt_conv_forward(ctypes.byref(a), _stream()), "mmt_conv_forward")
+    if rec:
+        _profiled(a, e0, "fwd%d" % var, lib().mmt_conv_ksplit(ctypes.byref(a)), pre, ebytes)
     if y_planes is not None:
         y._mmt_planes = (y_planes, y._version)
     if amax_slot is not None:
@@ -1784,21 +1795,11 @@ def conv_forward_pg(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, r
     form.  tile_rows / ksplit: 0 = the library's choice.  Raises for shapes the kernel does not take."""
     x = nhwc(x)
     N, Cin, H, W = x.shape
-    if w is not None:
-        wsrc, flipped, fscale = nhwc(w), False, None
-        Cout, _, KH, KW = wsrc.shape
-    else:
-        wsrc, flipped, fscale = nhwc(f16_src[0]), True, f16_src[1]
-        Cout, Cin_w, KH, KW = w_shape
-        if Cin_w != Cin:
-            raise RuntimeError("conv channel mismatch: x has %d, w has %d" % (Cin, Cin_w))
-    Ho = (H + 2 * pad - KH) // stride + 1
-    Wo = (W + 2 * pad - KW) // stride + 1
-    a = ConvArgs()
+    src = (nhwc(w), False, None) if w is not None else (nhwc(f16_src[0]), True, f16_src[1])
+    Cout, KH, KW = _weight_dims(Cin, src[0].shape if w is not None else w_shape)
+    Ho, Wo = _conv_out_hw(H, W, KH, KW, stride, pad)
+    a = _conv_shape(ConvArgs(), N, H, W, Cin, Cout, KH, KW, stride, pad, Ho, Wo)
     a.x = x.data_ptr()
-    a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = N, H, W, Cin, Cout, KH, KW
-    a.stride, a.pad, a.Ho, a.Wo = stride, pad, Ho, Wo
-    a.out_stride, a.mask_scale = 1, 1.0
     y = empty_nhwc(N, Cout, Ho, Wo, x.device)
     a.y = y.data_ptr()
     a.scale, a.shift, a.relu = _p(scale), _p(shift), 1 if relu else 0
@@ -1808,19 +1809,8 @@ def conv_forward_pg(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, r
         a.mask, a.mask_scale = nhwc(mask).data_ptr(), float(mask_scale)
     slot = _amax_slot(x.device)
     a.y_amax, a.y_amax_stats = slot.ptr, 1
-    if flipped:
-        a.w_src, a.w_src_scale = wsrc.data_ptr(), _p(fscale)
-    else:
-        a.w = wsrc.data_ptr()
-    a.f16_guard_x = _guard(_amax_of(x))
-    wp16, sw = f16_weight_planes(wsrc, fscale, flipped)
-    xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x) if xp is None else (tuple(xp) + (0, 0))[:4]
-    a.x_planes, a.x_plane_stride = xp16.data_ptr(), xp16.stride(0)
-    a.w_planes, a.w_plane_stride = wp16.data_ptr(), wp16.stride(0)
-    _check(lib().mmt_conv_forward_pg(ctypes.byref(a), sx.data_ptr(), sw.data_ptr(), int(tile_rows), int(ksplit), _stream()),
-           "mmt_conv_forward_pg")
-    y._mmt_amax = (slot, y._version)
-    return y
+    # (a, kind, x, src, y, slot, rb_site, tile_rows, ksplit, xp, prof, counted)
+    return _conv_f16(a, K_PG, x, src, y, slot, None, int(tile_rows), int(ksplit), xp, None, False)
 
 
 def stem_fused(x, w_s2d, scale, shift):
@@ -1846,11 +1836,9 @@ def stem_fused(x, w_s2d, scale, shift):
 
 def conv_pg_plan(N, Cin, H, W, Cout, KH, KW, stride, pad):
     """(tile rows, K ranges) the library would run this shape with on the plane-fed kernel; (0, 0): not one of its shapes"""
-    a = ConvArgs()
+    Ho, Wo = _conv_out_hw(H, W, KH, KW, stride, pad)
+    a = _conv_shape(ConvArgs(), N, H, W, Cin, Cout, KH, KW, stride, pad, Ho, Wo)
     a.x = a.w_planes = 16   # placeholders: only the shape is looked at
-    a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = N, H, W, Cin, Cout, KH, KW
-    a.stride, a.pad, a.out_stride = stride, pad, 1
-    a.Ho, a.Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
     rows, ks = c_int(0), c_int(0)
     _check(lib().mmt_conv_pg_plan(ctypes.byref(a), ctypes.byref(rows), ctypes.byref(ks)), "mmt_conv_pg_plan")
     return rows.value, ks.value
@@ -1978,37 +1966,59 @@ def wgrad_prepare(x, dy):
         _amax_of(nhwc(dy))
 
 
-def _conv_wgrad_planes(x, dy, xr, dr, w_shape, stride, pad, dw, rowscale, dbias):
+def _wgrad_stats(x, dy, dw, passes):
+    """the recorded statistics (slot, version) of both operands of a weight gradient on the two-term fp16 split (3 products instead of
+    6), or None: not eligible -- an operand nobody recorded a maximum of (`passes`: big operands, where the saving pays for it, take a
+    reduction pass here), or a site whose range defeats fp16 (lagged crest-factor test)"""
+    ax, ad = _recorded(x), _recorded(dy)
+    if passes and x.numel() >= WGRAD_F16_MIN_ELEMS:
+        if ax is None:
+            ax = _amax_of(x)
+        if ad is None:
+            ad = _amax_of(dy)
+    if ax is None or ad is None or not (_site_ok(("wgx", dw.data_ptr()), x) and _site_ok(("wgd", dw.data_ptr()), dy)):
+        return None
+    return ax, ad
+
+
+def _wgrad_planes(x, dy, st=None):
+    """the row-blocked fp16 planes both operands carry for the whole batch -> (x's record, dy's record, lag bits), or None.  Planes a
+    producer's epilogue wrote carry a scale fixed beforehand: the kernel's guard tests it (bit 0: x, bit 1: dy), so with the operands'
+    statistics `st` at hand both guards must be there"""
+    xr, dr = _rb_of(x), _rb_of(dy)
+    if xr is None or dr is None or xr[4] is not None or dr[4] is not None:
+        return None
+    lag = (1 if xr[3] == "epi" else 0) | (2 if dr[3] == "epi" else 0)
+    if st is not None and lag and (_guard(st[0]) is None or _guard(st[1]) is None):
+        return None
+    return xr, dr, lag
+
+
+def _conv_wgrad_planes(x, dy, w_shape, stride, pad, dw, rowscale, dbias):
     """the weight gradient from the row-blocked fp16 planes both operands already have (include/mmtpsm.h: mmt_conv_wgrad_planes;
-    csrc/conv_wgpl.hip) -> False when the library does not take the layer"""
+    csrc/conv_wgpl.hip) -> False when the operands have none, or no recorded maxima, or the library does not take the layer"""
+    pl = _wgrad_planes(x, dy)
+    if pl is None:
+        return False
     Cout, Cin, KH, KW = w_shape
-    N, _, H, W = x.shape
     key = (x.shape, dy.shape, w_shape, stride, pad)
     plan = _WPLAN_PL.get(key)
     if plan is None:
-        a = ConvArgs()
-        a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = N, H, W, Cin, Cout, KH, KW
-        a.stride, a.pad, a.Ho, a.Wo = stride, pad, dy.shape[2], dy.shape[3]
-        a.out_stride = 1
+        a = _conv_shape(ConvArgs(), x.shape[0], x.shape[2], x.shape[3], Cin, Cout, KH, KW, stride, pad, dy.shape[2], dy.shape[3])
         splits = lib().mmt_conv_wgrad_planes_splits(ctypes.byref(a))
         if len(_WPLAN_PL) > 4096:
             _WPLAN_PL.clear()
         plan = _WPLAN_PL[key] = (bytes(a), splits)
-    if plan[1] <= 0:
+    splits = plan[1]
+    if splits <= 0:
         return False
-    ax, ad = getattr(x, "_mmt_amax", None), getattr(dy, "_mmt_amax", None)
-    if ax is None or ad is None or ax[1] != x._version or ad[1] != dy._version:
-        return False
-    if not (_site_ok(("wgx", dw.data_ptr()), x) and _site_ok(("wgd", dw.data_ptr()), dy)):
+    st = _wgrad_stats(x, dy, dw, False)
+    xr, dr, lag = pl
+    if st is None or (lag and (_guard(st[0]) is None or _guard(st[1]) is None)):
         return False
     a = ConvArgs.from_buffer_copy(plan[0])
     a.x = x.data_ptr()
-    a.f16_guard_x, a.f16_guard_dy = _guard(ax), _guard(ad)
-    # planes a producer's epilogue wrote carry a scale fixed beforehand: the kernel's guard tests it (bit 0: x, bit 1: dy)
-    a.x_planes_lag = (1 if len(xr) > 3 and xr[3] == "epi" else 0) | (2 if len(dr) > 3 and dr[3] == "epi" else 0)
-    if a.x_planes_lag and (a.f16_guard_x is None or a.f16_guard_dy is None):
-        return False
-    splits = plan[1]
+    a.f16_guard_x, a.f16_guard_dy, a.x_planes_lag = _guard(st[0]), _guard(st[1]), lag
     ws = torch.empty((splits * Cout * KH * KW * Cin,), dtype=torch.float32, device=x.device) if splits > 1 else None
     _TLS.last_ws = ws
     rc = lib().mmt_conv_wgrad_planes(ctypes.byref(a), dy.data_ptr(), xr[0].data_ptr(), xr[0].stride(0), dr[0].data_ptr(), dr[0].stride(0),
@@ -2042,54 +2052,35 @@ def conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale=None, dbias=None, side=
     x = nhwc(x)
     dy = nhwc(dy)
     Cout, Cin, KH, KW = w_shape
-    N, _, H, W = x.shape
-    if WG_PLANES and F16X2 and x.dtype == torch.float32 and dy.dtype == torch.float32:
-        xr, dr = getattr(x, "_mmt_rb", None), getattr(dy, "_mmt_rb", None)
-        if (xr is not None and dr is not None and xr[2] == x._version and dr[2] == dy._version and get_conv_precision() == 3
-                and (len(xr) < 5 or xr[4] is None) and (len(dr) < 5 or dr[4] is None)
-                and _conv_wgrad_planes(x, dy, xr, dr, w_shape, stride, pad, dw, rowscale, dbias)):
-            return
+    f16 = F16X2 and x.dtype == torch.float32 and dy.dtype == torch.float32 and get_conv_precision() == 3
+    if f16 and WG_PLANES and _conv_wgrad_planes(x, dy, w_shape, stride, pad, dw, rowscale, dbias):
+        return
     # the shape half of the argument block and the split count depend on the shapes only: kept after the first call
     key = (x.shape, dy.shape, w_shape, stride, pad, x.dtype, dy.dtype)
     plan = _WPLAN.get(key)
     if plan is None:
-        a = ConvArgs()
-        a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = N, H, W, Cin, Cout, KH, KW
-        a.stride, a.pad, a.Ho, a.Wo = stride, pad, dy.shape[2], dy.shape[3]
-        a.out_stride = 1
+        a = _conv_shape(ConvArgs(), x.shape[0], x.shape[2], x.shape[3], Cin, Cout, KH, KW, stride, pad, dy.shape[2], dy.shape[3])
         a.io_bf16 = (IO_X if x.dtype == torch.bfloat16 else 0) | (IO_DY if dy.dtype == torch.bfloat16 else 0)
         a.x = x.data_ptr()
         splits = lib().mmt_conv_wgrad_splits(ctypes.byref(a))
         a.x = None
         if len(_WPLAN) > 4096:
             _WPLAN.clear()
-        _WPLAN[key] = (bytes(a), splits)
-    else:
-        a, splits = ConvArgs.from_buffer_copy(plan[0]), plan[1]
+        plan = _WPLAN[key] = (bytes(a), splits)
+    a, splits = ConvArgs.from_buffer_copy(plan[0]), plan[1]
     a.x = x.data_ptr()
-    if F16X2 and not a.io_bf16 and Cout % 4 == 0 and get_conv_precision() == 3:
-        ax, ad = getattr(x, "_mmt_amax", None), getattr(dy, "_mmt_amax", None)
-        big = N * H * W * Cin >= WGRAD_F16_MIN_ELEMS   # where 3 products instead of 6 pay for a reduction pass over an operand
-        if big and (ax is None or ax[1] != x._version):
-            ax = _amax_of(x)
-        if big and (ad is None or ad[1] != dy._version):
-            ad = _amax_of(dy)
-        if (ax is not None and ad is not None and ax[1] == x._version and ad[1] == dy._version
-                and _site_ok(("wgx", dw.data_ptr()), x) and _site_ok(("wgd", dw.data_ptr()), dy)):
-            # both operands carry their recorded maximum: two-term fp16 split (3 products instead of 6)
-            a.f16_x_amax, a.f16_dy_amax = ax[0].data_ptr(), ad[0].data_ptr()
-            a.f16_guard_x, a.f16_guard_dy = _guard(ax), _guard(ad)
-            F16_STATS["wgrad"] += 1
+    st = _wgrad_stats(x, dy, dw, True) if f16 and Cout % 4 == 0 else None
+    if st is not None:
+        # both operands carry their recorded maximum: two-term fp16 split
+        a.f16_x_amax, a.f16_dy_amax = st[0][0].data_ptr(), st[1][0].data_ptr()
+        a.f16_guard_x, a.f16_guard_dy = _guard(st[0]), _guard(st[1])
+        F16_STATS["wgrad"] += 1
     ws = torch.empty((splits * Cout * KH * KW * Cin,), dtype=torch.float32, device=x.device) if splits > 1 else None
     _TLS.last_ws = ws
-    if PROFILE is not None and PROFILE_ALL:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _check(lib().mmt_conv_wgrad(ctypes.byref(a), _p(dy), _p(rowscale), _p(dw), _p(dbias), _p(ws), _stream()), "mmt_conv_wgrad")
-        e1.record()
-        PROFILE.append((2.0 * N * a.Ho * a.Wo * Cout * Cin * KH * KW, e0, e1, ("wgrad", N, H, W, Cin, Cout, KH, stride, 1)))
-        return
+    e0 = _ev() if PROFILE is not None and PROFILE_ALL else None
     _check(lib().mmt_conv_wgrad(ctypes.byref(a), _p(dy), _p(rowscale), _p(dw), _p(dbias), _p(ws), _stream()), "mmt_conv_wgrad")
+    if e0 is not None:
+        _profiled(a, e0, "wgrad", splits, None, 0)
 
 
 # a batch of weight gradients as grouped launches (mmt_conv_wgrad_group): -0.5 ... -0.75 ms per step with every job cut into a quarter
@@ -2103,38 +2094,24 @@ def _wgrad_group_job(x, dy, w_shape, stride, pad, dw, rowscale, dbias, keep):
     if not (F16X2 and _PREC == 3 and x.dtype == torch.float32 and dy.dtype == torch.float32):
         return None
     Cout, Cin, KH, KW = w_shape
-    N, _, H, W = x.shape
     if Cout % 4 or Cin % 4:
         return None
-    ax, ad = getattr(x, "_mmt_amax", None), getattr(dy, "_mmt_amax", None)
-    big = N * H * W * Cin >= WGRAD_F16_MIN_ELEMS
-    if big and (ax is None or ax[1] != x._version):
-        ax = _amax_of(x)
-    if big and (ad is None or ad[1] != dy._version):
-        ad = _amax_of(dy)
-    if ax is None or ad is None or ax[1] != x._version or ad[1] != dy._version:
-        return None
-    if not (_site_ok(("wgx", dw.data_ptr()), x) and _site_ok(("wgd", dw.data_ptr()), dy)):
+    st = _wgrad_stats(x, dy, dw, True)
+    if st is None:
         return None
     j = WgradJob()
-    a = j.a
-    a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = N, H, W, Cin, Cout, KH, KW
-    a.stride, a.pad, a.Ho, a.Wo = stride, pad, dy.shape[2], dy.shape[3]
-    a.out_stride, a.mask_scale = 1, 1.0
+    a = _conv_shape(j.a, x.shape[0], x.shape[2], x.shape[3], Cin, Cout, KH, KW, stride, pad, dy.shape[2], dy.shape[3])
     a.x = x.data_ptr()
-    a.f16_x_amax, a.f16_dy_amax = ax[0].data_ptr(), ad[0].data_ptr()
-    a.f16_guard_x, a.f16_guard_dy = _guard(ax), _guard(ad)
+    a.f16_x_amax, a.f16_dy_amax = st[0][0].data_ptr(), st[1][0].data_ptr()
+    a.f16_guard_x, a.f16_guard_dy = _guard(st[0]), _guard(st[1])
     j.dy, j.rowscale, j.dw, j.dbias = dy.data_ptr(), _p(rowscale), dw.data_ptr(), _p(dbias)
-    xr, dr = getattr(x, "_mmt_rb", None), getattr(dy, "_mmt_rb", None)
-    if (WG_PLANES and xr is not None and dr is not None and xr[2] == x._version and dr[2] == dy._version
-            and (len(xr) < 5 or xr[4] is None) and (len(dr) < 5 or dr[4] is None)):
-        lag = (1 if len(xr) > 3 and xr[3] == "epi" else 0) | (2 if len(dr) > 3 and dr[3] == "epi" else 0)
-        if not (lag and (a.f16_guard_x is None or a.f16_guard_dy is None)):
-            a.x_planes_lag = lag
-            j.x_planes, j.x_plane_stride = xr[0].data_ptr(), xr[0].stride(0)
-            j.dy_planes, j.dy_plane_stride = dr[0].data_ptr(), dr[0].stride(0)
-            j.s_x, j.s_dy = xr[1].data_ptr(), dr[1].data_ptr()
-            keep.extend((xr[0], dr[0]))
+    pl = _wgrad_planes(x, dy, st) if WG_PLANES else None
+    if pl is not None:
+        xr, dr, a.x_planes_lag = pl
+        j.x_planes, j.x_plane_stride = xr[0].data_ptr(), xr[0].stride(0)
+        j.dy_planes, j.dy_plane_stride = dr[0].data_ptr(), dr[0].stride(0)
+        j.s_x, j.s_dy = xr[1].data_ptr(), dr[1].data_ptr()
+        keep.extend((xr[0], dr[0]))
     return j
 
 

@@ -233,9 +233,7 @@ def conv(x, w, b=None, stride=1, pad=0, relu=False, input_relu=False, out_rb=Fal
 def _carry_stats(src, view):
     """a reshaped view of a tensor keeps the statistics slot its producer recorded (same values, shared version counter)"""
     if view is not src:
-        am = getattr(src, "_mmt_amax", None)
-        if am is not None and am[1] == src._version:
-            view._mmt_amax = (am[0], view._version)
+        H.carry_stats(src, view)
 
 
 class LinearFn(torch.autograd.Function):
@@ -283,19 +281,10 @@ def linear(x, w, b=None, relu=False, input_relu=False, in_mask_scale=1.0, mul=No
 
 
 def batch_slice(t, lo, hi):
-    """images lo..hi of an NHWC-dense (N,C,H,W) tensor: a dense view; the bf16 planes a producer attached go along"""
+    """images lo..hi of an NHWC-dense (N,C,H,W) tensor: a dense view; what a producer attached goes along (_hip.carry: the statistics
+    of the whole batch, the slice of its bf16 planes and of its row-blocked fp16 planes [N H][C / 16][W][16])"""
     v = t[lo:hi]
-    pl = H.planes_of(t)
-    if pl is not None:
-        per = t.numel() // t.shape[0]
-        v._mmt_planes = (pl[:, lo * per:hi * per], v._version)
-    am = getattr(t, "_mmt_amax", None)
-    if am is not None and am[1] == t._version:
-        v._mmt_amax = (am[0], v._version)   # max over the whole batch: an upper bound for the slice (fp16 split scale)
-    rb = getattr(t, "_mmt_rb", None)      # row-blocked fp16 planes [N H][C / 16][W][16]: image-major, so a batch slice is a slice
-    if rb is not None and rb[2] == t._version and (len(rb) < 5 or rb[4] is None or hi <= rb[4]):
-        per = t.numel() // t.shape[0]   # (planes that cover only the leading images of the batch: slices inside them)
-        v._mmt_rb = (rb[0][:, lo * per:hi * per], rb[1], v._version) + tuple(rb[3:4]) + ((None,) if len(rb) > 4 else ())
+    H.carry(t, v, images=(lo, hi))
     return v
 
 
@@ -755,9 +744,7 @@ class _ForkAcc(object):
             self.seen.append(t)
         self.buf, self.fresh = t, fresh
         if not fresh:   # changed in place through raw pointers: what its producer recorded about it no longer holds
-            for a in ("_mmt_amax", "_mmt_rb", "_mmt_planes"):
-                if getattr(t, a, None) is not None:
-                    setattr(t, a, None)
+            H.drop(t)
         return first
 
 
@@ -810,15 +797,8 @@ def fork(x, n, rb_site=None):
     if acc is not None:
         for o in outs:
             o._mmt_acc = acc
-    rb = getattr(x, "_mmt_rb", None)
-    if rb is not None and rb[2] == x._version:
-        for o in outs:
-            o._mmt_rb = (rb[0], rb[1], o._version) + tuple(rb[3:])
-    for a in ("_mmt_planes", "_mmt_amax"):   # planes / statistics of the tensor go along with its aliases
-        v = getattr(x, a, None)
-        if v is not None and v[1] == x._version:
-            for o in outs:
-                setattr(o, a, (v[0], o._version))
+    for o in outs:   # planes / statistics of the tensor go along with its aliases
+        H.carry(x, o)
     return outs
 
 

@@ -81,9 +81,7 @@ def _pool_keep_stats(y):
     (its sampled mean is y's, i.e. lower than the pooled tensor's: the crest-factor test errs on the careful side) and
     layer1's first convolutions need no reduction pass over the 134 MB tensor."""
     p = H.maxpool3x3s2(y)
-    am = getattr(y, "_mmt_amax", None)
-    if am is not None and am[1] == y._version:
-        p._mmt_amax = (am[0], p._version)
+    H.carry_stats(y, p)
     return p
 
 
@@ -253,13 +251,8 @@ def forward_pair(backbone, xa, xb):
         pyr = list(fused.FPNFn.apply(*args, getattr(fpn, "out_planes", True), pre))
         for p_ in pyr:
             _stage_hook(body, "heads", p_)   # fires when the heads' backward has delivered this level's gradient
-        for p_, o_ in zip(pyr, pre[1]):  # the node's outputs are new tensor objects: the planes / statistics of the slices go along
-            pl = H.planes_of(o_)
-            if pl is not None:
-                p_._mmt_planes = (pl, p_._version)
-            am = getattr(o_, "_mmt_amax", None)
-            if am is not None and am[1] == o_._version:
-                p_._mmt_amax = (am[0], p_._version)
+        for p_, o_ in zip(pyr, pre[1]):  # the node's outputs are new tensor objects: the bf16 planes / statistics of the slices go along
+            H.carry(o_, p_, False)
         if fpn.top_blocks is not None:
             pyr.extend(fpn.top_blocks(pyr[-1]))
         res.append(tuple(pyr))
@@ -304,13 +297,12 @@ class FPN(nn.Module):
 class LastLevelMaxPool(nn.Module):
     def forward(self, x):
         y = x[:, :, ::2, ::2]  # max_pool2d(kernel 1, stride 2) == subsampling (fpn.py:72-74)
-        am = getattr(x, "_mmt_amax", None)
-        if am is not None and am[1] == x._version and x.is_cuda:
+        if x.is_cuda and H._recorded(x) is not None:
             # dense here (the copy its consumers would make anyway), with P5's statistics slot: the maximum of a subset is bounded
             # by it -- what the fp16 split's scale needs (no reduction pass over P6)
             y = y.contiguous(memory_format=torch.channels_last)
             H.record_torch(lambda src=x, dst=y: dst.copy_(src[:, :, ::2, ::2]))   # (a launch plan replays C-ABI calls: this copy too)
-            y._mmt_amax = (am[0], y._version)
+            H.carry_stats(x, y)
         return [y]
 
 

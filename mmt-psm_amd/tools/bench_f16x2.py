@@ -20,7 +20,8 @@ def f16x2(x, w, scale, shift, relu, pre=None):
     N, Cin, Hh, W = x.shape; Cout = w.shape[0]
     xp, sx = pre[0] if pre is not None else H.f16_split(x)
     wp, sw = pre[1] if pre is not None else H.f16_weight_planes(w)
-    a = H._conv_args(x, w, 1, 1, Hh, W)
+    a = H._conv_shape(H.ConvArgs(), N, Hh, W, Cin, Cout, w.shape[2], w.shape[3], 1, 1, Hh, W)
+    a.x, a.w = x.data_ptr(), w.data_ptr()
     y = H.empty_nhwc(N, Cout, Hh, W, x.device)
     a.y, a.scale, a.shift, a.relu = y.data_ptr(), H._p(scale), H._p(shift), 1 if relu else 0
     a.x_planes, a.x_plane_stride, a.w_planes, a.w_plane_stride = xp.data_ptr(), xp.stride(0), wp.data_ptr(), wp.stride(0)

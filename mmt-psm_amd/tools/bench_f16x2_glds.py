@@ -16,7 +16,8 @@ def timeit(f, it=30):
 def f16(x, w, sc, sh, stride, pad, relu, res, amax, wp, sw):
     N, Cin, Hh, W = x.shape; Cout, _, k, _ = w.shape
     Ho, Wo = (Hh + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    a = H._conv_args(x, w, stride, pad, Ho, Wo)
+    a = H._conv_shape(H.ConvArgs(), N, Hh, W, Cin, Cout, w.shape[2], w.shape[3], stride, pad, Ho, Wo)
+    a.x, a.w = x.data_ptr(), w.data_ptr()
     y = H.empty_nhwc(N, Cout, Ho, Wo, x.device)
     a.y, a.scale, a.shift, a.relu = y.data_ptr(), H._p(sc), H._p(sh), 1 if relu else 0
     if res is not None:

@@ -23,7 +23,8 @@ def timeit(f, it=10):
 def run(x, w, scale, shift, pre):
     N, Cin, Hh, W = x.shape; Cout = w.shape[0]
     (xp, sx), (wp, sw) = pre
-    a = H._conv_args(x, w, 1, 1, Hh, W)
+    a = H._conv_shape(H.ConvArgs(), N, Hh, W, Cin, Cout, w.shape[2], w.shape[3], 1, 1, Hh, W)
+    a.x, a.w = x.data_ptr(), w.data_ptr()
     y = H.empty_nhwc(N, Cout, Hh, W, x.device)
     a.y, a.scale, a.shift, a.relu = y.data_ptr(), H._p(scale), H._p(shift), 1
     a.x_planes, a.x_plane_stride, a.w_planes, a.w_plane_stride = xp.data_ptr(), xp.stride(0), wp.data_ptr(), wp.stride(0)
