@@ -658,6 +658,36 @@ int mmt_paste_mask_stack(const float* prob, const float* boxes /*[D,4]*/, int D,
 int mmt_polygon_targets(const float* poly_xy, const int32_t* poly_off, const int32_t* roi_poly, const float* boxes,
                         int P, int M, float* out, int32_t* overflow, void* stream);
 
+/* ---------------------------------------------------------------- mask work of the PAP evaluator (csrc/maskeval.hip)
+ * A mask on the device: 64-bit words over the run-length codec's COLUMN-major flattening -- bit k of the mask is pixel
+ * (y = k % H, x = k / H), ceil(H*W/64) words per mask, tail bits zero -- and one record of MMT_MASK_REC_INTS int32 per mask:
+ * [0] area, [1] xmin, [2] xmax, [3] ymin, [4] ymax, [5] wrap (some column x < W-1 has its bottom pixel and column x+1 its top
+ * pixel set: the run-based rleToBbox, pycoco/maskApi.c:135-151, then reports the full height), [6..7] zero.  An empty mask's
+ * record is all zero (box [0, 0, 0, 0]).  Integer arithmetic, no atomics.  Every entry point returns MMT_EINVAL for
+ * H*W >= 2^31, H or W <= 0, a negative count, more than 65535 masks, or a null pointer where an array is needed; a count of
+ * zero is a no-op.
+ *
+ * pack (pycoco/maskApi.c:21-34 rleEncode's scan, pycoco/_mask.pyx:144): masks uint8 [n][H][W] row-major as
+ * mmt_paste_mask_stack writes them, non-zero = set -> words [n][ceil(H*W/64)], rec [n][8]. */
+#define MMT_MASK_REC_INTS 8
+int mmt_mask_pack(const uint8_t* masks, int n, int H, int W, uint64_t* words, int32_t* rec, void* stream);
+/* expand from runs (pycoco/_mask.pyx:160 decode): ends = the concatenated INCLUSIVE PREFIX SUMS of every mask's run lengths
+ * (runs alternate 0 / 1 starting with zeros; the host parses the strings and checks that the last sum is H*W), mask i owns
+ * ends[off[i] .. off[i+1]) -> the same words and records.  Positions behind a mask's last sum stay zero. */
+int mmt_mask_expand(const int32_t* ends, const int64_t* off /*[n+1]*/, int n, int H, int W, uint64_t* words, int32_t* rec,
+                    void* stream);
+/* transitions (pycoco/maskApi.c:21-34): counts[i] = number of positions k in [0, H*W) with bit(k) != bit(k-1), bit(-1) = 0;
+ * then pos[off[i] .. off[i+1]) = those positions ascending (off = exclusive prefix sums of counts, formed by the host, which
+ * takes differences to get the run lengths). */
+int mmt_mask_transition_counts(const uint64_t* words, int n, int H, int W, int32_t* counts, void* stream);
+int mmt_mask_transition_positions(const uint64_t* words, int n, int H, int W, const int64_t* off /*[n+1]*/, int32_t* pos,
+                                  void* stream);
+/* pair intersections (pycoco/maskApi.c:239-260 rleIouInterUnion under pycoco/_mask.pyx:293-380 iouIntUni): inter [m][n] =
+ * popcount(D_d & G_g) where the two boxes overlap by iouIntUni's rule (min(x_d+w_d, x_g+w_g) - max(x_d, x_g) > 0, the same
+ * for y; boxes from the records), -1 where they do not.  Masks of one size; the host settles unequal sizes. */
+int mmt_mask_pair_intersections(const uint64_t* dwords, const int32_t* drec, int m, const uint64_t* gwords,
+                                const int32_t* grec, int n, int H, int W, int32_t* inter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,11 @@ _SIGS = {
     "mmt_paste_masks": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
     "mmt_paste_mask_stack": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
     "mmt_polygon_targets": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "mmt_mask_pack": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "mmt_mask_expand": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "mmt_mask_transition_counts": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "mmt_mask_transition_positions": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "mmt_mask_pair_intersections": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
 }
 
 _lib = None
@@ -2502,3 +2507,64 @@ def polygon_targets(poly_xy, poly_off, roi_poly, boxes, M):
     _check(lib().mmt_polygon_targets(_p(poly_xy), _p(poly_off), _p(roi_poly), _p(boxes), P, M, _p(out), _p(ovf), _stream()),
            "mmt_polygon_targets")
     return out, ovf
+
+
+# ---- mask work of the PAP evaluator (include/mmtpsm.h: mmt_mask_*; csrc/maskeval.hip).  A stack of masks on the device is
+# (words int64 [n, ceil(H*W/64)] -- the 64-bit words of the codec's column-major flattening --, records int32 [n, 8]).
+MASK_REC = 8   # MMT_MASK_REC_INTS
+
+
+def _mask_buffers(n, H, W, device):
+    if H <= 0 or W <= 0 or H * W >= (1 << 31):
+        raise RuntimeError("masks of %d x %d: 0 < H * W < 2^31 only" % (H, W))
+    return (torch.empty((n, (H * W + 63) // 64), dtype=torch.int64, device=device),
+            torch.empty((n, MASK_REC), dtype=torch.int32, device=device))
+
+
+def mask_pack(masks):
+    """masks uint8 (n, H, W), non-zero = set -> (words, records) (mmt_mask_pack)"""
+    masks = _dev(masks, "masks")
+    if masks.dtype != torch.uint8 or masks.dim() != 3:
+        raise RuntimeError("mask_pack: a uint8 (n, H, W) stack")
+    masks = masks.contiguous()
+    n, H, W = masks.shape
+    words, rec = _mask_buffers(n, H, W, masks.device)
+    _check(lib().mmt_mask_pack(_p(masks), n, H, W, _p(words), _p(rec), _stream()), "mmt_mask_pack")
+    return words, rec
+
+
+def mask_expand(ends, off, H, W):
+    """ends int32: the concatenated inclusive prefix sums of every mask's run lengths, off int64 (n + 1) -> (words, records)
+    (mmt_mask_expand)"""
+    ends, off = _dev(ends, "ends"), _dev(off, "off")
+    if ends.dtype != torch.int32 or off.dtype != torch.int64 or off.numel() < 1:
+        raise RuntimeError("mask_expand: int32 prefix sums and int64 offsets")
+    n = off.numel() - 1
+    words, rec = _mask_buffers(n, H, W, ends.device)
+    _check(lib().mmt_mask_expand(_p(ends.contiguous()), _p(off.contiguous()), n, H, W, _p(words), _p(rec), _stream()), "mmt_mask_expand")
+    return words, rec
+
+
+def mask_transitions(words, H, W):
+    """-> (counts int64 (n,) on the HOST, positions int32 on the HOST, concatenated mask after mask): where bit(k) != bit(k - 1)
+    in each mask, ascending (mmt_mask_transition_counts / _positions).  The only data that crosses to the host."""
+    words = _dev(words, "words")
+    n = words.shape[0]
+    counts = torch.empty((n,), dtype=torch.int32, device=words.device)
+    _check(lib().mmt_mask_transition_counts(_p(words), n, H, W, _p(counts), _stream()), "mmt_mask_transition_counts")
+    counts = counts.cpu().to(torch.int64)
+    off = torch.zeros((n + 1,), dtype=torch.int64)
+    torch.cumsum(counts, 0, out=off[1:])
+    pos = torch.empty((max(int(off[-1]), 1),), dtype=torch.int32, device=words.device)
+    off_d = off.to(words.device)
+    _check(lib().mmt_mask_transition_positions(_p(words), n, H, W, _p(off_d), _p(pos), _stream()), "mmt_mask_transition_positions")
+    return counts, pos[:int(off[-1])].cpu()
+
+
+def mask_pair_intersections(dwords, drec, gwords, grec, H, W):
+    """-> int32 (m, n) on the device: popcount(D_d & G_g), -1 where the two boxes do not overlap (mmt_mask_pair_intersections)"""
+    m, n = _dev(dwords, "dwords").shape[0], _dev(gwords, "gwords").shape[0]
+    out = torch.empty((m, n), dtype=torch.int32, device=dwords.device)
+    _check(lib().mmt_mask_pair_intersections(_p(dwords), _p(drec), m, _p(gwords), _p(grec), n, H, W, _p(out), _stream()),
+           "mmt_mask_pair_intersections")
+    return out

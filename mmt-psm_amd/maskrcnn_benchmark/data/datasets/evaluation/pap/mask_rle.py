@@ -5,7 +5,12 @@
 An RLE is COCO's: {"size": [h, w], "counts": ...} over the mask flattened COLUMN-major, runs alternating 0 / 1 starting with
 zeros; `counts` is the compressed ASCII string (bytes or str) or a plain list of run lengths (COCO's "uncompressed" form).
 Host code: evaluation runs once per checkpoint on a few hundred windows ("irrelevant to the throughput
-metric")."""
+metric").
+
+Opt-in device path (`encode_device`, `iouIntUni(..., on_device=True)`): the dense mask work -- finding the runs of a pasted
+mask, decoding every string for every (window, category), the pair intersections -- runs in the HIP kernels of
+csrc/maskeval.hip (include/mmtpsm.h: mmt_mask_*); the host keeps the strings.  Same strings byte for byte, same integers.
+It has no fallback: without a GPU or the library it raises."""
 import numpy as np
 
 
@@ -119,15 +124,137 @@ def _bbox(m):
     return float(xs.min()), float(y0), float(xs.max() - xs.min() + 1), float(y1 - y0 + 1)
 
 
-def iouIntUni(dt, gt, iscrowd):
+def _backend():
+    """the HIP binding, or RuntimeError: the device path has no host fallback"""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("on_device=True: the mask kernels (csrc/maskeval.hip) need the MI355X; no GPU visible")
+    from maskrcnn_benchmark import _hip
+    _hip.lib()
+    return _hip
+
+
+def _runs_of_positions(pos, n):
+    """ascending positions k in [0, n) where bit(k) != bit(k - 1), bit(-1) = 0 -> run lengths as `_runs` gives them: a leading
+    position 0 is the zero-length first run of a mask that starts with a set pixel, no position at all is [n]"""
+    if n == 0:
+        return [0]
+    pos = np.asarray(pos, dtype=np.int64)
+    return np.diff(np.concatenate(([0], pos, [n]))).tolist()
+
+
+def encode_device(masks):
+    """uint8 GPU tensor (n, H, W) or (n, 1, H, W), non-zero = set -> [encode(m) for m in masks.cpu().numpy()] with the runs
+    found on the device (mmt_mask_pack + mmt_mask_transition_*): only the transition counts and positions cross to the host"""
+    H = _backend()
+    if masks.dim() == 4 and masks.shape[1] == 1:
+        masks = masks[:, 0]
+    if masks.dim() != 3:
+        raise RuntimeError("encode_device: (n, H, W) or (n, 1, H, W) masks")
+    n, h, w = (int(v) for v in masks.shape)
+    if n == 0:
+        return []
+    if h * w == 0:
+        return [{"size": [h, w], "counts": _to_string([0]).encode("ascii")} for _ in range(n)]
+    words, _ = H.mask_pack(masks)
+    counts, pos = H.mask_transitions(words, h, w)
+    pos, out, at = pos.numpy(), [], 0
+    for c in counts.tolist():
+        out.append({"size": [h, w], "counts": _to_string(_runs_of_positions(pos[at:at + c], h * w)).encode("ascii")})
+        at += c
+    return out
+
+
+def _expand_device(H, rles, device):
+    """RLEs of ONE size -> (words, records on the host) (mmt_mask_expand): the host parses the strings and hands over the prefix
+    sums of the runs"""
+    import torch
+    h, w = (int(v) for v in rles[0]["size"])
+    ends, off = [], [0]
+    for r in rles:
+        e = np.cumsum(np.asarray(counts_of(r), dtype=np.int64))
+        if e.shape[0] == 0 or e[-1] != h * w or (np.diff(e) < 0).any() or e[0] < 0:
+            raise ValueError("RLE does not cover its %d x %d mask" % (h, w))
+        ends.append(e.astype(np.int32))
+        off.append(off[-1] + e.shape[0])
+    ends = torch.from_numpy(np.concatenate(ends)).to(device)
+    off = torch.tensor(off, dtype=torch.int64).to(device)
+    words, rec = H.mask_expand(ends, off, h, w)
+    return words, rec.cpu().numpy().astype(np.int64)
+
+
+def _box_of_record(r, h):
+    """`_bbox` from a device record (area, xmin, xmax, ymin, ymax, wrap)"""
+    if r[0] == 0:
+        return 0, 0, 0, 0
+    return (r[1], 0, r[2] - r[1] + 1, h) if r[5] else (r[1], r[3], r[2] - r[1] + 1, r[4] - r[3] + 1)
+
+
+def _iouIntUni_device(dt, gt, iscrowd):
+    import torch
+    H = _backend()
+    m, n = len(dt), len(gt)
+    device = torch.device("cuda", torch.cuda.current_device())
+    groups = {}   # size -> ([detection indices], [ground-truth indices])
+    for side, lst in enumerate((dt, gt)):
+        for i, r in enumerate(lst):
+            groups.setdefault(tuple(int(v) for v in r["size"]), ([], []))[side].append(i)
+    if any(h * w == 0 for h, w in groups):
+        raise RuntimeError("on_device=True: masks without pixels")
+    inter = np.full((m, n), -1, dtype=np.int64)          # -1: boxes disjoint
+    other = np.zeros((m, n), dtype=bool)                 # sizes differ
+    area_d, box_d, box_g = np.zeros(m, np.int64), [None] * m, [None] * n
+    area_g = np.zeros(n, np.int64)
+    for (h, w), (di, gi) in groups.items():
+        dw = gw = None
+        if di:
+            dw, drec = _expand_device(H, [dt[i] for i in di], device)
+            area_d[di] = drec[:, 0]
+            for i, r in zip(di, drec):
+                box_d[i] = _box_of_record(r, h)
+        if gi:
+            gw, grec = _expand_device(H, [gt[i] for i in gi], device)
+            area_g[gi] = grec[:, 0]
+            for i, r in zip(gi, grec):
+                box_g[i] = _box_of_record(r, h)
+        if di and gi:
+            dr = torch.from_numpy(drec.astype(np.int32)).to(device)
+            gr = torch.from_numpy(grec.astype(np.int32)).to(device)
+            inter[np.ix_(di, gi)] = H.mask_pair_intersections(dw, dr, gw, gr, h, w).cpu().numpy()
+    if len(groups) > 1:   # pairs of unequal sizes: -1 where the boxes overlap, settled here before (and without) any launch for them
+        for d in range(m):
+            for g in range(n):
+                if tuple(dt[d]["size"]) != tuple(gt[g]["size"]):
+                    bd, bg = box_d[d], box_g[g]
+                    ow = min(bd[0] + bd[2], bg[0] + bg[2]) - max(bd[0], bg[0])
+                    oh = min(bd[1] + bd[3], bg[1] + bg[3]) - max(bd[1], bg[1])
+                    other[d, g] = ow > 0 and oh > 0
+    hit = (inter >= 0) & ~other
+    i = np.where(hit, inter, 0)
+    u = area_d[:, None] + area_g[None, :] - i
+    if iscrowd is not None:
+        crowd = np.array([bool(c) for c in iscrowd], dtype=bool)
+        u = np.where(crowd[None, :], area_d[:, None], u)
+    u = np.where(i == 0, 1, u)
+    iou = np.where(hit, i / u, 0.0)
+    iou[other] = -1
+    return iou, np.where(hit, i, 0).astype(np.float64), np.where(hit, u, 0).astype(np.float64)
+
+
+def iouIntUni(dt, gt, iscrowd, on_device=False):
     """(iou, intersection, union), each (len(dt), len(gt)) float64 -- the fork's addition to pycocotools (`_mask.pyx:293-380`,
     `maskApi.c:239-260`): pairs whose bounding boxes overlap get i = |d & g| and u = |d | g| (crowd gt: u = |d|) with the C
     code's `i == 0 -> u = 1`; a pair of different mask sizes gets iou -1.  Pairs whose boxes do not overlap have iou 0 and
     -- where the C code leaves its malloc'ed intersection / union cells unwritten -- intersection 0, union 0 here.
-    [] when either list is empty."""
+    [] when either list is empty.  on_device=True: the same three matrices from the expand and pair kernels of csrc/maskeval.hip
+    (RuntimeError without a GPU or the library)."""
     m, n = len(dt), len(gt)
+    if on_device:
+        _backend()
     if m == 0 or n == 0:
         return []
+    if on_device:
+        return _iouIntUni_device(dt, gt, iscrowd)
     D = [decode(r).astype(bool) for r in dt]
     G = [decode(r).astype(bool) for r in gt]
     bd, bg = [_bbox(x) for x in D], [_bbox(x) for x in G]

@@ -14,7 +14,12 @@ metric" -- restated with the reference's outputs, including the behaviour that o
   * mAP / AP50 / AP75 / AP85 (cal_MAP :480-510, accumulate :706-797): COCO matching at IoU 0.5:0.05:0.95 and the 101-point
     interpolated precision, no area ranges, no crowd / ignore flags.
 Detections and ground truths are dicts {"image_id": {"file_name", "location": (x, y), "id"}, "category_id", "segmentation":
-RLE, "score"}; a window's key is file_name_x_y (:222-225)."""
+RLE, "score"}; a window's key is file_name_x_y (:222-225).
+
+`on_device=True` (opt-in, off by default) moves the dense mask work -- run-length encoding of the pasted masks, the
+intersections behind `iouIntUni` -- into the kernels of csrc/maskeval.hip through `mask_rle.encode_device` and
+`mask_rle.iouIntUni(..., on_device=True)`: the same strings and integers, so every statistic is equal; the metric code below
+is the same either way."""
 import copy
 import os
 import tempfile
@@ -51,8 +56,8 @@ PR_THRESHOLDS = np.linspace(0.2, 0.9, 28)
 
 
 class Papeval(object):
-    def __init__(self, gts, dts, iou_type):
-        self.iou_type = iou_type
+    def __init__(self, gts, dts, iou_type, on_device=False):
+        self.iou_type, self.on_device = iou_type, bool(on_device)
         self.PapGt, self.PapDt = gts, dts
         self.params = Params(iouType=iou_type)
         self._gts, self._dts = defaultdict(list), defaultdict(list)
@@ -107,7 +112,7 @@ class Papeval(object):
         g = [x["segmentation"] for x in gt]
         d = [x["segmentation"] for x in dt]
         gt_area = maskUtils.area(g) if len(g) else None
-        res = maskUtils.iouIntUni(d, g, [0] * len(g))
+        res = maskUtils.iouIntUni(d, g, [0] * len(g), on_device=self.on_device)
         if len(d) == 0 or len(g) == 0:
             merged = maskUtils.merge(copy.deepcopy(d if len(d) else g), intersect=False)
             return [], [], [maskUtils.area(merged)], gt_area, []
@@ -335,24 +340,28 @@ class PapResults(object):
         return repr(self.results)
 
 
-def evaluate_predictions_on_pap(pap_gts, pap_results, json_result_file=None, iou_type="segm"):
+def evaluate_predictions_on_pap(pap_gts, pap_results, json_result_file=None, iou_type="segm", on_device=False):
     """pap_eval.py:189-203"""
     if json_result_file:
         import json
         with open(json_result_file, "w") as f:
             json.dump(pap_results, f)
-    ev = Papeval(pap_gts, pap_results, iou_type)
+    ev = Papeval(pap_gts, pap_results, iou_type, on_device=on_device)
     ev.evaluate()
     ev.accumulate()
     ev.summarize()
     return ev
 
 
-def prepare_for_pap_segmentation(predictions, dataset):
+def prepare_for_pap_segmentation(predictions, dataset, on_device=False):
     """predictions {image index: BoxList with 'mask', 'scores', 'labels'} + the dataset's ground truth -> the evaluator's dict
     lists (pap_eval.py:79-143).  Masks that are not window-sized yet -- the M x M probabilities of MaskPostProcessor, as in a
     predictions.pth -- are pasted first, as the reference does (pap_eval.py:107-109: Masker(threshold=0.5, padding=1)); the
-    paste is the device kernel `mmt_paste_mask_stack`, so that case needs the GPU (no host implementation: it raises)."""
+    paste is the device kernel `mmt_paste_mask_stack`, so that case needs the GPU (no host implementation: it raises).
+    on_device=True: the masks, pasted or not, stay on (or go to) the GPU and are encoded by `mask_rle.encode_device`; only the
+    positions of their run boundaries come back.  It raises without a GPU."""
+    if on_device:
+        maskUtils._backend()
     masker = None
     gts, dts = [], []
     for image_id, prediction in predictions.items():
@@ -374,27 +383,32 @@ def prepare_for_pap_segmentation(predictions, dataset):
                 from maskrcnn_benchmark.modeling.roi_heads.mask_head.mask_head import Masker
                 masker = Masker(threshold=0.5, padding=1)
             dev = torch.device("cuda", torch.cuda.current_device())
-            masks = masker.forward_single_image(masks.to(dev), prediction.to(dev)).cpu()
+            masks = masker.forward_single_image(masks.to(dev), prediction.to(dev))
+            if not on_device:
+                masks = masks.cpu()
         scores = prediction.get_field("scores").tolist()
         labels = [dataset.contiguous_category_id_to_json_id[i] for i in prediction.get_field("labels").tolist()]
         boxes = prediction.bbox.tolist()
+        if on_device:
+            masks = torch.as_tensor(masks).to(torch.device("cuda", torch.cuda.current_device()))
+            rles = maskUtils.encode_device(masks.to(torch.uint8))   # (the host path's np.asarray(..., dtype=np.uint8))
         for k, m in enumerate(masks):
-            rle = maskUtils.encode(np.asarray(m[0].cpu() if hasattr(m, "cpu") else m[0], dtype=np.uint8))
+            rle = rles[k] if on_device else maskUtils.encode(np.asarray(m[0].cpu() if hasattr(m, "cpu") else m[0], dtype=np.uint8))
             rle["counts"] = rle["counts"].decode("utf-8")
             dts.append({"image_id": original_id, "category_id": labels[k], "segmentation": rle, "score": scores[k], "bbox": boxes[k]})
     return gts, dts
 
 
-def do_pap_evaluation(dataset, predictions, output_folder, iou_types, logger, visual_num=0):
+def do_pap_evaluation(dataset, predictions, output_folder, iou_types, logger, visual_num=0, on_device=False):
     """pap_eval.py:20-47 (the visualisation of :49-77 is out of scope)"""
     logger.info("Preparing results for Pap format")
-    pap_gts, pap_results = prepare_for_pap_segmentation(predictions, dataset)
+    pap_gts, pap_results = prepare_for_pap_segmentation(predictions, dataset, on_device=on_device)
     results = PapResults(*iou_types)
     logger.info("Evaluating predictions")
     for iou_type in iou_types:
         with tempfile.NamedTemporaryFile() as f:
             path = os.path.join(output_folder, iou_type + ".json") if output_folder else f.name
-            results.update(evaluate_predictions_on_pap(pap_gts, pap_results, path, iou_type))
+            results.update(evaluate_predictions_on_pap(pap_gts, pap_results, path, iou_type, on_device=on_device))
     logger.info(results)
     if output_folder:
         torch.save(results, os.path.join(output_folder, "pap_results.pth"))

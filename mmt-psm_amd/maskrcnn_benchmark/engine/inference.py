@@ -9,6 +9,7 @@ PAP evaluator reads, and otherwise returns the predictions (the dataset classes 
 on purpose: a failing batch raises instead of being skipped by a bare `except: continue` (:39-40), and predictions of
 other ranks travel through `torch.distributed.all_gather_object` instead of a temporary directory (utils/comm.py:81-147)."""
 import datetime
+import inspect
 import logging
 import os
 import time
@@ -57,8 +58,19 @@ def _accumulate_predictions_from_multiple_gpus(predictions_per_gpu):
     return predictions
 
 
+def _accepts(fn, name):
+    try:
+        ps = inspect.signature(fn).parameters
+    except (TypeError, ValueError):
+        return False
+    return name in ps or any(p.kind is p.VAR_KEYWORD for p in ps.values())
+
+
 def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=False, device="cuda", expected_results=(),
-              expected_results_sigma_tol=4, output_folder=None, generate_data=False, visual_num=0, evaluator=None):
+              expected_results_sigma_tol=4, output_folder=None, generate_data=False, visual_num=0, evaluator=None,
+              eval_on_device=False):
+    """eval_on_device: handed on as `on_device` to the evaluator (the PAP evaluator then scores masks with the kernels of
+    csrc/maskeval.hip); an evaluator that does not take it cannot honour it: that raises, nothing falls back"""
     device = torch.device(device)
     logger = logging.getLogger("maskrcnn_benchmark.inference")
     dataset = getattr(data_loader, "dataset", None)
@@ -82,9 +94,15 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
     if evaluate is None and dataset is not None:
         from maskrcnn_benchmark.data.datasets import evaluation as _ev
         if all(hasattr(dataset, a) for a in ("id_to_img_map", "get_ground_truth", "contiguous_category_id_to_json_id", "maxWS")):
-            return _ev.evaluate(dataset, predictions, output_folder, box_only=box_only, iou_types=iou_types, visual_num=visual_num)
+            return _ev.evaluate(dataset, predictions, output_folder, box_only=box_only, iou_types=iou_types, visual_num=visual_num,
+                                on_device=eval_on_device)
     if evaluate is None:
         return predictions
+    extra = {}
+    if eval_on_device:
+        if not _accepts(evaluate, "on_device"):
+            raise RuntimeError("eval_on_device=True, but the evaluator takes no `on_device`; there is no fallback path")
+        extra["on_device"] = True
     return evaluate(predictions=predictions, output_folder=output_folder, box_only=box_only, iou_types=iou_types,
                     expected_results=expected_results, expected_results_sigma_tol=expected_results_sigma_tol,
-                    visual_num=visual_num)
+                    visual_num=visual_num, **extra)
