@@ -653,8 +653,9 @@ int mmt_paste_mask_stack(const float* prob, const float* boxes /*[D,4]*/, int D,
  *   poly_xy   float32 concatenated vertices (x,y interleaved) of all polygons
  *   poly_off  int32 [NP+1] vertex offsets of each polygon
  *   roi_poly  int32 [P,2]: polygons roi_poly[p][0]..roi_poly[p][1]-1 belong to ROI p (its matched instance)
- *   boxes     [P,4] proposals;  out [P,M,M] float {0,1};  overflow int32[1] set if a ROI exceeded the
- *   crossing-list capacity (never for 28x28 targets of sane polygons) */
+ *   boxes     [P,4] proposals;  out [P,M,M] float {0,1};  1 <= M <= 32 (else MMT_EINVAL).
+ *   overflow  int32[1], always written 0: the crossing list is filled in passes of 64 edges x at most M crossings each and
+ *   cannot fill, whatever the polygon; the argument stays for callers built against the capped list (it may be null) */
 int mmt_polygon_targets(const float* poly_xy, const int32_t* poly_off, const int32_t* roi_poly, const float* boxes,
                         int P, int M, float* out, int32_t* overflow, void* stream);
 

@@ -96,15 +96,23 @@ extern "C" int mmt_paste_mask_stack(const float* prob, const float* boxes, int D
 //   mask[q] = (#{j : a_j <= q}) mod 2     (q = column-major pixel index)
 // so the sort + run-length stage is replaced by a parity count over an (unsorted) crossing list kept
 // in LDS.  One wave per ROI; lanes own polygon edges for the boundary walk and pixels for the fill.
-#define POLY_CAP 1536
+//
+// The list cannot fill.  Parity adds over any partition of the edges, so a polygon's edges are walked in passes of
+// POLY_PASS = 64, one edge per lane, and every pass XORs its own parities into the polygon's.  Along one edge the walk's
+// column u never turns back, and a crossing is recorded only where u steps over the centre of one of the M pixel
+// columns: at most M per edge, 64 * M per pass -- 8 KB at the largest M the entry point takes (32).
+#define POLY_PASS 64
+#define POLY_MAX_M 32   // M * M <= 16 pixels per lane x 64 lanes
 
 __global__ __launch_bounds__(64) void polygon_kernel(const float* __restrict__ xy, const int* __restrict__ poly_off,
                                                      const int* __restrict__ roi_poly, const float* __restrict__ boxes,
                                                      int M, float* __restrict__ out, int* __restrict__ overflow) {
-  __shared__ unsigned cross[POLY_CAP];
+  __shared__ unsigned cross[POLY_PASS * POLY_MAX_M];
   __shared__ int ncross;
   const int p = blockIdx.x, lane = threadIdx.x;
   const int h = M, w = M;
+  const int cap = POLY_PASS * M;
+  if (p == 0 && lane == 0 && overflow) *overflow = 0;   // kept in the ABI; nothing can overflow
   // crop + resize of structures/segmentation_mask.py:96-120 in float32, ratio cast like `tensor * python_float`
   const float b0 = boxes[p * 4 + 0], b1 = boxes[p * 4 + 1], b2 = boxes[p * 4 + 2], b3 = boxes[p * 4 + 3];
   float bw = b2 - b0, bh = b3 - b1;
@@ -112,72 +120,72 @@ __global__ __launch_bounds__(64) void polygon_kernel(const float* __restrict__ x
   if (!(bh >= 1.f)) bh = 1.f;
   const float rw = (float)((double)M / (double)bw), rh = (float)((double)M / (double)bh);
   const int npix = h * w;
-  // per-pixel accumulated mask (union over polygons): each lane owns pixels lane, lane+64, ...
-  unsigned char acc[16];  // ceil(28*28/64)=13
-  const int per = (npix + 63) / 64;
-  for (int i = 0; i < per; i++) acc[i] = 0;
+  // accumulated mask (union over polygons): bit i of a lane is pixel q = lane + 64 * i (column-major), i < 16
+  unsigned acc = 0;
 
   for (int pi = roi_poly[2 * p]; pi < roi_poly[2 * p + 1]; pi++) {
     const int v0 = poly_off[pi], k = poly_off[pi + 1] - v0;
-    if (lane == 0) ncross = 0;
-    __syncthreads();
+    unsigned par = 0;   // this polygon's parities, pass by pass
     const double scale = 5;
-    for (int j = lane; j < k; j += 64) {
-      const int j1 = (j + 1 == k) ? 0 : j + 1;
-      const float fxs = (xy[(v0 + j) * 2 + 0] - b0) * rw, fys = (xy[(v0 + j) * 2 + 1] - b1) * rh;
-      const float fxe = (xy[(v0 + j1) * 2 + 0] - b0) * rw, fye = (xy[(v0 + j1) * 2 + 1] - b1) * rh;
-      int xs = (int)(scale * (double)fxs + .5), ys = (int)(scale * (double)fys + .5);
-      int xe = (int)(scale * (double)fxe + .5), ye = (int)(scale * (double)fye + .5);
-      const int dx = abs(xe - xs), dy = abs(ys - ye);
-      const bool flip = (dx >= dy && xs > xe) || (dx < dy && ys > ye);
-      if (flip) { int t = xs; xs = xe; xe = t; t = ys; ys = ye; ye = t; }
-      const double s = dx >= dy ? (double)(ye - ys) / dx : (double)(xe - xs) / dy;
-      const int n = (dx >= dy ? dx : dy);
-      int pu = 0, pv = 0;
-      for (int d = 0; d <= n; d++) {
-        const int t = flip ? n - d : d;
-        int u, v;
-        if (dx >= dy) { u = t + xs; v = (int)(ys + s * t + .5); }
-        else { v = t + ys; u = (int)(xs + s * t + .5); }
-        if (d > 0 && u != pu) {
-          double xd = (double)(u < pu ? u : u - 1);
-          xd = (xd + .5) / scale - .5;
-          if (!(floor(xd) != xd || xd < 0 || xd > w - 1)) {
-            double yd = (double)(v < pv ? v : pv);
-            yd = (yd + .5) / scale - .5;
-            if (yd < 0) yd = 0; else if (yd > h) yd = h;
-            yd = ceil(yd);
-            const int slot = atomicAdd(&ncross, 1);
-            if (slot < POLY_CAP) cross[slot] = (unsigned)((int)xd * h + (int)yd);
+    for (int j0 = 0; j0 < k; j0 += POLY_PASS) {
+      if (lane == 0) ncross = 0;
+      __syncthreads();
+      const int j = j0 + lane;
+      if (j < k) {
+        const int j1 = (j + 1 == k) ? 0 : j + 1;
+        const float fxs = (xy[(v0 + j) * 2 + 0] - b0) * rw, fys = (xy[(v0 + j) * 2 + 1] - b1) * rh;
+        const float fxe = (xy[(v0 + j1) * 2 + 0] - b0) * rw, fye = (xy[(v0 + j1) * 2 + 1] - b1) * rh;
+        int xs = (int)(scale * (double)fxs + .5), ys = (int)(scale * (double)fys + .5);
+        int xe = (int)(scale * (double)fxe + .5), ye = (int)(scale * (double)fye + .5);
+        const int dx = abs(xe - xs), dy = abs(ys - ye);
+        const bool flip = (dx >= dy && xs > xe) || (dx < dy && ys > ye);
+        if (flip) { int t = xs; xs = xe; xe = t; t = ys; ys = ye; ye = t; }
+        const double s = dx >= dy ? (double)(ye - ys) / dx : (double)(xe - xs) / dy;
+        const int n = (dx >= dy ? dx : dy);
+        int pu = 0, pv = 0;
+        for (int d = 0; d <= n; d++) {
+          const int t = flip ? n - d : d;
+          int u, v;
+          if (dx >= dy) { u = t + xs; v = (int)(ys + s * t + .5); }
+          else { v = t + ys; u = (int)(xs + s * t + .5); }
+          if (d > 0 && u != pu) {
+            double xd = (double)(u < pu ? u : u - 1);
+            xd = (xd + .5) / scale - .5;
+            if (!(floor(xd) != xd || xd < 0 || xd > w - 1)) {
+              double yd = (double)(v < pv ? v : pv);
+              yd = (yd + .5) / scale - .5;
+              if (yd < 0) yd = 0; else if (yd > h) yd = h;
+              yd = ceil(yd);
+              const int slot = atomicAdd(&ncross, 1);
+              if (slot < cap) cross[slot] = (unsigned)((int)xd * h + (int)yd);   // (always: see above)
+            }
           }
+          pu = u; pv = v;
         }
-        pu = u; pv = v;
       }
+      __syncthreads();
+      const int nc = min(ncross, cap);
+      for (int c = 0; c < nc; c++) {
+        const unsigned a = cross[c];
+#pragma unroll
+        for (int i = 0; i < 16; i++) par ^= (a <= (unsigned)(lane + 64 * i) ? 1u : 0u) << i;
+      }
+      __syncthreads();
     }
-    __syncthreads();
-    int nc = ncross;
-    if (nc > POLY_CAP) { if (lane == 0) atomicExch(overflow, 1); nc = POLY_CAP; }
-    for (int i = 0; i < per; i++) {
-      const int q = lane + 64 * i;  // column-major index q = x*h + y
-      if (q >= npix) break;
-      unsigned cnt = 0;
-      for (int j = 0; j < nc; j++) cnt += (cross[j] <= (unsigned)q) ? 1u : 0u;
-      acc[i] |= (unsigned char)(cnt & 1u);
-    }
-    __syncthreads();
+    acc |= par;
   }
-  for (int i = 0; i < per; i++) {
+  for (int i = 0; i < 16; i++) {
     const int q = lane + 64 * i;
     if (q >= npix) break;
     const int x = q / h, y = q - x * h;
-    out[((long)p * h + y) * w + x] = acc[i] ? 1.f : 0.f;
+    out[((long)p * h + y) * w + x] = ((acc >> i) & 1u) ? 1.f : 0.f;
   }
 }
 
 extern "C" int mmt_polygon_targets(const float* poly_xy, const int32_t* poly_off, const int32_t* roi_poly,
                                    const float* boxes, int P, int M, float* out, int32_t* overflow, void* stream) {
   if (P <= 0) return 0;
-  if (M * M > 16 * 64) return MMT_EINVAL;
+  if (M < 1 || M > POLY_MAX_M) return MMT_EINVAL;
   hipLaunchKernelGGL(polygon_kernel, dim3(P), dim3(64), 0, (hipStream_t)stream, poly_xy, poly_off, roi_poly, boxes, M,
                      out, overflow);
   MMT_LAUNCH_CHECK();

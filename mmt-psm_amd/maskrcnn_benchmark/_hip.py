@@ -2335,6 +2335,9 @@ def mask_bce(logits, labels, targets, grad_scale=1.0):
 
 
 def _teachers(ts, flips):
+    if not 1 <= len(ts) <= MGD_MAX_TEACHERS or len(flips) != len(ts):
+        raise RuntimeError("MGD: %d teacher views with %d flips; the kernels take 1 to %d views, one flip each"
+                           % (len(ts), len(flips), MGD_MAX_TEACHERS))
     T = MgdTeachers()
     T.nt = len(ts)
     for i, (t, f) in enumerate(zip(ts, flips)):
