@@ -571,6 +571,21 @@ int mmt_gconv3x3_dgrad(const float* dy, const float* w, const float* scale, cons
 int mmt_gconv3x3_wgrad(const float* x, const float* dy, const float* rowscale, float* dw, int N, int H, int W, int C, int Cg,
                        int stride, void* stream);
 
+/* ---------------------------------------------------------------- backward of the stem (csrc/stem_bwd.hip), FREEZE_CONV_BODY_AT 0
+ * mmt_maxpool3x3s2_backward: gradient of mmt_maxpool3x3s2 with the ReLU mask of the pooled tensor's producer fused in.  NHWC fp32:
+ * y [N][H][W][C] (the pool's input, a ReLU output), g [N][Ho][Wo][C] with Ho = (H - 1) / 2 + 1, dy [N][H][W][C]:
+ *   dy[n,h,w,c] = (y[n,h,w,c] > 0) * sum g[n,ho,wo,c] over the windows (ho, wo) that contain (h, w) and whose FIRST maximum in
+ *   (kh, kw) scan order lies at (h, w) (ATen's max_pool2d rule; taps outside the image never win).
+ * Gather form: every element of dy is written by its one owner, zeros included; the (at most four) addends of an element are summed
+ * in ascending (ho, wo) order.  Any H, W >= 1, C % 4 == 0, else MMT_EINVAL.
+ * mmt_stem_wgrad: weight gradient of the 7x7 / stride 2 / pad 3, 3 -> 64 stem convolution from the image itself:
+ *   dw[co][kh][kw][ci] += rowscale[co] * sum_{n,ho,wo} dy[n,ho,wo,co] * x[n, ci, 2 ho - 3 + kh, 2 wo - 3 + kw]
+ * x [N][3][H][W] fp32 NCHW (any H, W >= 1), dy [N][Ho][Wo][64] NHWC with Ho = (H - 1) / 2 + 1, dw [64][7][7][3] (the parameter's
+ * channels-last memory), rowscale [64] or NULL.  Exact fp32 products on the fp32-input MFMA; pixel ranges across blocks, summed
+ * into dw with fp32 atomics like mmt_conv_wgrad's split form. */
+int mmt_maxpool3x3s2_backward(const float* y, const float* g, float* dy, int N, int H, int W, int C, void* stream);
+int mmt_stem_wgrad(const float* x, const float* dy, const float* rowscale, float* dw, int N, int H, int W, void* stream);
+
 /* ---------------------------------------------------------------- losses (forward value + gradient in one launch)
  * mask-logit BCE (mask_head/loss.py:177-179): logits [P,28*28,NC] NHWC, labels int32 [P], targets [P,28*28] {0,1};
  * loss (1 float, accumulated; zero it first) = mean BCEWithLogits(logits[p,:,label_p], target); grad [P,28*28,NC]

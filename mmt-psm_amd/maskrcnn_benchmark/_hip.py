@@ -166,6 +166,8 @@ _SIGS = {
     "mmt_gconv3x3_forward": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "mmt_gconv3x3_dgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "mmt_gconv3x3_wgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "mmt_maxpool3x3s2_backward": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "mmt_stem_wgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "mmt_mask_bce": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "mmt_mgd_level_forward": [c_void_p, ctypes.POINTER(MgdTeachers), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_mgd_level_backward": [c_void_p, ctypes.POINTER(MgdTeachers), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
@@ -733,6 +735,23 @@ def f16_weight_planes(w, flip_scale=None, flipped=False):
                                          _stream()), "mmt_pack_weight_f16")
     _F16W[(ptr, flipped)] = (key, pl, am, weakref.ref(w))
     return pl, am[1:2]
+
+
+def refresh_f16_weight_planes(w):
+    """`w` -- a weight that is not a parameter of a flattened model -- was rewritten in place: its fp16 planes are re-packed into
+    the SAME plane and scale tensors (a recorded launch plan holds their addresses).  Nothing cached for it: nothing to do."""
+    hit = _F16W.get((w.data_ptr(), False))
+    if hit is None or hit[3]() is not w:
+        return
+    _, pl, am, ref = hit
+    Cout, Cin, KH, KW = w.shape
+    K = Cin * KH * KW
+    am.zero_()
+    F16_STATS["weight_pack"] = F16_STATS.get("weight_pack", 0) + 1
+    _check(lib().mmt_amax(w.data_ptr(), w.numel(), None, K, Cout, am.data_ptr(), _stream()), "mmt_amax")
+    _check(lib().mmt_pack_weight_f16(w.data_ptr(), pl.data_ptr(), pl.stride(0), Cout, K, 1.0, am.data_ptr(), am.data_ptr() + 4,
+                                     _stream()), "mmt_pack_weight_f16")
+    _F16W[(w.data_ptr(), False)] = ((w._version, tuple(w.shape), None, None, PLANES_EPOCH, None), pl, am, ref)
 
 
 def set_bf16_storage(on):
@@ -2206,6 +2225,52 @@ def maxpool3x3s2(x):
     else:
         _check(lib().mmt_maxpool3x3s2(_p(x), _p(y), N, H, W, C, Ho, Wo, _stream()), "mmt_maxpool3x3s2")
     return y
+
+
+def refuse_trainable_stem_bf16():
+    """a stem that records gradients, asked before its forward launches (modeling/backbone/backbone.py): its backward reads the
+    un-pooled output as fp32"""
+    if bf16_storage():
+        raise NotImplementedError("MODEL.BACKBONE.FREEZE_CONV_BODY_AT 0 (a trainable stem) is not offered with bf16 activation "
+                                  "storage: set_bf16_storage(False)")
+
+
+def maxpool3x3s2_backward(y, g, out=None):
+    """include/mmtpsm.h: mmt_maxpool3x3s2_backward.  y (N, C, H, W) the pool's input (a ReLU output), g the gradient of
+    maxpool3x3s2(y) -> (y > 0) * the pool's gradient, ATen's first-maximum rule; every element is written (out: a destination to fill)"""
+    y, g = nhwc(_dev(y, "y")), nhwc(_dev(g, "g"))
+    N, C, H, W = y.shape
+    if (y.dtype != torch.float32 or g.dtype != torch.float32 or C % 4
+            or tuple(g.shape) != (N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1)):
+        raise RuntimeError("max-pool backward: fp32 y (N, C, H, W) with C %% 4 == 0 and g of the pooled shape; got y %s, g %s"
+                           % (tuple(y.shape), tuple(g.shape)))
+    if out is None:
+        out = empty_nhwc(N, C, H, W, y.device)
+    elif tuple(out.shape) != (N, C, H, W) or out.dtype != torch.float32 or not out.is_cuda or nhwc(out) is not out:
+        raise RuntimeError("max-pool backward: `out` is an NHWC-dense fp32 GPU tensor of y's shape")
+    _check(lib().mmt_maxpool3x3s2_backward(_p(y), _p(g), _p(out), N, H, W, C, _stream()), "mmt_maxpool3x3s2_backward")
+    return out
+
+
+def stem_wgrad(x, dy, dw, rowscale=None):
+    """include/mmtpsm.h: mmt_stem_wgrad.  x (N, 3, H, W) fp32 NCHW-contiguous (the image), dy (N, 64, Ho, Wo) the gradient of the
+    7x7 / stride 2 / pad 3 convolution's output; dw (64, 3, 7, 7 in the weight's channels-last layout) += rowscale[co] * the
+    weight gradient"""
+    _dev(x, "x")
+    dy = nhwc(_dev(dy, "dy"))
+    N, C, H, W = x.shape
+    if (C != 3 or x.dtype != torch.float32 or not x.is_contiguous() or dy.dtype != torch.float32
+            or tuple(dy.shape) != (N, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1)):
+        raise RuntimeError("stem weight gradient: fp32 NCHW-contiguous x (N, 3, H, W) and dy (N, 64, Ho, Wo); got x %s, dy %s"
+                           % (tuple(x.shape), tuple(dy.shape)))
+    _dev(dw, "dw")
+    if dw.dtype != torch.float32 or dw.numel() != 64 * 147 or (dw.dim() == 4 and (tuple(dw.shape) != (64, 3, 7, 7) or nhwc(dw) is not dw)) \
+            or (dw.dim() != 4 and not dw.is_contiguous()):
+        raise RuntimeError("stem weight gradient: dw is a dense fp32 tensor in the weight's layout (64, 3, 7, 7 channels-last)")
+    if rowscale is not None and not (rowscale.is_cuda and rowscale.dtype == torch.float32 and rowscale.numel() == 64 and rowscale.is_contiguous()):
+        raise RuntimeError("stem weight gradient: rowscale is a dense fp32 GPU vector of 64 elements")
+    _check(lib().mmt_stem_wgrad(_p(x), _p(dy), _p(rowscale), _p(dw), N, H, W, _stream()), "mmt_stem_wgrad")
+    return dw
 
 
 # ------------------------------------------------------------------------------------------ grouped 3x3 convolution (ResNeXt conv2)

@@ -49,6 +49,7 @@ class FlatParams(object):
             view = self._view_like(self.data[o:o + k], p)
             view.copy_(p.data)
             p.data = view
+            p._flat_ref = me   # (what is derived from a parameter outside the bulk packs asks for the buffer's plane generation)
             if p.requires_grad:
                 p.grad = self._view_like(self.grad[o:o + k], p)
                 # fused backward nodes accumulate weight gradients straight into this slot (layers/fused.py)

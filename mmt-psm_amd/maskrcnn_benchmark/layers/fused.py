@@ -408,6 +408,32 @@ class BottleneckFn(torch.autograd.Function):
         return dx, dw1, dw2, dw3, dwd, None, None, None, None
 
 
+class StemFn(torch.autograd.Function):
+    """A trainable stem (FREEZE_CONV_BODY_AT 0; backbone/resnet.py:288-293): conv 7x7 / 2 + FrozenBN + ReLU -> max pool 3x3 / 2.
+    `pre` = (y, pooled) of the un-fused forward launches for this image batch (backbone.py: StemWithFixedBatchNorm.forward_raw, or
+    batch slices of it: forward_pair); the node records the image and y.  Backward: the pool's gradient with y's ReLU mask
+    (mmt_maxpool3x3s2_backward; `g` arrives masked by (pooled > 0), which changes nothing: a window whose maximum is 0 has no
+    positive element), then the weight gradient straight from the image (mmt_stem_wgrad).  The input is the image: no dx."""
+
+    @staticmethod
+    def forward(ctx, x, w, scale, pre):
+        y, pooled = pre
+        ctx.save_for_backward(x, y)
+        ctx.scale = scale
+        ctx.dst = _dst(w)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        d = ctx.dst
+        dy = H.maxpool3x3s2_backward(y, H.nhwc(g))
+        dw = d if d is not None else torch.zeros((64, 7, 7, 3), dtype=torch.float32, device=x.device).permute(0, 3, 1, 2)
+        H.stem_wgrad(x, dy, dw, ctx.scale)
+        _touch(d)
+        return None, (None if d is not None else dw), None, None
+
+
 def fpn_forward(cs, wi, bi, wl, bl, out_planes=True):
     """the 8 launches of the FPN -> (inner[4], outs[4])"""
     inner = [None] * 4

@@ -25,19 +25,37 @@ class StemWithFixedBatchNorm(nn.Module):
         self.conv1 = Conv2d(3, out, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = FrozenBatchNorm2d(out)
 
+    # set by ResNet for FREEZE_CONV_BODY_AT 0: the filter changes under raw-pointer updates of the flat parameter buffer (SGD for the
+    # student, the EMA for the teacher -- engine/flat.py), which no version counter sees; what is derived from it below then follows
+    # the buffer's plane generation as well
+    follows_updates = False
+
+    def _weight_gen(self):
+        if not self.follows_updates:
+            return None
+        ref = getattr(self.conv1.weight, "_flat_ref", None)
+        flat = ref() if ref is not None else None
+        return None if flat is None else flat.plane_gen
+
     def _s2d_weight(self):
         """the 7x7 / stride-2 filter as a 4x4 / stride-1 filter over the 2x2 space-to-depth image: pad the filter
         to 8x8 with a zero row / column in FRONT (tap kh sits at 2a + b - 1), fold the parity (b_h, b_w) and the
-        4-padded RGB channel into 16 input channels.  Cached: the stem is frozen (reference resnet.py:StemWithFixedBatchNorm
-        + FREEZE_CONV_BODY_AT >= 1), re-made only if the parameter is written."""
+        4-padded RGB channel into 16 input channels.  Cached: re-made when the parameter is written, or -- a trainable stem --
+        when its flat buffer was updated; then IN PLACE, filter and packed planes alike: a launch plan recorded for the
+        teacher's backbone holds their addresses."""
         w = self.conv1.weight
-        key = (w.data_ptr(), w._version)
-        if getattr(self, "_s2d_key", None) != key:
+        key = (w.data_ptr(), w._version, self._weight_gen())
+        old = getattr(self, "_s2d_key", None)
+        if old != key:
             co = w.shape[0]
             w8 = w.new_zeros((co, 8, 8, 4))
             w8[:, 1:, 1:, :3] = w.detach().permute(0, 2, 3, 1)
             ws = w8.view(co, 4, 2, 4, 2, 4).permute(0, 1, 3, 2, 4, 5).reshape(co, 4, 4, 16)
-            self._s2d_w = ws.contiguous().permute(0, 3, 1, 2)  # (co, 16, 4, 4) in channels_last memory
+            if old is not None and old[:2] == key[:2] and self._s2d_w.device == w.device:
+                self._s2d_w.copy_(ws.permute(0, 3, 1, 2))
+                H.refresh_f16_weight_planes(self._s2d_w)
+            else:
+                self._s2d_w = ws.contiguous().permute(0, 3, 1, 2)  # (co, 16, 4, 4) in channels_last memory
             self._s2d_key = key
         return self._s2d_w
 
@@ -51,12 +69,35 @@ class StemWithFixedBatchNorm(nn.Module):
                 and H._site_ok(("stem", self.conv1.weight.data_ptr()), x, count=count))
 
     def forward(self, x):
-        n, c, h, w = x.shape
-        s, b = self.bn1.folded()
+        """the stem's output for the image batch `x`.  Whether gradients are recorded follows `conv1.weight.requires_grad` alone, as in
+        torch: ResNet clears it unless FREEZE_CONV_BODY_AT is 0, and a stem built on its own has it set (nn.Parameter's default) -- in
+        grad mode it then runs the un-fused launches below, with the same values as the one-launch stem; freeze the weight or call
+        under torch.no_grad() for the fused launch."""
+        if self.conv1.weight.requires_grad and torch.is_grad_enabled():
+            # FREEZE_CONV_BODY_AT 0: the un-fused launches (their un-pooled output is what the backward reads), one autograd node
+            H.refuse_trainable_stem_bf16()
+            with torch.no_grad():
+                pre = self.forward_raw(x)
+            return self.node(x, pre)
         if self.fused_ok(x):
             # round 5: the whole stem -- convolution, FrozenBN, ReLU, max pool -- as one launch (csrc/conv_stem.hip): the 537 MB of
             # un-pooled output (8 x 1024^2) never exist; bit-identical to the three launches below
+            s, b = self.bn1.folded()
             return H.stem_fused(x, self._s2d_weight(), s, b)
+        return self.forward_raw(x)[1]
+
+    def node(self, x, pre):
+        """the autograd node of a trainable stem for the image batch `x` and pre = forward_raw(x) (or a batch slice of both:
+        forward_pair)"""
+        out = fused.StemFn.apply(x, self.conv1.weight, self.bn1.folded()[0], pre)
+        if out is not pre[1]:
+            H.carry(pre[1], out)
+        return out
+
+    def forward_raw(self, x):
+        """no autograd: (y, pooled) -- the convolution + FrozenBN + ReLU output and its max pool -- by the un-fused launches"""
+        n, c, h, w = x.shape
+        s, b = self.bn1.folded()
         if h % 2 == 0 and w % 2 == 0:
             # 16-channel space-to-depth image -> the DMA-fed split-bf16 kernel instead of the 4-channel fp32 one:
             # out(ho) = sum_kh x(2 ho - 3 + kh) w(kh) = sum_{a,b} z(ho - 2 + a, b) w8(2 a + b),  z(i, b) = x(2 i + b)
@@ -64,7 +105,7 @@ class StemWithFixedBatchNorm(nn.Module):
             z[..., :3] = x.view(n, c, h // 2, 2, w // 2, 2).permute(0, 2, 4, 3, 5, 1)
             y = H.conv_forward(z.view(n, h // 2, w // 2, 16).permute(0, 3, 1, 2), self._s2d_weight(), s, b, 1, 2,
                                relu=True, out_size=(h // 2, w // 2), out_dtype=torch.bfloat16 if H.bf16_storage() else None)
-            return _pool_keep_stats(y)
+            return y, _pool_keep_stats(y)
         # odd sizes: pad RGB -> 4 channels (zero weight on the 4th), fp32-input kernel
         x4 = x.new_zeros((n, h, w, 4))
         x4[..., :3] = x.permute(0, 2, 3, 1)
@@ -72,7 +113,7 @@ class StemWithFixedBatchNorm(nn.Module):
         w4[..., :3] = self.conv1.weight.detach().permute(0, 2, 3, 1)
         y = H.conv_forward(x4.permute(0, 3, 1, 2), w4.permute(0, 3, 1, 2), s, b, 2, 3, relu=True,
                            out_dtype=torch.bfloat16 if H.bf16_storage() else None)
-        return _pool_keep_stats(y)
+        return y, _pool_keep_stats(y)
 
 
 def _pool_keep_stats(y):
@@ -165,11 +206,15 @@ class ResNet(nn.Module):
             m = self.stem if si == 0 else getattr(self, "layer%d" % si)
             for p in m.parameters():
                 p.requires_grad = False
+        self.stem.follows_updates = self.freeze_at == 0
 
     def forward(self, x):
         outs = []
-        with torch.no_grad():
-            x = self.stem(x)
+        if self.freeze_at == 0:
+            x = self.stem(x)      # (a node of its own when gradients are recorded: layers/fused.py::StemFn)
+        else:
+            with torch.no_grad():
+                x = self.stem(x)
         for i, name in enumerate(self.stages, 1):
             if i < self.freeze_at:
                 with torch.no_grad():
@@ -202,8 +247,17 @@ def forward_pair(backbone, xa, xb):
     body, fpn = backbone.body, backbone.fpn
     n = xa.shape[0]
     halves = ((0, n), (n, 2 * n))
+    stem_pre = None
+    train_stem = body.freeze_at == 0 and torch.is_grad_enabled() and body.stem.conv1.weight.requires_grad
     with torch.no_grad():
-        x = body.stem(torch.cat([xa, xb], 0))
+        x_cat = torch.cat([xa, xb], 0)
+        if train_stem:
+            H.refuse_trainable_stem_bf16()
+            stem_pre = body.stem.forward_raw(x_cat)   # (y, pooled): each half gets its own StemFn node below
+            x = stem_pre[1]
+        else:
+            x = body.stem(x_cat)
+        x0 = x
         raw = {}     # block -> (o1, o2, out) on the concatenated batch
         frozen = []
         for i, name in enumerate(body.stages, 1):
@@ -228,6 +282,10 @@ def forward_pair(backbone, xa, xb):
     for lo, hi in halves:
         outs = []
         x = None
+        if stem_pre is not None:
+            x = body.stem.node(x_cat[lo:hi], tuple(fused.batch_slice(t, lo, hi) for t in stem_pre))
+        elif body.freeze_at < 2:
+            x = fused.batch_slice(x0, lo, hi)   # (the frozen stem's output: layer1's first node reads it)
         for i, name in enumerate(body.stages, 1):
             if i < body.freeze_at:
                 x = fused.batch_slice(frozen[i - 1], lo, hi)

@@ -69,6 +69,10 @@ class GeneralizedRCNN(nn.Module):
             # (only the fused stem reads the image through C-ABI launches alone; the key carries what else selects
             # launches or addresses: the stem switch and this model's weight epoch -- bumped by load_state_dict)
             from maskrcnn_benchmark.modeling.backbone.backbone import _STEM_FUSED
+            if self.backbone.body.stem.follows_updates:
+                # FREEZE_CONV_BODY_AT 0: the stem filter moves with every SGD / EMA step; what a replay reads of it is brought up to
+                # date here, in place, at the addresses the plan recorded
+                self.backbone.body.stem._s2d_weight()
             return _hip.planned(("backbone", id(self), _STEM_FUSED[0], getattr(self, "_weights_epoch", 0)),
                                 lambda t: tuple(self.backbone(t)), x)
         return tuple(self.backbone(x))
