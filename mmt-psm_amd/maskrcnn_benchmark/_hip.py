@@ -211,7 +211,6 @@ F16X2 = F16X2_DEFAULT
 F16X2_TILED = True   # (constant, read by bench.py: the tiled kernel -- 1x1, small-map 3x3, fc -- runs on the fp16 split like the strip kernel)
 F16_STATS = {"wgrad": 0, "conv": 0, "tiled": 0, "pg": 0, "amax_pass": 0, "fallback": 0, "weight_pack": 0}   # launches that took the fp16 path (tools, tests)
 WGRAD_F16_MIN_ELEMS = 1 << 22
-_F16W = {}   # weight address -> (key, planes, device scale)
 
 
 def set_f16x2(on):
@@ -220,7 +219,7 @@ def set_f16x2(on):
     F16X2 = F16X2_DEFAULT if on is None else bool(on)
     _PLAN_EPOCH[0] += 1
     _PLAN.clear()
-    _F16W.clear()
+    LOOSE.forget()
     _F16SITE.clear()
     _SITES.clear()
     rb_reset()
@@ -690,68 +689,40 @@ def f16_split_pg(x):
     return xp, st, 1, 0
 
 
+def _pack_f16(w, scale, flipped, pl, am):
+    """the per-call pack of one weight's fp16 form: reduction launch (am[0] = max |w scale|) + packing launch (am[1] = scale word)"""
+    Cout, Cin, KH, KW = w.shape
+    F16_STATS["weight_pack"] = F16_STATS.get("weight_pack", 0) + 1
+    _check(lib().mmt_amax(w.data_ptr(), w.numel(), _p(scale) if flipped else None, Cin * KH * KW, Cout, am.data_ptr(), _stream()), "mmt_amax")
+    if flipped:
+        _check(lib().mmt_pack_weight_flipped_f16(w.data_ptr(), _p(scale), pl.data_ptr(), pl.stride(0), Cout, KH, KW, Cin,
+                                                 am.data_ptr(), am.data_ptr() + 4, _stream()), "mmt_pack_weight_flipped_f16")
+    else:
+        _check(lib().mmt_pack_weight_f16(w.data_ptr(), pl.data_ptr(), pl.stride(0), Cout, Cin * KH * KW, 1.0, am.data_ptr(),
+                                         am.data_ptr() + 4, _stream()), "mmt_pack_weight_f16")
+
+
 def f16_weight_planes(w, flip_scale=None, flipped=False):
     """packed fp16 planes + a one-element device view holding their scale, of a forward weight or of its data-gradient form
     (taps flipped, transposed, rows scaled by flip_scale).  Parameters of a flattened model (engine/flat.py) are packed in
     bulk after every SGD / EMA step (raw-pointer updates that no version counter sees) and only looked up here; anything else
-    is packed per call and cached until the tensor (or the scale vector) is modified."""
-    ptr = w.data_ptr()
-    ent = PLANES.get(ptr)
-    flat = ent[0]() if ent is not None else None
-    gen = None
-    if flat is not None and ent[2] == w.numel():
-        gen = flat.plane_gen
-        if flat.plane_versions.get(ptr) == w._version and flat.plane_epoch >= PLANES_EPOCH:
-            if flipped:
-                hit = flat.flipped16(w, flip_scale)
-                if hit is not None:
-                    return hit
-            elif flat.f16_gen == gen and len(ent) > 3:
-                hit = flat.views16.get(ptr)   # the views never change: planes16 / stat16 are allocated once
-                if hit is None:
-                    n = packed_elems(w.shape[0], w.numel() // w.shape[0])
-                    hit = flat.views16[ptr] = (flat.planes16[:, ent[1]:ent[1] + n], flat.stat16[ent[3], 1:2])
-                return hit
-    # valid for THIS tensor object only (an address is reused by the allocator; parameters are long-lived objects)
-    key = (w._version, tuple(w.shape), _p(flip_scale), None if flip_scale is None else flip_scale._version, PLANES_EPOCH, gen)
-    hit = _F16W.get((ptr, flipped))
-    if hit is not None and hit[0] == key and hit[3]() is w:
-        return hit[1], hit[2][1:2]
+    is packed per call and kept until the tensor (or the scale vector) is modified."""
+    form = "f16_dgrad" if flipped else "f16"
+    flat, hit = _flat_form(w, form, flip_scale)
+    if hit is not None:
+        return hit
+    stamp = _loose_stamp(w, flip_scale, w)
+    hit = LOOSE.get(w, form, stamp, flip_scale)
+    if hit is not None:
+        return hit
     Cout, Cin, KH, KW = w.shape
     am = torch.zeros((2,), dtype=torch.float32, device=w.device)
-    K = Cin * KH * KW
-    F16_STATS["weight_pack"] = F16_STATS.get("weight_pack", 0) + 1
-    _check(lib().mmt_amax(w.data_ptr(), w.numel(), _p(flip_scale) if flipped else None, K, Cout, am.data_ptr(), _stream()), "mmt_amax")
-    if flipped:
-        pl = torch.empty((2, packed_elems(Cin, KH * KW * Cout)), dtype=torch.float16, device=w.device)
-        _check(lib().mmt_pack_weight_flipped_f16(w.data_ptr(), _p(flip_scale), pl.data_ptr(), pl.stride(0), Cout, KH, KW, Cin,
-                                                 am.data_ptr(), am.data_ptr() + 4, _stream()), "mmt_pack_weight_flipped_f16")
-        if flat is not None and gen is not None and flat.plane_versions.get(ptr) == w._version:
-            # from the next optimiser step on these planes follow the parameters in the bulk launch (engine/flat.py)
-            flat.register_flipped16(w, flip_scale, pl, (Cout, KH, KW, Cin))
-    else:
-        pl = torch.empty((2, packed_elems(Cout, K)), dtype=torch.float16, device=w.device)
-        _check(lib().mmt_pack_weight_f16(w.data_ptr(), pl.data_ptr(), pl.stride(0), Cout, K, 1.0, am.data_ptr(), am.data_ptr() + 4,
-                                         _stream()), "mmt_pack_weight_f16")
-    _F16W[(ptr, flipped)] = (key, pl, am, weakref.ref(w))
-    return pl, am[1:2]
-
-
-def refresh_f16_weight_planes(w):
-    """`w` -- a weight that is not a parameter of a flattened model -- was rewritten in place: its fp16 planes are re-packed into
-    the SAME plane and scale tensors (a recorded launch plan holds their addresses).  Nothing cached for it: nothing to do."""
-    hit = _F16W.get((w.data_ptr(), False))
-    if hit is None or hit[3]() is not w:
-        return
-    _, pl, am, ref = hit
-    Cout, Cin, KH, KW = w.shape
-    K = Cin * KH * KW
-    am.zero_()
-    F16_STATS["weight_pack"] = F16_STATS.get("weight_pack", 0) + 1
-    _check(lib().mmt_amax(w.data_ptr(), w.numel(), None, K, Cout, am.data_ptr(), _stream()), "mmt_amax")
-    _check(lib().mmt_pack_weight_f16(w.data_ptr(), pl.data_ptr(), pl.stride(0), Cout, K, 1.0, am.data_ptr(), am.data_ptr() + 4,
-                                     _stream()), "mmt_pack_weight_f16")
-    _F16W[(w.data_ptr(), False)] = ((w._version, tuple(w.shape), None, None, PLANES_EPOCH, None), pl, am, ref)
+    pl = torch.empty((2, packed_elems(Cin, KH * KW * Cout) if flipped else packed_elems(Cout, Cin * KH * KW)), dtype=torch.float16,
+                     device=w.device)
+    _pack_f16(w, flip_scale, flipped, pl, am)
+    if flipped and flat is not None and flat.register(form, w, flip_scale, pl, am):
+        return pl, am[1:2]   # (served by the buffer from now on)
+    return LOOSE.put(w, form, stamp, flip_scale, (pl, am[1:2]), w, am)
 
 
 def set_bf16_storage(on):
@@ -1731,13 +1702,11 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
     a.x = x.data_ptr()
     if w is None:
         a.w_planes, a.w_plane_stride = planes.data_ptr(), planes.stride(0)
-        _TLS.bf16_owner = None
-        if f16_src is not None:   # data-gradient planes of a flat model's weight: deferred like the forward planes
-            ent = PLANES.get(f16_src[0].data_ptr())
-            _TLS.bf16_owner = ent[0]() if ent is not None else None
+        # data-gradient planes of a flat model's weight: deferred like the forward planes
+        planes_owner = _flat_form(f16_src[0], None)[0] if f16_src is not None else None
     else:
         a.w = w.data_ptr()
-        _keep = _weight_planes(w, a)  # noqa: F841  (keeps a per-call plane buffer alive until the launch is queued)
+        _keep, planes_owner = _weight_planes(w, a)  # noqa: F841  (keeps a per-call plane buffer alive until the launch is queued)
     if out_stride > 1:
         oh, ow = out_hw
         y = y_out if y_out is not None else empty_nhwc(N, Cout, oh, ow, x.device, zero=True, dtype=out_dtype)
@@ -1800,7 +1769,8 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
         if rec:
             pre = (p0, _ev())
     e0 = _ev() if rec else None
-    _ensure_bf16()
+    if planes_owner is not None:
+        planes_owner.ensure_bf16()
     _check(lib().mmt_conv_forward(ctypes.byref(a), _stream()), "mmt_conv_forward")
     if rec:
         _profiled(a, e0, "fwd%d" % var, lib().mmt_conv_ksplit(ctypes.byref(a)), pre, ebytes)
@@ -1868,14 +1838,92 @@ def conv_pg_plan(N, Cin, H, W, Cout, KH, KW, stride, pad):
     return rows.value, ks.value
 
 
-# pre-split bf16 planes of weight tensors (split-bf16 conv modes), keyed by the weight's device address:
-#   address -> (weakref to the owning FlatParams, element offset, numel).  engine/flat.py registers every parameter of a
-#   flattened model here (one [3, total] buffer refreshed after each SGD / EMA step); anything else -- and any parameter
-#   modified in place since the last refresh (its version counter moved) -- is split per call.
-PLANES = {}
+# ---- who owns the derived forms of a weight (what a convolution reads instead of the weight: packed bf16 / fp16 planes of the
+# forward and the data-gradient matrix, the flipped fp32 tensor).  A parameter of a flattened model: its FlatParams, found by the
+# weight's address -- a Linear weight arrives as a fresh view every call, a backward pass sees new objects -- in FLATS, whose
+# values are weak: an entry goes when its owner dies; FlatParams.form alone decides what is current (the invariants are stated
+# there).  Anything else -- also a flat model's parameter written through torch since the last refresh -- : LOOSE, by the identity of
+# the tensor object.  An entry holds a weak reference to its owner, is removed when the owner dies and is served only to that very
+# object: neither an id nor an address that comes back can hit.  One validity rule: `_loose_stamp` and the identity of the scale
+# vector.  Raw-pointer writes (sgd_momentum, ema_update) announce their bytes: `forget`.
+FLATS = weakref.WeakValueDictionary()   # address of a packed weight matrix -> the FlatParams that holds it (engine/flat.py puts them)
 GRAD_SLOTS = {}  # address of a parameter's slot in a flat gradient buffer -> (weakref FlatParams, parameter name); engine/flat.py
-PLANES_EPOCH = 0  # bumped by set_conv_precision: planes packed before a mode switch are not trusted afterwards (steps taken
-                  # in mode 0 do not refresh them)
+PLANES_EPOCH = 0  # THE counter of the arithmetic mode, bumped by set_conv_precision: nothing packed before a mode switch is trusted
+                  # afterwards (steps taken in mode 0 do not refresh the planes)
+
+
+def _flat_form(w, form, scale=None):
+    """-> (the live FlatParams whose buffer holds the packed matrix `w`, or None; what it serves for `w` in `form`, or None)"""
+    flat = FLATS.get(w.data_ptr())
+    return flat, (flat.form(w, form, scale) if flat is not None and form is not None else None)
+
+
+class _LooseEntry(object):
+    __slots__ = ("ref", "stamp", "scale", "served", "lo", "hi", "keep")
+
+
+class LooseForms(object):
+    """derived forms ("f16", "f16_dgrad", "f32_dgrad") of weights no flat buffer vouches for, keyed by (id(owner), form)"""
+
+    def __init__(self):
+        self.entries = {}
+
+    def get(self, owner, form, stamp, scale):
+        e = self.entries.get((id(owner), form))
+        return e.served if e is not None and e.stamp == stamp and e.scale is scale and e.ref() is owner else None
+
+    def put(self, owner, form, stamp, scale, served, src, keep=None):
+        """keep `served` for (owner, form); src: the tensor it was derived from (its bytes are what `forget` compares) -> served"""
+        key = (id(owner), form)
+        e = self.entries.get(key)
+        if e is None or e.ref() is not owner:
+            # ONE entry and one finalizer per live owner and form: `forget` empties the entry and leaves it in place, so that the
+            # next put finds it (a finalizer holds its entry until the owner dies: a popped entry would pin what it served)
+            e = self.entries[key] = _LooseEntry()
+            e.ref = weakref.ref(owner)
+            weakref.finalize(owner, self._drop, key, e)
+        e.stamp, e.scale, e.served, e.keep, e.lo = stamp, scale, served, keep, src.data_ptr()
+        e.hi = e.lo + src.numel() * src.element_size()
+        return served
+
+    def _drop(self, key, e):
+        if self.entries.get(key) is e:
+            self.entries.pop(key, None)
+
+    def forget(self, t=None):
+        """the bytes of `t` were rewritten through raw pointers (no version counter moved): what was derived from them is let go
+        (t None: everything)"""
+        lo, hi = (0, 1 << 64) if t is None else (t.data_ptr(), t.data_ptr() + t.numel() * t.element_size())
+        # (list of the values: one C call that allocates nothing the collector tracks, so neither the teacher's thread nor a
+        # finalizer can change the dict under it)
+        for e in list(self.entries.values()):
+            if e.lo < hi and lo < e.hi:
+                e.stamp = e.scale = e.served = e.keep = None
+
+    def refresh(self, w):
+        """`w` -- a weight that is not a parameter of a flattened model -- was rewritten in place: its fp16 planes are re-packed into
+        the SAME plane and scale tensors (a recorded launch plan holds their addresses).  Nothing kept for it: nothing to do."""
+        e = self.entries.get((id(w), "f16"))
+        if e is not None and e.served is not None and e.ref() is w:
+            e.keep.zero_()
+            _pack_f16(w, None, False, e.served[0], e.keep)
+            e.stamp = _loose_stamp(w, None, w)
+
+
+LOOSE = LooseForms()
+refresh_f16_weight_planes = LOOSE.refresh
+
+
+def _loose_stamp(w, scale, owner, stream=None):
+    """what a loose form was packed from and under"""
+    # the tensor's version and dimensions, the scale vector's version, the arithmetic counter, the plane generation of the flat buffer
+    # its owner is a parameter of (raw-pointer updates of the buffer; engine/flat.py marks every parameter, also those it packs no
+    # planes for), and -- the fp32 form only, a plain tensor handed to the next launch; the fp16 planes' addresses sit in recorded
+    # plans and stay -- the stream
+    ref = getattr(owner, "_flat_ref", None)
+    flat = ref() if ref is not None else None
+    return (w._version, tuple(w.shape), None if scale is None else scale._version, PLANES_EPOCH,
+            None if flat is None else flat.plane_gen, stream)
 
 
 def packed_elems(cout, k):
@@ -1901,28 +1949,14 @@ def pack_weight_flipped(w, scale=None):
     w = nhwc(w)
     # A weight is used by several backward passes between two optimiser steps (labeled and unlabeled student pass, the RPN
     # head on five levels): packed once per parameter generation of its flat buffer (engine/flat.py: refresh_planes).
-    ptr, key = w.data_ptr(), None
-    ent = PLANES.get(ptr)
-    if ent is not None:
-        flat = ent[0]()
-        if (flat is not None and ent[2] == w.numel() and flat.plane_versions.get(ptr) == w._version
-                and flat.plane_epoch >= PLANES_EPOCH):
-            key = (id(flat), flat.plane_gen, _p(scale), None if scale is None else scale._version)
-            hit = FLIPPED.get(ptr)
-            if hit is not None and hit[0] == key:
-                return hit[1]
-    planes = torch.empty((3, packed_elems(Cin, KH * KW * Cout)), dtype=torch.bfloat16, device=w.device)
-    _check(lib().mmt_pack_weight_flipped(w.data_ptr(), _p(scale), planes.data_ptr(), planes.stride(0), Cout, KH, KW, Cin,
-                                         _stream()), "mmt_pack_weight_flipped")
-    if key is not None:
-        FLIPPED[ptr] = (key, planes)
-        # from the next optimiser step on this weight's data-gradient planes are re-packed together with all the others in
-        # one launch right after the step (engine/flat.py: refresh_planes), instead of one launch per layer in backward
-        flat.register_flipped(w, scale, planes, (Cout, KH, KW, Cin))
+    flat, planes = _flat_form(w, "bf16_dgrad", scale)
+    if planes is None:
+        planes = torch.empty((3, packed_elems(Cin, KH * KW * Cout)), dtype=torch.bfloat16, device=w.device)
+        _check(lib().mmt_pack_weight_flipped(w.data_ptr(), _p(scale), planes.data_ptr(), planes.stride(0), Cout, KH, KW, Cin,
+                                             _stream()), "mmt_pack_weight_flipped")
+        if flat is not None:
+            flat.register("bf16_dgrad", w, scale, planes)
     return planes
-
-
-FLIPPED = {}  # weight address -> ((flat id, generation, scale address, scale version), packed data-gradient planes)
 
 
 def pack_weights(base, planes, descs, unit_desc, n_units):
@@ -1930,35 +1964,16 @@ def pack_weights(base, planes, descs, unit_desc, n_units):
                                   unit_desc.data_ptr(), n_units, _stream()), "mmt_pack_weights")
 
 
-def _ensure_bf16():
-    o = getattr(_TLS, "bf16_owner", None)
-    if o is not None:
-        o.ensure_bf16()
-
-
 def _weight_planes(w, a):
-    """fill a.w_planes / a.w_plane_stride for a dense weight tensor when a split-bf16 mode is on"""
-    _TLS.bf16_owner = None
+    """fill a.w_planes / a.w_plane_stride for a dense weight tensor when a split-bf16 mode is on -> (the planes, kept alive until the
+    launch is queued; the FlatParams that serves them or None: conv_forward calls its ensure_bf16 before a launch that reads them)"""
     if get_conv_precision() == 0 or (w.shape[1] & 15) or w.shape[0] <= 32:
-        return None
-    ptr = w.data_ptr()
-    ent = PLANES.get(ptr)
-    if ent is not None:
-        flat = ent[0]()
-        if flat is None or flat.planes is None:
-            del PLANES[ptr]
-        elif ent[2] == w.numel() and flat.plane_versions.get(ptr) == w._version and flat.plane_epoch >= PLANES_EPOCH:
-            a.w_planes, a.w_plane_stride = flat.planes.data_ptr() + 2 * ent[1], flat.planes.stride(0)
-            _TLS.bf16_owner = flat   # (packed lazily on the fp16 split: conv_forward calls ensure_bf16 before a launch that reads them)
-            return flat.planes
-    pl = pack_weight(w)
+        return None, None
+    flat, pl = _flat_form(w, "bf16")
+    if pl is None:
+        flat, pl = None, pack_weight(w)
     a.w_planes, a.w_plane_stride = pl.data_ptr(), pl.stride(0)
-    return pl
-
-
-WEIGHTS_GEN = [0]    # bumped by every library call that writes parameters through raw pointers (sgd_momentum, ema_update: those bump no tensor
-                     # version) and at the start of every training step (engine/MTtrainer.py)
-_LOOSE_FLIPS = {}    # weight address -> ((version, shape, scale address, scale version, stream), flipped fp32 weights)
+    return pl, flat
 
 
 _PREC = None   # the library's mode, mirrored here (asked several times per launch)
@@ -2200,18 +2215,15 @@ def weight_flip_transpose(w, scale=None, owner=None):
     Cout, Cin, KH, KW = w.shape
     # the RPN predictors' data gradient runs once per pyramid level with the same weights: flipped once per version and stream
     # (identity of the Parameter object, not its address: a freed tensor's address comes back with another tensor's values)
-    ptr = w.data_ptr()
-    key = (w._version, WEIGHTS_GEN[0], (Cout, Cin, KH, KW), _p(scale), None if scale is None else scale._version, _stream())
-    hit = _LOOSE_FLIPS.get(ptr)
-    if hit is not None and hit[0] == key and hit[2]() is w0:
-        return hit[1]
+    stamp = _loose_stamp(w, scale, w0, _stream())
+    hit = LOOSE.get(w0, "f32_dgrad", stamp, scale)
+    if hit is not None:
+        return hit
     wd = empty_nhwc(Cin, Cout, KH, KW, w.device)
     _check(lib().mmt_weight_flip_transpose(_p(w), _p(scale), _p(wd), Cout, KH, KW, Cin, _stream()),
            "mmt_weight_flip_transpose")
-    if scale is None and owner is not None and w0.data_ptr() == ptr and w0._version == w._version:
-        if len(_LOOSE_FLIPS) >= 64:
-            _LOOSE_FLIPS.clear()
-        _LOOSE_FLIPS[ptr] = (key, wd, weakref.ref(w0))
+    if scale is None and owner is not None and w0.data_ptr() == w.data_ptr() and w0._version == w._version:
+        LOOSE.put(w0, "f32_dgrad", stamp, scale, wd, w)
     return wd
 
 
@@ -2527,14 +2539,14 @@ def ema_update(teacher_flat, student_flat, alpha):
     _dev(teacher_flat)
     _dev(student_flat)
     assert teacher_flat.numel() == student_flat.numel() and teacher_flat.is_contiguous() and student_flat.is_contiguous()
-    WEIGHTS_GEN[0] += 1
+    LOOSE.forget(teacher_flat)
     _check(lib().mmt_ema_update(_p(teacher_flat), _p(student_flat), teacher_flat.numel(), float(alpha), _stream()),
            "mmt_ema_update")
 
 
 def sgd_momentum(p, g, buf, lr, wd, momentum, first):
     _dev(p)
-    WEIGHTS_GEN[0] += 1
+    LOOSE.forget(p)
     _check(lib().mmt_sgd_momentum(_p(p), _p(g), _p(buf), p.numel(), float(lr), float(wd), float(momentum),
                                   1 if first else 0, _stream()), "mmt_sgd_momentum")
 

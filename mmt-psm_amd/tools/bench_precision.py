@@ -5,13 +5,18 @@ from maskrcnn_benchmark import _hip as hip
 import ctypes
 hip.lib()
 def cl(x): return x.contiguous(memory_format=torch.channels_last)
-class FakeFlat(object):
-    pass
+from maskrcnn_benchmark.engine.flat import flatten_model
+class OneLayer(torch.nn.Module):
+    def __init__(self, w):
+        super().__init__(); self.weight = torch.nn.Parameter(w)
 def register(w):
-    import weakref
-    f = FakeFlat(); f.planes = hip.pack_weight(w); f.plane_versions = {w.data_ptr(): w._version}; f.plane_epoch = hip.PLANES_EPOCH + 10**9
-    hip.PLANES[w.data_ptr()] = (weakref.ref(f), 0, w.numel())
-    return f
+    """w as the parameter of a flattened one-layer model, its planes pre-packed in the model's buffer -> (model, the parameter);
+    the model's planes follow the arithmetic mode only through a refresh: `remode`"""
+    m = OneLayer(w); flatten_model(m)
+    return m, m.weight
+def remode(keep, mode):
+    hip.set_conv_precision(mode)
+    if keep is not None: keep[0]._flat.refresh_planes()
 cases = [
  ("fpn_layer1 3x3 256@256^2 N2", 2,256,256,256,256,3,1,1),
  ("fpn_layer1 N8", 8,256,256,256,256,3,1,1),
@@ -31,22 +36,23 @@ for name,N,Cin,H,W,Cout,k,s,p in [("check 3x3 s1 64@24^2", 2,64,24,24,96,3,1,1),
     ref = torch.nn.functional.conv2d(x.double(), w.double(), None, s, p)
     for glds in (0, 1):
         keep = register(w) if glds else None
+        wk = keep[1].detach() if glds else w
         for mode in (0,3,2,1):
-            hip.set_conv_precision(mode)
-            y = hip.conv_forward(x,w,None,None,s,p)
+            remode(keep, mode)
+            y = hip.conv_forward(x,wk,None,None,s,p)
             err = (y.double()-ref).abs().max().item()/ref.abs().max().item()
             print("%-24s planes=%d mode %d  max err %.3e" % (name, glds, mode, err))
-        hip.PLANES.clear()
+        del keep, wk
 for name,N,Cin,H,W,Cout,k,s,p in cases:
     x = cl(torch.randn(N,Cin,H,W,device='cuda')); w = cl(torch.randn(Cout,Cin,k,k,device='cuda')*0.05)
     sc = torch.rand(Cout,device='cuda'); sh = torch.rand(Cout,device='cuda')
-    keep = register(w)
+    keep = register(w); w = keep[1].detach()
     Ho=(H+2*p-k)//s+1; Wo=(W+2*p-k)//s+1
     fl = 2.0*N*Ho*Wo*Cout*Cin*k*k
     line = "%-28s" % name
     y0 = None
     for mode in (0,3,2,1):
-        hip.set_conv_precision(mode)
+        remode(keep, mode)
         for _ in range(3): y = hip.conv_forward(x,w,sc,sh,s,p,relu=True)
         torch.cuda.synchronize()
         e0=torch.cuda.Event(enable_timing=True); e1=torch.cuda.Event(enable_timing=True)
@@ -58,5 +64,5 @@ for name,N,Cin,H,W,Cout,k,s,p in cases:
         err = (y-y0).abs().max().item()/y0.abs().max().item()
         line += " | m%d %6.3f ms %6.1f TF err %.1e" % (mode, ms, fl/ms/1e9, err)
     print(line, flush=True)
-    hip.PLANES.clear()
+    del keep, w
 hip.set_conv_precision(0)

@@ -528,7 +528,9 @@ def test_packed_weight_planes_bookkeeping(hip, restore_mode, arith):
     y_percall = fwd()  # not flattened: packed per call
     flat = flatten_model(m)
     w0 = m[0].weight
-    assert hip.PLANES[w0.data_ptr()][0]() is flat and flat.planes is not None
+    served = flat.form(w0, "bf16")   # the lookup serves the flat's planes for w0
+    assert flat.planes is not None and served is not None and served.untyped_storage().data_ptr() == flat.planes.untyped_storage().data_ptr()
+    assert hip.FLATS.get(w0.data_ptr()) is flat
     assert torch.equal(fwd(), y_percall) and close(y_percall)  # same arithmetic through the cached planes
     # (a) raw-pointer update + refresh (what FlatSGD.step / update_teacher do)
     flat.data.mul_(1.5)
@@ -546,8 +548,8 @@ def test_packed_weight_planes_bookkeeping(hip, restore_mode, arith):
     assert close(fwd())
     flat.refresh_planes()
     assert close(fwd())
-    # (d) the data-gradient planes are cached per parameter generation (H.FLIPPED): reused inside a generation, rebuilt
-    # after the parameters moved
+    # (d) the data-gradient planes are kept per parameter generation (FlatParams.form): reused inside a generation -- no pack launch,
+    # the same planes -- and re-packed IN PLACE after the parameters moved
     h = cl(torch.randn(2, 64, 20, 20))
 
     def dgrad():
@@ -560,14 +562,32 @@ def test_packed_weight_planes_bookkeeping(hip, restore_mode, arith):
         F.conv2d(xx, m[1].weight.double(), m[1].bias.double()).sum().backward()
         return xx.grad
 
-    g1 = dgrad()
-    key1 = hip.FLIPPED[m[1].weight.data_ptr()][0]
-    g2 = dgrad()
-    assert hip.FLIPPED[m[1].weight.data_ptr()][0] == key1 and torch.equal(g1, g2)
+    def served_dgrad():   # what the data-gradient launch of this arithmetic reads: (planes, scale word or None)
+        w1 = hip.nhwc(m[1].weight)
+        s = flat.form(w1, "f16_dgrad") if arith == "f16x2" else (flat.form(w1, "bf16_dgrad"), None)
+        assert s is not None and s[0] is not None
+        return s
+
+    def counted():
+        c0 = hip.C_CALLS[0]
+        g = dgrad()
+        return g, hip.C_CALLS[0] - c0
+
+    g1, c1 = counted()
+    p1, s1 = served_dgrad()
+    k0 = hip.F16_STATS["weight_pack"]
+    g2, c2 = counted()
+    g2b, c2b = counted()
+    # the first pass packed per call and registered the forms; later ones in the generation issue no pack launch
+    assert c2 < c1 and c2b == c2 and hip.F16_STATS["weight_pack"] == k0
+    assert served_dgrad()[0].data_ptr() == p1.data_ptr() and torch.equal(g1, g2) and torch.equal(g1, g2b)
+    before = (p1.clone(), None if s1 is None else s1.clone())
     flat.data.mul_(0.5)
     flat.refresh_planes()
     g3, r3 = dgrad(), dgrad_ref()
-    assert hip.FLIPPED[m[1].weight.data_ptr()][0] != key1
+    p3, s3 = served_dgrad()
+    # re-packed in place: the same planes, other contents (the fp16 planes hold w * 2^k: halving w moves the scale word instead)
+    assert p3.data_ptr() == p1.data_ptr() and not (torch.equal(p3, before[0]) and (s3 is None or torch.equal(s3, before[1])))
     assert (g3.double() - r3).abs().max().item() < 1e-5 * r3.abs().max().item()
 
 
@@ -600,11 +620,11 @@ def test_batch_pack_maxima_are_the_matrices_maxima(hip, restore_mode):
         assert flat.stat16 is not None and flat.stat16.shape[0] == len(mats) == 4
         for d, p in enumerate(mats):
             assert flat.stat16[d, 0].item() == p.detach().abs().max().item(), d
-        t = flat.__dict__.get("_flip16_table")
-        assert t is not None and len(t[3]) >= 3
-        for w, scale, planes, dims in flat._flip16_entries.values():
-            want = (w.detach() * (scale.view(-1, 1, 1, 1) if scale is not None else 1.0)).abs().max().item()
-            assert t[4][t[3][w.data_ptr()], 0].item() == want, dims
+        forms = flat.dgrad_forms("f16_dgrad")
+        assert len(forms) >= 3
+        for e in forms:
+            want = (e.w.detach() * (e.scale.view(-1, 1, 1, 1) if e.scale is not None else 1.0)).abs().max().item()
+            assert e.stat[0].item() == want, e.dims
         # the planes reproduce the layers (forward and data gradient) after the bulk re-pack
         x2 = cl(torch.randn(2, 64, 24, 24)).requires_grad_(True)
         h = x2

@@ -368,3 +368,54 @@ def test_predicted_exposed_communication_model():
     q = predict_exposed_comm([{"mbytes": 100.0, "issued_ms": 0.0}, {"mbytes": 100.0, "issued_ms": 0.0}], 0.0, world=8)
     assert abs(q["ring"]["last_arrival_ms"] - 2 * (2 * 7 / 8 * 100e6 / 153e9 * 1e3 + 0.05)) < 1e-3
     assert predict_exposed_comm(pieces, backward_end_ms=100.0)["ring"]["exposed_comm_ms"] == 0.0
+
+
+def test_loose_weight_forms_go_by_the_owners_identity():
+    """_hip.LooseForms: an entry is served to the very object it was kept for, under the stamp and scale vector it was kept with; it
+    leaves with its owner (a new object, whatever id or address it gets, never hits) and with a raw-pointer write over its source"""
+    from maskrcnn_benchmark._hip import LooseForms
+    L = LooseForms()
+    w, scale = torch.zeros(4, 4), torch.ones(4)
+    served = L.put(w, "f16", (0,), None, ("planes", "scale"), w)
+    assert L.get(w, "f16", (0,), None) is served
+    assert L.get(w, "f16", (1,), None) is None and L.get(w, "f16", (0,), scale) is None and L.get(w, "f16_dgrad", (0,), None) is None
+    assert L.get(w.detach(), "f16", (0,), None) is None          # another object over the same memory
+    L.put(w, "f16", (1,), scale, "again", w)                     # replaced in place: one entry, one finalizer's worth
+    assert L.get(w, "f16", (1,), scale) == "again" and len(L.entries) == 1
+    key = next(iter(L.entries))
+    del w
+    assert not L.entries
+    for _ in range(64):                                          # objects that come and go: ids repeat, nothing is served
+        t = torch.zeros(4, 4)
+        assert L.get(t, "f16", (1,), scale) is None
+        L.put(t, "f16", (1,), scale, "t", t)
+        if (id(t), "f16") == key:
+            break
+    del t
+    assert not L.entries
+    a, b = torch.zeros(8), torch.zeros(8)
+    L.put(a, "f32_dgrad", (0,), None, "a", a)
+    L.put(b, "f32_dgrad", (0,), None, "b", b)
+    L.forget(torch.zeros(8))                                     # somebody else's bytes
+    assert L.get(a, "f32_dgrad", (0,), None) == "a" and L.get(b, "f32_dgrad", (0,), None) == "b"
+    L.forget(a[6:])                                              # any part of a's bytes
+    assert L.get(a, "f32_dgrad", (0,), None) is None and L.get(b, "f32_dgrad", (0,), None) == "b"
+    # a training run: put -> raw-pointer write -> put, step after step, on ONE live owner.  What an earlier step served is let go,
+    # and there stays one entry and one finalizer for the owner, however many steps
+    import weakref
+    served, n_final = [], None
+    for i in range(20):
+        t = torch.zeros(3)
+        served.append(weakref.ref(t))
+        assert L.put(a, "f32_dgrad", (0,), None, t, a) is t and L.get(a, "f32_dgrad", (0,), None) is t
+        del t
+        if i % 2:
+            L.forget(a)
+        else:
+            L.forget()                                           # (a switch of the arithmetic lets everything go)
+        assert L.get(a, "f32_dgrad", (0,), None) is None and served[-1]() is None
+        n_final = len(weakref.finalize._registry) if n_final is None else n_final
+        assert len(weakref.finalize._registry) == n_final and len(L.entries) == 2
+    assert all(r() is None for r in served)
+    del a, b
+    assert not L.entries
