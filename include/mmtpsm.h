@@ -704,6 +704,48 @@ int mmt_mask_transition_positions(const uint64_t* words, int n, int H, int W, co
 int mmt_mask_pair_intersections(const uint64_t* dwords, const int32_t* drec, int m, const uint64_t* gwords,
                                 const int32_t* grec, int n, int H, int W, int32_t* inter, void* stream);
 
+/* ---------------------------------------------------------------- deterministic mode (csrc/ordered.hip, csrc/ordered.h)
+ * Same inputs, same build -> the same bits, run to run: every sum whose order the float atomics of the default kernels leave to
+ * timing has a form here that adds in an order fixed by the shapes alone -- block partials stored to a caller's workspace, then a
+ * second small launch that adds them in block order (the reference inherits the same run-to-run variation from ATen's atomics:
+ * cuda/ROIAlign_cuda.cu:177-254, index_put_ with accumulate).  The default entry points and their launches are unchanged; the host
+ * side (maskrcnn_benchmark/_hip.py: set_deterministic) routes to the forms below.
+ * mmt_set_deterministic: the library-wide flag.  Its one effect inside the library: mmt_rpn_loss then expects `sums` to be
+ * 8 + 3 * MMT_RPN_LOSS_MAX_BLOCKS floats (sums [0:3], the caller's `out` may sit at [4:6], block partials from [8]) and adds the
+ * partials in block order.  Always returns 0.  mmt_get_deterministic: the flag. */
+#define MMT_COLSUM_MAX_BLOCKS 256      /* mmt_colsum_ordered: ws = MMT_COLSUM_MAX_BLOCKS * C floats */
+#define MMT_MASK_BCE_WS 2048           /* mmt_mask_bce_ordered: MMT_MASK_BCE_WS floats (its block limit) */
+#define MMT_MGD_MAX_BLOCKS 4096        /* mmt_mgd_level_forward_ordered: MMT_MGD_MAX_BLOCKS * (nt + 1); views: * (ns * nt + 1) */
+#define MMT_RPN_LOSS_MAX_BLOCKS 1024
+#define MMT_BOX_LOSS_MAX_BLOCKS 256    /* mmt_box_loss_ordered: 2 * MMT_BOX_LOSS_MAX_BLOCKS */
+int mmt_set_deterministic(int on);
+int mmt_get_deterministic(void);
+/* mmt_roi_align_backward with a fixed summation order: the tile-gather kernel of mmt_roi_align_backward_dense without the
+ * environment gate, plus bit l of accumulate_mask: level l computes grad_feat[l] = grad_feat[l] + s, s the tile's fixed-order sum
+ * (a gradient that lands in a buffer other consumers have added to; tiles no ROI reaches are left alone); a level without its
+ * bit is written, zeros included.  Every element has exactly one owner either way.  Returns 1 and touches nothing for calls it
+ * does not take: sampling_ratio != 2, C % 64 != 0, C > 256, K > 8192. */
+int mmt_roi_align_backward_ordered(const mmt_pyramid* pyr /*[host]*/, const float* rois, const int32_t* levels, int K, int PH,
+                                   int PW, int sampling_ratio, const float* grad_out, int accumulate_mask, void* stream);
+/* mmt_colsum in a fixed order: stage one writes per-block partial sums [blocks][C] to ws (rows per block and the block count are
+ * functions of M alone, blocks <= MMT_COLSUM_MAX_BLOCKS), stage two adds a column's partials in block order and accumulates into
+ * out.  Any C >= 1, M >= 0. */
+int mmt_colsum_ordered(const float* dy, int M, int C, float* out, float* ws, void* stream);
+/* the loss entry points with their scalar sums in block order: arguments and results of the entry point of the same name, plus
+ * the workspace (sizes above; never NULL).  Gradients are those of the default entry points bit for bit.  mmt_box_loss_ordered
+ * stands for both mmt_box_loss (n_rows NULL) and mmt_box_loss_rows; mmt_ciam_bwd_ordered: ws = n floats. */
+int mmt_mask_bce_ordered(const float* logits, const int32_t* labels, const float* targets, int P, int HW, int NC,
+                         float grad_scale, float* loss, float* grad, float* ws, void* stream);
+int mmt_mgd_level_forward_ordered(const float* s, const mmt_mgd_teachers* T /*[host]*/, const float* m, int N, int H, int W,
+                                  int C, float* acc, float* ws, void* stream);
+int mmt_mgd_views_forward_ordered(const mmt_mgd_students* S /*[host]*/, const mmt_mgd_teachers* T /*[host]*/, const float* m,
+                                  int N, int H, int W, int C, float* acc, float* ws, void* stream);
+int mmt_box_loss_ordered(const float* logits, const float* breg, const int64_t* labels, const float* regt, int R, int NC,
+                         const int64_t* n_rows /*or NULL*/, float* out, float* dlogits, float* dbreg, float* ws, void* stream);
+int mmt_ciam_bwd_ordered(const float* x, const int64_t* group, int n, int C, int HW, int max_group, const float* gamma,
+                         const float* A, const int* J, const float* dout, float* T, float* R, float* dx, float* dgamma, float* ws,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,13 +7,17 @@
 //   psm_rows     <- box_head/loss.py:185-237,267-287,311-315  evaluatePSM / cls_loss / sharpen
 //   psm_variance <- box_head/loss.py:164-173,191-194  std over the K teacher views of softmax probs
 #include "common.h"
+#include "ordered.h"
+// Deterministic mode (include/mmtpsm.h: mmt_set_deterministic): every reducing kernel below takes a workspace `ws`.  NULL: the block's
+// partial sums meet in float atomics, as ever.  Given: the block stores them at ws[block * nv + v] and ordered_finish adds them in
+// block order (csrc/ordered.h).
 
 // ----------------------------------------------------------------------------- mask BCE
 __global__ __launch_bounds__(256) void mask_bce_kernel(const float* __restrict__ logits,
                                                        const int* __restrict__ labels,
                                                        const float* __restrict__ tgt, long total, int HW, int NC,
                                                        float inv_n, float gscale, float* __restrict__ loss,
-                                                       float* __restrict__ grad) {
+                                                       float* __restrict__ grad, float* __restrict__ ws) {
   float part = 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int p = (int)(i / HW);
@@ -29,19 +33,32 @@ __global__ __launch_bounds__(256) void mask_bce_kernel(const float* __restrict__
   __shared__ float red[4];
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) * inv_n);
+  if (threadIdx.x == 0) {
+    const float v = (red[0] + red[1] + red[2] + red[3]) * inv_n;
+    if (ws) ws[blockIdx.x] = v; else atomicAdd(loss, v);
+  }
+}
+
+static int mask_bce_launch(const float* logits, const int32_t* labels, const float* targets, int P, int HW, int NC,
+                           float grad_scale, float* loss, float* grad, float* ws, void* stream) {
+  const long total = (long)P * HW;
+  if (total == 0) return 0;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > MMT_MASK_BCE_WS) blocks = MMT_MASK_BCE_WS;
+  hipLaunchKernelGGL(mask_bce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, labels, targets,
+                     total, HW, NC, 1.f / (float)total, grad_scale, loss, grad, ws);
+  MMT_LAUNCH_CHECK();
+  return ws ? ordered_finish(ws, blocks, 1, loss, (hipStream_t)stream) : 0;
 }
 
 extern "C" int mmt_mask_bce(const float* logits, const int32_t* labels, const float* targets, int P, int HW,
                             int NC, float grad_scale, float* loss, float* grad, void* stream) {
-  const long total = (long)P * HW;
-  if (total == 0) return 0;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(mask_bce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, labels, targets,
-                     total, HW, NC, 1.f / (float)total, grad_scale, loss, grad);
-  MMT_LAUNCH_CHECK();
-  return 0;
+  return mask_bce_launch(logits, labels, targets, P, HW, NC, grad_scale, loss, grad, nullptr, stream);
+}
+extern "C" int mmt_mask_bce_ordered(const float* logits, const int32_t* labels, const float* targets, int P, int HW,
+                                    int NC, float grad_scale, float* loss, float* grad, float* ws, void* stream) {
+  if (!ws) return MMT_EINVAL;
+  return mask_bce_launch(logits, labels, targets, P, HW, NC, grad_scale, loss, grad, ws, stream);
 }
 
 // ----------------------------------------------------------------------------- MGD
@@ -54,7 +71,8 @@ struct MgdT {
 template <bool BWD>
 __global__ __launch_bounds__(256) void mgd_kernel(const float* __restrict__ s, MgdT T, const float* __restrict__ m,
                                                   long npix, int W, int C4, float* __restrict__ acc,
-                                                  const float* __restrict__ coef, float* __restrict__ grad) {
+                                                  const float* __restrict__ coef, float* __restrict__ grad,
+                                                  float* __restrict__ ws) {
   // one thread per (pixel, float4 of channels)
   float num[8];
 #pragma unroll
@@ -105,14 +123,16 @@ __global__ __launch_bounds__(256) void mgd_kernel(const float* __restrict__ s, M
     if (threadIdx.x < 9) {
       const int k = threadIdx.x;
       const float v = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-      if (k == 8) atomicAdd(acc + T.nt, v);
-      else if (k < T.nt) atomicAdd(acc + k, v);
+      const int idx = k == 8 ? T.nt : k;
+      if (k == 8 || k < T.nt) {
+        if (ws) ws[(long)blockIdx.x * (T.nt + 1) + idx] = v; else atomicAdd(acc + idx, v);
+      }
     }
   }
 }
 
 static int mgd_launch(bool bwd, const float* s, const mmt_mgd_teachers* T, const float* m, int N, int H, int W,
-                      int C, float* acc, const float* coef, float* grad, void* stream) {
+                      int C, float* acc, const float* coef, float* grad, void* stream, float* ws = nullptr) {
   if (!T || T->nt < 1 || T->nt > 8 || (C & 3)) return MMT_EINVAL;
   MgdT q;
   for (int i = 0; i < 8; i++) { q.t[i] = T->t[i < T->nt ? i : 0]; q.flip[i] = T->flip[i < T->nt ? i : 0]; }
@@ -121,20 +141,25 @@ static int mgd_launch(bool bwd, const float* s, const mmt_mgd_teachers* T, const
   const long total = npix * (C / 4);
   if (total == 0) return 0;
   int blocks = (int)((total + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
+  if (blocks > MMT_MGD_MAX_BLOCKS) blocks = MMT_MGD_MAX_BLOCKS;
   if (bwd)
     hipLaunchKernelGGL(mgd_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, s, q, m, npix, W, C / 4,
-                       acc, coef, grad);
+                       acc, coef, grad, nullptr);
   else
     hipLaunchKernelGGL(mgd_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, s, q, m, npix, W, C / 4,
-                       acc, coef, grad);
+                       acc, coef, grad, ws);
   MMT_LAUNCH_CHECK();
-  return 0;
+  return (ws && !bwd) ? ordered_finish(ws, blocks, q.nt + 1, acc, (hipStream_t)stream) : 0;
 }
 
 extern "C" int mmt_mgd_level_forward(const float* s, const mmt_mgd_teachers* T, const float* m, int N, int H, int W,
                                      int C, float* acc, void* stream) {
   return mgd_launch(false, s, T, m, N, H, W, C, acc, nullptr, nullptr, stream);
+}
+extern "C" int mmt_mgd_level_forward_ordered(const float* s, const mmt_mgd_teachers* T, const float* m, int N, int H, int W,
+                                             int C, float* acc, float* ws, void* stream) {
+  if (!ws) return MMT_EINVAL;
+  return mgd_launch(false, s, T, m, N, H, W, C, acc, nullptr, nullptr, stream, ws);
 }
 extern "C" int mmt_mgd_level_backward(const float* s, const mmt_mgd_teachers* T, const float* m, int N, int H,
                                       int W, int C, const float* coef, float* grad_s, void* stream) {
@@ -157,7 +182,7 @@ struct MgdS {
 template <bool BWD, int S>
 __global__ __launch_bounds__(256) void mgd_views_kernel(MgdS Sv, MgdT T, const float* __restrict__ m, long rows, int W,
                                                         int C4, float* __restrict__ acc, const float* __restrict__ coef,
-                                                        float* __restrict__ grad) {
+                                                        float* __restrict__ grad, float* __restrict__ ws) {
   const int nt = T.nt;
   const int Wh = (W + 1) >> 1;
   float num[S][MGD_MAX_T];
@@ -253,11 +278,10 @@ __global__ __launch_bounds__(256) void mgd_views_kernel(MgdS Sv, MgdT T, const f
     __syncthreads();
     for (int q = threadIdx.x; q <= S * MGD_MAX_T; q += 256) {
       const float v = red[0][q] + red[1][q] + red[2][q] + red[3][q];
-      if (q == S * MGD_MAX_T) {
-        atomicAdd(acc + S * nt, v);
-      } else {
-        const int j = q / MGD_MAX_T, k = q - j * MGD_MAX_T;
-        if (k < nt) atomicAdd(acc + j * nt + k, v);
+      const int j = q / MGD_MAX_T, k = q - j * MGD_MAX_T;
+      const int idx = q == S * MGD_MAX_T ? S * nt : j * nt + k;
+      if (q == S * MGD_MAX_T || k < nt) {
+        if (ws) ws[(long)blockIdx.x * (S * nt + 1) + idx] = v; else atomicAdd(acc + idx, v);
       }
     }
   }
@@ -265,12 +289,12 @@ __global__ __launch_bounds__(256) void mgd_views_kernel(MgdS Sv, MgdT T, const f
 
 template <bool BWD, int S>
 static void mgd_views_go(int blocks, hipStream_t st, const MgdS& sv, const MgdT& q, const float* m, long rows, int W, int C4,
-                         float* acc, const float* coef, float* grad) {
-  hipLaunchKernelGGL((mgd_views_kernel<BWD, S>), dim3(blocks), dim3(256), 0, st, sv, q, m, rows, W, C4, acc, coef, grad);
+                         float* acc, const float* coef, float* grad, float* ws) {
+  hipLaunchKernelGGL((mgd_views_kernel<BWD, S>), dim3(blocks), dim3(256), 0, st, sv, q, m, rows, W, C4, acc, coef, grad, BWD ? nullptr : ws);
 }
 
 static int mgd_views_launch(bool bwd, const mmt_mgd_students* Sv, const mmt_mgd_teachers* T, const float* m, int N, int H,
-                            int W, int C, float* acc, const float* coef, float* grad, void* stream) {
+                            int W, int C, float* acc, const float* coef, float* grad, void* stream, float* ws = nullptr) {
   if (!Sv || !T || Sv->ns < 1 || Sv->ns > MGD_MAX_S || T->nt < 1 || T->nt > MGD_MAX_T || Sv->ns * T->nt > MGD_MAX_TERMS ||
       (C & 3) || N < 0 || H < 0 || W < 0)
     return MMT_EINVAL;
@@ -286,26 +310,31 @@ static int mgd_views_launch(bool bwd, const mmt_mgd_students* Sv, const mmt_mgd_
   const long total = rows * ((W + 1) / 2) * (C / 4);
   if (total == 0) return 0;
   int blocks = (int)((total + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
+  if (blocks > MMT_MGD_MAX_BLOCKS) blocks = MMT_MGD_MAX_BLOCKS;
   hipStream_t st = (hipStream_t)stream;
   const int C4 = C / 4;
   switch (Sv->ns * 2 + (bwd ? 1 : 0)) {
-    case 2: mgd_views_go<false, 1>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
-    case 3: mgd_views_go<true, 1>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
-    case 4: mgd_views_go<false, 2>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
-    case 5: mgd_views_go<true, 2>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
-    case 6: mgd_views_go<false, 3>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
-    case 7: mgd_views_go<true, 3>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
-    case 8: mgd_views_go<false, 4>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
-    default: mgd_views_go<true, 4>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad); break;
+    case 2: mgd_views_go<false, 1>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad, ws); break;
+    case 3: mgd_views_go<true, 1>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad, ws); break;
+    case 4: mgd_views_go<false, 2>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad, ws); break;
+    case 5: mgd_views_go<true, 2>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad, ws); break;
+    case 6: mgd_views_go<false, 3>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad, ws); break;
+    case 7: mgd_views_go<true, 3>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad, ws); break;
+    case 8: mgd_views_go<false, 4>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad, ws); break;
+    default: mgd_views_go<true, 4>(blocks, st, sv, q, m, rows, W, C4, acc, coef, grad, ws); break;
   }
   MMT_LAUNCH_CHECK();
-  return 0;
+  return (ws && !bwd) ? ordered_finish(ws, blocks, Sv->ns * q.nt + 1, acc, st) : 0;
 }
 
 extern "C" int mmt_mgd_views_forward(const mmt_mgd_students* S, const mmt_mgd_teachers* T, const float* m, int N, int H, int W,
                                      int C, float* acc, void* stream) {
   return mgd_views_launch(false, S, T, m, N, H, W, C, acc, nullptr, nullptr, stream);
+}
+extern "C" int mmt_mgd_views_forward_ordered(const mmt_mgd_students* S, const mmt_mgd_teachers* T, const float* m, int N, int H,
+                                             int W, int C, float* acc, float* ws, void* stream) {
+  if (!ws) return MMT_EINVAL;
+  return mgd_views_launch(false, S, T, m, N, H, W, C, acc, nullptr, nullptr, stream, ws);
 }
 extern "C" int mmt_mgd_views_backward(const mmt_mgd_students* S, const mmt_mgd_teachers* T, const float* m, int N, int H,
                                       int W, int C, const float* coef, float* grad_s, void* stream) {
@@ -451,7 +480,8 @@ extern "C" int mmt_psm_variance(const float* teacher, int Kaug, int R, int NC, i
 __global__ __launch_bounds__(256) void rpn_loss_sums_kernel(const float* __restrict__ obj, const float4* __restrict__ reg,
                                                             const float* __restrict__ labels, const float4* __restrict__ regt,
                                                             const uint8_t* __restrict__ pos, const uint8_t* __restrict__ neg,
-                                                            long R, float beta, float* __restrict__ sums) {
+                                                            long R, float beta, float* __restrict__ sums,
+                                                            float* __restrict__ ws) {
   float cnt = 0.f, bce = 0.f, box = 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < R; i += (long)gridDim.x * 256) {
     const bool p = pos[i] != 0, s = p || neg[i] != 0;
@@ -479,7 +509,8 @@ __global__ __launch_bounds__(256) void rpn_loss_sums_kernel(const float* __restr
   __syncthreads();
   if (threadIdx.x < 3) {
     const float v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-    if (v != 0.f) atomicAdd(sums + threadIdx.x, v);
+    if (ws) ws[(long)blockIdx.x * 3 + threadIdx.x] = v;
+    else if (v != 0.f) atomicAdd(sums + threadIdx.x, v);
   }
 }
 
@@ -527,10 +558,16 @@ extern "C" int mmt_rpn_loss(const float* obj, const float* reg, const float* lab
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(sums, 0, 3 * sizeof(float), s) != hipSuccess) return MMT_EINVAL;
   int blocks = (int)((R + 255) / 256);
-  if (blocks > 1024) blocks = 1024;
+  if (blocks > MMT_RPN_LOSS_MAX_BLOCKS) blocks = MMT_RPN_LOSS_MAX_BLOCKS;
+  // deterministic mode: `sums` is the longer workspace of the header; the block partials live behind its first 8 floats
+  float* const ws = mmt_get_deterministic() ? sums + 8 : nullptr;
   hipLaunchKernelGGL(rpn_loss_sums_kernel, dim3(blocks), dim3(256), 0, s, obj, (const float4*)reg, labels, (const float4*)regt, pos,
-                     neg, R, beta, sums);
+                     neg, R, beta, sums, ws);
   MMT_LAUNCH_CHECK();
+  if (ws) {
+    const int e = ordered_finish(ws, blocks, 3, sums, s);
+    if (e) return e;
+  }
   hipLaunchKernelGGL(rpn_loss_grad_kernel, dim3(blocks), dim3(256), 0, s, obj, (const float4*)reg, labels, (const float4*)regt, pos,
                      neg, R, beta, sums, out, dobj, (float4*)dreg);
   MMT_LAUNCH_CHECK();
@@ -543,7 +580,8 @@ extern "C" int mmt_rpn_loss(const float* obj, const float* reg, const float* lab
 __global__ __launch_bounds__(256) void box_loss_kernel(const float* __restrict__ logits, const float* __restrict__ breg,
                                                        const int64_t* __restrict__ labels, const float* __restrict__ regt, int R,
                                                        int NC, float* __restrict__ out, float* __restrict__ dlogits,
-                                                       float* __restrict__ dbreg, const int64_t* __restrict__ n_rows) {
+                                                       float* __restrict__ dbreg, const int64_t* __restrict__ n_rows,
+                                                       float* __restrict__ ws) {
   // n_rows (device, or null = R): the rows that count -- fixed-capacity lists carry rows labelled -1 behind an image's sampled set
   // (box_head.py::subsample_fixed); those contribute nothing and are not rows of the mean
   const float inv = 1.f / (n_rows ? fmaxf((float)*n_rows, 1.f) : (float)R);
@@ -581,19 +619,33 @@ __global__ __launch_bounds__(256) void box_loss_kernel(const float* __restrict__
     red[threadIdx.x >> 6][1] = box;
   }
   __syncthreads();
-  if (threadIdx.x < 2) atomicAdd(out + threadIdx.x, (red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]) * inv);
+  if (threadIdx.x < 2) {
+    const float v = (red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]) * inv;
+    if (ws) ws[blockIdx.x * 2 + threadIdx.x] = v; else atomicAdd(out + threadIdx.x, v);
+  }
 }
 
-extern "C" int mmt_box_loss_rows(const float* logits, const float* breg, const int64_t* labels, const float* regt, int R, int NC,
-                                 const int64_t* n_rows, float* out, float* dlogits, float* dbreg, void* stream) {
+static int box_loss_launch(const float* logits, const float* breg, const int64_t* labels, const float* regt, int R, int NC,
+                           const int64_t* n_rows, float* out, float* dlogits, float* dbreg, float* ws, void* stream) {
   if (!logits || !breg || !labels || !regt || !out || !dlogits || !dbreg || R < 1 || NC < 2) return MMT_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(out, 0, 2 * sizeof(float), s) != hipSuccess) return MMT_EINVAL;
   int blocks = (R + 255) / 256;
-  if (blocks > 256) blocks = 256;
-  hipLaunchKernelGGL(box_loss_kernel, dim3(blocks), dim3(256), 0, s, logits, breg, labels, regt, R, NC, out, dlogits, dbreg, n_rows);
+  if (blocks > MMT_BOX_LOSS_MAX_BLOCKS) blocks = MMT_BOX_LOSS_MAX_BLOCKS;
+  hipLaunchKernelGGL(box_loss_kernel, dim3(blocks), dim3(256), 0, s, logits, breg, labels, regt, R, NC, out, dlogits, dbreg, n_rows, ws);
   MMT_LAUNCH_CHECK();
-  return 0;
+  return ws ? ordered_finish(ws, blocks, 2, out, s) : 0;
+}
+
+extern "C" int mmt_box_loss_rows(const float* logits, const float* breg, const int64_t* labels, const float* regt, int R, int NC,
+                                 const int64_t* n_rows, float* out, float* dlogits, float* dbreg, void* stream) {
+  return box_loss_launch(logits, breg, labels, regt, R, NC, n_rows, out, dlogits, dbreg, nullptr, stream);
+}
+
+extern "C" int mmt_box_loss_ordered(const float* logits, const float* breg, const int64_t* labels, const float* regt, int R, int NC,
+                                    const int64_t* n_rows, float* out, float* dlogits, float* dbreg, float* ws, void* stream) {
+  if (!ws) return MMT_EINVAL;
+  return box_loss_launch(logits, breg, labels, regt, R, NC, n_rows, out, dlogits, dbreg, ws, stream);
 }
 
 extern "C" int mmt_box_loss(const float* logits, const float* breg, const int64_t* labels, const float* regt, int R, int NC,

@@ -6,6 +6,7 @@
 // channels x 196 pixels): they are latency-bound, not matrix-bound -- fp32 FMAs on the vector ALU, operands staged in LDS,
 // one workgroup per (class, head) / per row block; nothing here is shaped for the MFMA units on purpose.
 #include "common.h"
+#include "ordered.h"
 
 namespace {
 
@@ -369,7 +370,8 @@ __global__ __launch_bounds__(256) void ciam_fwd_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void ciam_bwd_rows_kernel(const float* __restrict__ x, const int64_t* __restrict__ grp, int n, int C,
                                                             int HW, const float* __restrict__ gamma, const float* __restrict__ A,
                                                             const float* __restrict__ dout, float* __restrict__ T,
-                                                            float* __restrict__ R, float* __restrict__ dgamma) {
+                                                            float* __restrict__ R, float* __restrict__ dgamma,
+                                                            float* __restrict__ ws) {
   extern __shared__ float lds[];
   const int i = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   __shared__ int s_lo, s_hi;
@@ -397,7 +399,9 @@ __global__ __launch_bounds__(256) void ciam_bwd_rows_kernel(const float* __restr
   __syncthreads();
   const float dot = s_red[0] + s_red[1] + s_red[2] + s_red[3];
   const float gm = gamma[0];
-  if (tid == 0) atomicAdd(dgamma, dot);
+  if (tid == 0) {   // (ws: deterministic mode, the rows' shares are added in row order by ordered_finish)
+    if (ws) ws[i] = dot; else atomicAdd(dgamma, dot);
+  }
   __syncthreads();
   float rs = 0.f;
   for (int j = tid; j < n; j += 256) {
@@ -506,9 +510,9 @@ extern "C" int mmt_ciam_fwd(const float* x, const int64_t* group, int n, int C, 
   return 0;
 }
 
-extern "C" int mmt_ciam_bwd(const float* x, const int64_t* group, int n, int C, int HW, int max_group, const float* gamma,
-                            const float* A, const int* J, const float* dout, float* T, float* R, float* dx, float* dgamma,
-                            void* stream) {
+static int ciam_bwd_launch(const float* x, const int64_t* group, int n, int C, int HW, int max_group, const float* gamma,
+                           const float* A, const int* J, const float* dout, float* T, float* R, float* dx, float* dgamma,
+                           float* ws, void* stream) {
   if (!x || !group || !gamma || !A || !J || !dout || !T || !R || !dx || !dgamma || n < 1 || C < 1 || C > CI_MAXC || HW < 1 ||
       max_group < 1 || max_group > CI_MAXG)
     return MMT_EINVAL;
@@ -516,10 +520,27 @@ extern "C" int mmt_ciam_bwd(const float* x, const int64_t* group, int n, int C, 
   if (lds1 > 64 * 1024 || lds2 > 64 * 1024) return MMT_EINVAL;
   if (hipMemsetAsync(dgamma, 0, sizeof(float), (hipStream_t)stream) != hipSuccess) return MMT_EINVAL;
   hipLaunchKernelGGL(ciam_bwd_rows_kernel, dim3(n), dim3(256), lds1, (hipStream_t)stream, x, group, n, C, HW, gamma, A, dout, T, R,
-                     dgamma);
+                     dgamma, ws);
   MMT_LAUNCH_CHECK();
+  if (ws) {
+    const int e = ordered_finish(ws, n, 1, dgamma, (hipStream_t)stream);
+    if (e) return e;
+  }
   hipLaunchKernelGGL(ciam_bwd_dx_kernel, dim3(n), dim3(256), lds2, (hipStream_t)stream, x, group, n, C, HW, gamma, A, J, T, R, dout,
                      dx);
   MMT_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int mmt_ciam_bwd(const float* x, const int64_t* group, int n, int C, int HW, int max_group, const float* gamma,
+                            const float* A, const int* J, const float* dout, float* T, float* R, float* dx, float* dgamma,
+                            void* stream) {
+  return ciam_bwd_launch(x, group, n, C, HW, max_group, gamma, A, J, dout, T, R, dx, dgamma, nullptr, stream);
+}
+
+extern "C" int mmt_ciam_bwd_ordered(const float* x, const int64_t* group, int n, int C, int HW, int max_group, const float* gamma,
+                                    const float* A, const int* J, const float* dout, float* T, float* R, float* dx, float* dgamma,
+                                    float* ws, void* stream) {
+  if (!ws) return MMT_EINVAL;
+  return ciam_bwd_launch(x, group, n, C, HW, max_group, gamma, A, J, dout, T, R, dx, dgamma, ws, stream);
 }

@@ -190,7 +190,9 @@ struct TileMap { int first[5]; int tx[4], ty[4]; };   // first[l] = index of lev
 
 __global__ __launch_bounds__(256) void roi_align_bwd_tiles_kernel(Pyr p, TileMap tm, const float* __restrict__ rois,
                                                                   const int* __restrict__ levels, int K, int PH, int PW,
-                                                                  const float* __restrict__ gout) {
+                                                                  const float* __restrict__ gout, int accmask) {
+  // accmask (mmt_roi_align_backward_ordered): bit l set = level l ACCUMULATES -- grad = grad + s with s the tile's fixed-order sum;
+  // every element still has its one owner, so the read-modify-write is plain
   extern __shared__ __attribute__((aligned(16))) float acc[];   // [64 pixels][C] then the ROI list (K ints) and 8 counters
   const int C = p.C;
   int* const list = (int*)(acc + 64 * C);
@@ -231,7 +233,9 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tiles_kernel(Pyr p, TileMap
     __syncthreads();
   }
   const int npx = 64 * C / 4;
+  const bool accum = (accmask >> lv) & 1;
   if (n == 0) {
+    if (accum) return;   // (nothing reaches the tile: what is there stays)
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     for (int i = tid; i < npx; i += 256) {
       const int pix = i / (C / 4), y = ty0 + (pix >> 3), x = tx0 + (pix & 7);
@@ -325,7 +329,10 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tiles_kernel(Pyr p, TileMap
   __syncthreads();
   for (int i = tid; i < npx; i += 256) {
     const int pix = i / (C / 4), y = ty0 + (pix >> 3), x = tx0 + (pix & 7);
-    if (y < H && x < W) *(f32x4*)(p.grad[lv] + (((long)b * H + y) * W + x) * C + (i % (C / 4)) * 4) = ((const f32x4*)acc)[i];
+    if (y < H && x < W) {
+      f32x4* const dst = (f32x4*)(p.grad[lv] + (((long)b * H + y) * W + x) * C + (i % (C / 4)) * 4);
+      *dst = accum ? *dst + ((const f32x4*)acc)[i] : ((const f32x4*)acc)[i];
+    }
   }
 }
 
@@ -388,16 +395,17 @@ extern "C" int mmt_roi_align_backward(const mmt_pyramid* pyr, const float* rois,
   return 0;
 }
 
-extern "C" int mmt_roi_align_backward_dense(const mmt_pyramid* pyr, const float* rois, const int32_t* levels, int K,
-                                            int PH, int PW, int sampling_ratio, const float* grad_out, void* stream) {
+// the tile-gather launch behind mmt_roi_align_backward_dense and mmt_roi_align_backward_ordered; 1 = not taken, nothing touched
+static int bwd_tiles_launch(const mmt_pyramid* pyr, const float* rois, const int32_t* levels, int K, int PH, int PW,
+                            int sampling_ratio, const float* grad_out, int accmask, bool gated, void* stream) {
   Pyr q;
   int e = fill(q, pyr);
   if (e) return e;
   // opt-in (MMT_ROI_BWD_DENSE=1): repeatable bit for bit, but proposals cluster on the objects -- a tile under 100 ROIs keeps one CU
   // busy for 0.4-6 ms while the scatter kernel spreads the same additions over the L2 atomic units of the whole chip in 0.2 ms
   // (profiles/r05_history.md): the step is 0.3 ms slower with it
-  const char* env = getenv("MMT_ROI_BWD_DENSE");
-  if (sampling_ratio != 2 || (q.C & 63) || q.C > 256 || K > 8192 || PH < 1 || PW < 1 || !env || !atoi(env)) return 1;   // not taken
+  const char* env = gated ? getenv("MMT_ROI_BWD_DENSE") : nullptr;
+  if (sampling_ratio != 2 || (q.C & 63) || q.C > 256 || K < 0 || K > 8192 || PH < 1 || PW < 1 || (gated && (!env || !atoi(env)))) return 1;   // not taken
   TileMap tm;
   int tiles = 0;
   for (int l = 0; l < 4; l++) {
@@ -418,7 +426,21 @@ extern "C" int mmt_roi_align_backward_dense(const mmt_pyramid* pyr, const float*
     if (er != hipSuccess) return (int)er;
     done = true;
   }
-  hipLaunchKernelGGL(roi_align_bwd_tiles_kernel, dim3(tiles), dim3(256), lds, (hipStream_t)stream, q, tm, rois, levels, K, PH, PW, grad_out);
+  hipLaunchKernelGGL(roi_align_bwd_tiles_kernel, dim3(tiles), dim3(256), lds, (hipStream_t)stream, q, tm, rois, levels, K, PH, PW, grad_out, accmask);
   MMT_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int mmt_roi_align_backward_dense(const mmt_pyramid* pyr, const float* rois, const int32_t* levels, int K,
+                                            int PH, int PW, int sampling_ratio, const float* grad_out, void* stream) {
+  return bwd_tiles_launch(pyr, rois, levels, K, PH, PW, sampling_ratio, grad_out, 0, true, stream);
+}
+
+// deterministic mode's form: no environment gate, and a per-level accumulate flag (bit l of accumulate_mask) for levels whose
+// gradient lands in a buffer that already holds other consumers' contributions
+extern "C" int mmt_roi_align_backward_ordered(const mmt_pyramid* pyr, const float* rois, const int32_t* levels, int K,
+                                              int PH, int PW, int sampling_ratio, const float* grad_out, int accumulate_mask,
+                                              void* stream) {
+  if (accumulate_mask < 0 || accumulate_mask > 15) return MMT_EINVAL;
+  return bwd_tiles_launch(pyr, rois, levels, K, PH, PW, sampling_ratio, grad_out, accumulate_mask, false, stream);
 }

@@ -188,6 +188,17 @@ _SIGS = {
     "mmt_mask_transition_counts": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_mask_transition_positions": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "mmt_mask_pair_intersections": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "mmt_set_deterministic": [c_int],
+    "mmt_get_deterministic": [],
+    "mmt_roi_align_backward_ordered": [ctypes.POINTER(Pyramid), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
+    "mmt_colsum_ordered": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "mmt_mask_bce_ordered": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mmt_mgd_level_forward_ordered": [c_void_p, ctypes.POINTER(MgdTeachers), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "mmt_mgd_views_forward_ordered": [ctypes.POINTER(MgdStudents), ctypes.POINTER(MgdTeachers), c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                      c_void_p, c_void_p],
+    "mmt_box_loss_ordered": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mmt_ciam_bwd_ordered": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p],
 }
 
 _lib = None
@@ -384,6 +395,12 @@ def _site_ok(site, x, count=True):
     ent = _SITES.get(site)
     if ent is None:
         ent = _SITES[site] = [True, None]
+    if _DET:
+        # deterministic mode: WHEN a pool's statistics reach the host is a matter of timing, and the answer picks the kernel -- the
+        # site keeps the state it has, nothing is polled or queued; the kernels' on-device range guard covers accuracy alone
+        if not ent[0] and count:
+            F16_STATS["fallback"] = F16_STATS.get("fallback", 0) + 1
+        return ent[0]
     pend = ent[1]
     if pend is not None:
         pool, gen = pend.pool, pend.gen
@@ -727,11 +744,80 @@ def f16_weight_planes(w, flip_scale=None, flipped=False):
 
 def set_bf16_storage(on):
     global _BF16_STORAGE
+    if on and _DET:
+        raise NotImplementedError("bf16 activation storage is not offered in deterministic mode (its kernels' summation orders were "
+                                  "never examined): set_deterministic(False)")
     _BF16_STORAGE = bool(on)
 
 
 def bf16_storage():
     return _BF16_STORAGE and get_conv_precision() == 1
+
+
+# ---- deterministic mode (include/mmtpsm.h: mmt_set_deterministic).  Process-wide and opt-in: with it, the same seed,
+# build, weights and batches give bit-identical training state run to run on one device.  Every sum whose order the default kernels
+# leave to timing goes through a fixed-order form (ROIAlign backward, bias gradients, loss scalars, CIAM's gamma), the lagged
+# host-side site test is frozen, torch's own deterministic algorithms are switched on, and the configurations whose unordered sums
+# have no ordered form yet refuse.  Off: nothing here is consulted beyond one boolean per call.
+_DET = os.environ.get("MMT_DETERMINISTIC", "0") != "0"
+_DET_TORCH = None   # torch's switches as set_deterministic(True) found them: (deterministic algorithms, warn only, fill uninitialised memory)
+COLSUM_MAX_BLOCKS, MASK_BCE_WS, MGD_MAX_BLOCKS, RPN_LOSS_MAX_BLOCKS, BOX_LOSS_MAX_BLOCKS = 256, 2048, 4096, 1024, 256   # include/mmtpsm.h
+
+
+def _det_torch(on):
+    global _DET_TORCH
+    from torch.utils import deterministic as td
+    if on:
+        if _DET_TORCH is None:
+            _DET_TORCH = (torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled(),
+                          td.fill_uninitialized_memory)
+        torch.use_deterministic_algorithms(True)
+        # (every buffer handed to a kernel here is fully written by it; filling each torch.empty first would add a launch per call)
+        td.fill_uninitialized_memory = False
+    elif _DET_TORCH is not None:
+        torch.use_deterministic_algorithms(_DET_TORCH[0], warn_only=_DET_TORCH[1])
+        td.fill_uninitialized_memory = _DET_TORCH[2]
+        _DET_TORCH = None
+
+
+def set_deterministic(on):
+    """True: deterministic mode (also torch.use_deterministic_algorithms(True)); False: the default kernels, and torch's switches back
+    to what set_deterministic(True) found.  MMT_DETERMINISTIC=1 in the environment switches it on at import."""
+    global _DET
+    on = bool(on)
+    if on and _BF16_STORAGE:
+        raise NotImplementedError("deterministic mode is not offered with bf16 activation storage (its kernels' summation orders were "
+                                  "never examined): set_bf16_storage(False)")
+    _det_torch(on)
+    _DET = on
+    if _lib is not None or os.path.exists(LIB_PATH):
+        if lib().mmt_set_deterministic(1 if on else 0) != 0:   # (a switch, not work: not counted among the launches)
+            raise RuntimeError("mmt_set_deterministic failed")
+
+
+def get_deterministic():
+    return _DET
+
+
+def reset_adaptive_state():
+    """forget what earlier launches taught the host side about tensors' ranges -- the sites' fp16 / bf16 states, the delayed scales of
+    f16_split, the producers' plane scales: the state a fresh process starts from (MTtrainer calls this when it is built in
+    deterministic mode, so that a second trainer of a process repeats the first)"""
+    _F16SITE.clear()
+    _SITES.clear()
+    rb_reset()
+
+
+if _DET:
+    if _BF16_STORAGE:
+        raise NotImplementedError("MMT_DETERMINISTIC=1 with MMT_BF16_STORAGE=1: deterministic mode is not offered with bf16 activation storage")
+    _det_torch(True)
+
+
+def _refuse_unordered(kernel, what):
+    if _DET:
+        raise NotImplementedError("%s is not offered in deterministic mode: %s adds into its destination with float atomics and has "
+                                  "no ordered form yet; set_deterministic(False)" % (what, kernel))
 
 
 def lib():
@@ -747,6 +833,8 @@ def lib():
             f = getattr(L, name)
             f.restype = c_int
             f.argtypes = args
+        if _DET:
+            L.mmt_set_deterministic(1)
         _lib = _LibProxy(L)
     return _lib
 
@@ -764,7 +852,7 @@ def _lib_raw():
 # on: ~70 ctypes calls instead of the Python that derives them (a manual graph: hipGraph replays of the two models serialise in
 # this runtime).  Only the input's address is patched.  Queries are not recorded.
 _NO_RECORD = frozenset(("mmt_conv_wants_planes", "mmt_conv_pg_wanted", "mmt_conv_writes_rb", "mmt_conv_wgrad_group_workspace", "mmt_conv_variant", "mmt_conv_ksplit", "mmt_conv_pg_plan",
-                        "mmt_conv_wgrad_splits", "mmt_get_conv_precision", "mmt_packed_weight_elems", "mmt_set_conv_precision"))
+                        "mmt_conv_wgrad_splits", "mmt_get_conv_precision", "mmt_packed_weight_elems", "mmt_set_conv_precision", "mmt_set_deterministic", "mmt_get_deterministic"))
 LAYOUT_EPOCH = [0]    # bumped when a flat model (re)allocates its plane buffers (engine/flat.py)
 LAUNCH_PLANS = os.environ.get("MMT_LAUNCH_PLANS", "1") != "0"
 _LP_SLOTS = 512
@@ -900,7 +988,7 @@ def planned(tag, fn, x):
     plan: the first call of a (tag, shape, stream, arithmetic) runs as it is (caches warm up: weight planes, folded BN), the second
     is recorded, later ones are replayed.  -> fn's result (replays return the SAME tensor objects, refilled)."""
     env = os.environ.get   # (the library's per-call switches -- A/B timing, parity tests -- choose kernels: part of the key)
-    key = (tag, tuple(x.shape), x.dtype, _stream(), _PLAN_EPOCH[0], PLANES_EPOCH, LAYOUT_EPOCH[0], F16X2, _PREC, _BF16_STORAGE, _RB_EPOCH[0],
+    key = (tag, tuple(x.shape), x.dtype, _stream(), _PLAN_EPOCH[0], PLANES_EPOCH, LAYOUT_EPOCH[0], F16X2, _PREC, _BF16_STORAGE, _RB_EPOCH[0], _DET,
            env("MMT_STRIP"), env("MMT_SPLITK"), env("MMT_ROWS"), env("MMT_PG"), env("MMT_C64"), env("MMT_DIRECT_EPI"))
     if getattr(_TLS, "rec", None) is None and _POOL_GRAVE:
         _drain_pools()
@@ -1069,6 +1157,8 @@ def roi_align_backward(grad_out, shapes, scales, rois, levels, ph, pw, sr, into=
     K = rois.shape[0]
     if into is not None and not any(t is not None for t in into):
         into = None
+    if _DET:
+        return _roi_align_backward_ordered(g, shapes, scales, rois, levels, K, ph, pw, sr, into)
     if into is None and g.is_cuda and g.dtype == torch.float32 and os.environ.get("MMT_ROI_BWD_DENSE", "0") != "0":
         # opt-in: the tile-gather form writes every element of every level once -- no clear, no atomics, repeatable (csrc/roi_align.hip)
         grads = [empty_nhwc(s[0], s[1], s[2], s[3], g.device) for s in shapes]
@@ -1088,6 +1178,32 @@ def roi_align_backward(grad_out, shapes, scales, rois, levels, ph, pw, sr, into=
         p = _pyramid(grads, scales, grads)
         _check(lib().mmt_roi_align_backward(ctypes.byref(p), _p(rois), _p(levels), K, ph, pw, sr, _p(g), _stream()),
                "mmt_roi_align_backward")
+    return grads
+
+
+def _roi_align_backward_ordered(g, shapes, scales, rois, levels, K, ph, pw, sr, into):
+    """deterministic mode: the tile-gather form (include/mmtpsm.h: mmt_roi_align_backward_ordered) -- a level given in `into` gets
+    grad = grad + (the tile's fixed-order sum), the others are written, zeros included; a call the kernel does not take raises"""
+    _dev(g, "grad_out")
+    if g.dtype != torch.float32:
+        raise NotImplementedError("roi_align_backward in deterministic mode: fp32 gradients only")
+    grads, mask = [], 0
+    for i, s in enumerate(shapes):
+        t = into[i] if into is not None else None
+        if t is not None:
+            if tuple(t.shape) != tuple(s) or t.dtype != torch.float32 or not t.is_contiguous(memory_format=torch.channels_last):
+                raise RuntimeError("roi_align_backward: `into` must hold dense NHWC fp32 tensors of the levels' shapes")
+            mask |= 1 << i
+        else:
+            t = empty_nhwc(s[0], s[1], s[2], s[3], g.device)
+        grads.append(t)
+    p = _pyramid(grads, scales, grads)
+    rc = lib().mmt_roi_align_backward_ordered(ctypes.byref(p), _p(rois), _p(levels), K, ph, pw, sr, _p(g), mask, _stream())
+    if rc == 1:
+        raise NotImplementedError("roi_align_backward in deterministic mode: roi_align_bwd_tiles_kernel takes sampling_ratio 2, "
+                                  "C %% 64 == 0, C <= 256 and K <= 8192 (got sampling_ratio %d, C %d, K %d), and the scatter kernel adds "
+                                  "with float atomics; set_deterministic(False)" % (sr, shapes[0][1], K))
+    _check(rc, "mmt_roi_align_backward_ordered")
     return grads
 
 
@@ -1325,6 +1441,11 @@ def ciam_bwd(x, group, gamma, A, J, dout):
     dx = torch.empty((n, C, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device)
     ws = torch.empty((n * n + n,), dtype=torch.float32, device=x.device)
     dgamma = torch.empty((1,), dtype=torch.float32, device=x.device)
+    if _DET:   # the rows' shares of dgamma added in row order
+        part = torch.empty((n,), dtype=torch.float32, device=x.device)
+        _check(lib().mmt_ciam_bwd_ordered(_p(x), _p(group), n, C, HW, n, _p(gamma), _p(A), _p(J), _p(dout), _p(ws), ws.data_ptr() + 4 * n * n,
+                                          _p(dx), _p(dgamma), _p(part), _stream()), "mmt_ciam_bwd_ordered")
+        return dx, dgamma
     _check(lib().mmt_ciam_bwd(_p(x), _p(group), n, C, HW, n, _p(gamma), _p(A), _p(J), _p(dout), _p(ws), ws.data_ptr() + 4 * n * n, _p(dx),
                               _p(dgamma), _stream()), "mmt_ciam_bwd")
     return dx, dgamma
@@ -2088,11 +2209,19 @@ def conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale=None, dbias=None, side=
                 else:
                     ws.record_stream(side)
                 _TLS.last_ws = None
+            _drain_det_ws(side, keep)
     x = nhwc(x)
     dy = nhwc(dy)
     Cout, Cin, KH, KW = w_shape
+    bias_to = None
+    if _DET and dbias is not None:
+        if dy.dtype != torch.float32:
+            raise NotImplementedError("deterministic mode: the ordered bias gradient reads fp32 gradients")
+        bias_to, dbias = dbias, None   # the weight-gradient kernels' bias epilogues use float atomics: an ordered column sum instead
     f16 = F16X2 and x.dtype == torch.float32 and dy.dtype == torch.float32 and get_conv_precision() == 3
     if f16 and WG_PLANES and _conv_wgrad_planes(x, dy, w_shape, stride, pad, dw, rowscale, dbias):
+        if bias_to is not None:
+            _bias_ordered(dy, bias_to)
         return
     # the shape half of the argument block and the split count depend on the shapes only: kept after the first call
     key = (x.shape, dy.shape, w_shape, stride, pad, x.dtype, dy.dtype)
@@ -2120,6 +2249,33 @@ def conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale=None, dbias=None, side=
     _check(lib().mmt_conv_wgrad(ctypes.byref(a), _p(dy), _p(rowscale), _p(dw), _p(dbias), _p(ws), _stream()), "mmt_conv_wgrad")
     if e0 is not None:
         _profiled(a, e0, "wgrad", splits, None, 0)
+    if bias_to is not None:
+        _bias_ordered(dy, bias_to)
+
+
+def _bias_ordered(dy, out):
+    """deterministic mode: out[c] += sum_m dy[m, c] in a fixed order (include/mmtpsm.h: mmt_colsum_ordered), on the stream of the
+    launch it belongs to; dy dense fp32 whose memory is [M][C] row-major"""
+    C = out.numel()
+    M = dy.numel() // C
+    ws = torch.empty((COLSUM_MAX_BLOCKS * C,), dtype=torch.float32, device=dy.device)
+    _check(lib().mmt_colsum_ordered(_p(dy), M, C, _p(out), _p(ws), _stream()), "mmt_colsum_ordered")
+    if getattr(_TLS, "stream", None) is not None:   # a side stream: the workspace lives until its caller has dealt with it
+        kept = getattr(_TLS, "det_ws", None)
+        if kept is None:
+            kept = _TLS.det_ws = []
+        kept.append(ws)
+
+
+def _drain_det_ws(side, keep):
+    kept = getattr(_TLS, "det_ws", None)
+    if kept:
+        for ws in kept:
+            if keep is not None:
+                keep.append(ws)
+            else:
+                ws.record_stream(side)
+        kept.clear()
 
 
 # a batch of weight gradients as grouped launches (mmt_conv_wgrad_group): -0.5 ... -0.75 ms per step with every job cut into a quarter
@@ -2164,18 +2320,21 @@ def conv_wgrad_group(jobs, side=None, keep=None):
             return conv_wgrad_group(jobs, None, keep)
         finally:
             _TLS.stream = None
+            _drain_det_ws(side, keep)
     keep_ = keep if keep is not None else []
-    grouped, single = [], []
+    grouped, single, biases = [], [], []   # biases: deterministic mode, (dy, dbias) of the grouped jobs -- ordered column sums behind the launches
     if WGRAD_GROUP and not (PROFILE is not None and PROFILE_ALL):
         for job in jobs:
             x, dy, w_shape, stride, pad, dw, rowscale, dbias = job
             x, dy = nhwc(x), nhwc(dy)
-            wj = _wgrad_group_job(x, dy, w_shape, stride, pad, dw, rowscale, dbias, keep_)
+            wj = _wgrad_group_job(x, dy, w_shape, stride, pad, dw, rowscale, None if _DET else dbias, keep_)
             if wj is None:
                 single.append(job)
             else:
                 grouped.append(wj)
                 keep_.extend((x, dy))
+                if _DET and dbias is not None:
+                    biases.append((dy, dbias))
     else:
         single = list(jobs)
     for c0 in range(0, len(grouped), 96):
@@ -2192,6 +2351,8 @@ def conv_wgrad_group(jobs, side=None, keep=None):
             if keep is not None:
                 keep.append(ws)
             # (callers without `keep` launch on the current stream: the caching allocator orders the buffer's reuse behind it)
+    for dy, dbias in biases:
+        _bias_ordered(dy, dbias)
     for job in single:
         conv_wgrad(*job)
         ws = getattr(_TLS, "last_ws", None)
@@ -2202,6 +2363,8 @@ def conv_wgrad_group(jobs, side=None, keep=None):
 
 def colsum(dy2d, out):
     """out[c] += sum_m dy2d[m, c]; dy2d any dense tensor whose memory is [M][C] row-major"""
+    if _DET:
+        return _bias_ordered(dy2d, out)
     C = out.numel()
     M = dy2d.numel() // C
     _check(lib().mmt_colsum(_p(dy2d), M, C, _p(out), _stream()), "mmt_colsum")
@@ -2281,6 +2444,7 @@ def stem_wgrad(x, dy, dw, rowscale=None):
         raise RuntimeError("stem weight gradient: dw is a dense fp32 tensor in the weight's layout (64, 3, 7, 7 channels-last)")
     if rowscale is not None and not (rowscale.is_cuda and rowscale.dtype == torch.float32 and rowscale.numel() == 64 and rowscale.is_contiguous()):
         raise RuntimeError("stem weight gradient: rowscale is a dense fp32 GPU vector of 64 elements")
+    _refuse_unordered("stem_wgrad_kernel", "a trainable stem (MODEL.BACKBONE.FREEZE_CONV_BODY_AT 0)")
     _check(lib().mmt_stem_wgrad(_p(x), _p(dy), _p(rowscale), _p(dw), N, H, W, _stream()), "mmt_stem_wgrad")
     return dw
 
@@ -2345,6 +2509,7 @@ def gconv3x3_dgrad(dy, w, x_hw, stride=1, scale=None, mask=None, out=None):
 
 def gconv3x3_wgrad(x, dy, w_shape, stride, dw, rowscale=None):
     """include/mmtpsm.h: mmt_gconv3x3_wgrad.  dw (C, Cg, 3, 3 in the weight's layout) += rowscale[co] * the weight gradient"""
+    _refuse_unordered("gconv_wgrad_kernel", "the weight gradient of a grouped 3x3 convolution (ResNeXt conv2)")
     if bf16_storage():
         raise NotImplementedError("grouped 3x3 convolutions (ResNeXt) are not offered with bf16 activation storage: "
                                   "set_bf16_storage(False)")
@@ -2374,7 +2539,8 @@ def rpn_loss(obj, reg, labels, regt, pos, neg, beta):
     if pos.dtype != torch.bool or neg.dtype != torch.bool:
         raise RuntimeError("rpn_loss: the sampler masks are bool tensors")
     R = obj.numel()
-    ws = torch.empty((8,), dtype=torch.float32, device=obj.device)      # sums [0:3], out [4:6]
+    # sums [0:3], out [4:6]; deterministic mode: the library's block partials behind them
+    ws = torch.empty((8 + 3 * RPN_LOSS_MAX_BLOCKS if _DET else 8,), dtype=torch.float32, device=obj.device)
     dobj, dreg = torch.empty_like(obj), torch.empty_like(reg)
     _check(lib().mmt_rpn_loss(_p(obj), _p(reg), _p(labels), _p(regt), _p(pos), _p(neg), R, float(beta), _p(ws), ws.data_ptr() + 16,
                               _p(dobj), _p(dreg), _stream()), "mmt_rpn_loss")
@@ -2390,6 +2556,12 @@ def box_loss(logits, breg, labels, regt, n_rows=None):
     R, NC = logits.shape
     out = torch.empty((2,), dtype=torch.float32, device=logits.device)
     dl, db = torch.empty_like(logits), torch.empty_like(breg)
+    if _DET:
+        ws = torch.empty((2 * BOX_LOSS_MAX_BLOCKS,), dtype=torch.float32, device=logits.device)
+        _check(lib().mmt_box_loss_ordered(_p(logits), _p(breg), _p(labels), _p(regt), R, NC,
+                                          None if n_rows is None else _p(n_rows.to(torch.int64)), _p(out), _p(dl), _p(db), _p(ws),
+                                          _stream()), "mmt_box_loss_ordered")
+        return out, dl, db
     if n_rows is not None:
         _check(lib().mmt_box_loss_rows(_p(logits), _p(breg), _p(labels), _p(regt), R, NC, _p(n_rows.to(torch.int64)), _p(out), _p(dl),
                                        _p(db), _stream()), "mmt_box_loss_rows")
@@ -2406,6 +2578,11 @@ def mask_bce(logits, labels, targets, grad_scale=1.0):
     targets = _dev(targets).float().contiguous()
     loss = torch.zeros((), dtype=torch.float32, device=logits.device)
     grad = empty_nhwc(P, NC, M, M, logits.device)
+    if _DET:
+        ws = torch.empty((MASK_BCE_WS,), dtype=torch.float32, device=logits.device)
+        _check(lib().mmt_mask_bce_ordered(_p(logits), _p(labels), _p(targets), P, M * M, NC, float(grad_scale), _p(loss), _p(grad),
+                                          _p(ws), _stream()), "mmt_mask_bce_ordered")
+        return loss, grad
     _check(lib().mmt_mask_bce(_p(logits), _p(labels), _p(targets), P, M * M, NC, float(grad_scale), _p(loss), _p(grad),
                               _stream()), "mmt_mask_bce")
     return loss, grad
@@ -2431,6 +2608,11 @@ def mgd_level_forward(s, ts, flips, m, acc=None):
     if acc is None:
         acc = torch.zeros((len(ts) + 1,), dtype=torch.float32, device=s.device)
     T = _teachers(ts, flips)
+    if _DET:
+        ws = torch.empty((MGD_MAX_BLOCKS * (len(ts) + 1),), dtype=torch.float32, device=s.device)
+        _check(lib().mmt_mgd_level_forward_ordered(_p(s), ctypes.byref(T), _p(m), N, H, W, C, _p(acc), _p(ws), _stream()),
+               "mmt_mgd_level_forward_ordered")
+        return acc
     _check(lib().mmt_mgd_level_forward(_p(s), ctypes.byref(T), _p(m), N, H, W, C, _p(acc), _stream()),
            "mmt_mgd_level_forward")
     return acc
@@ -2485,6 +2667,11 @@ def mgd_views_forward(ss, mirrors, ts, flips, m, acc=None):
     if acc is None:
         acc = torch.zeros((len(ss) * len(ts) + 1,), dtype=torch.float32, device=ss[0].device)
     S, T = _students(ss, mirrors), _teachers(ts, flips)
+    if _DET:
+        ws = torch.empty((MGD_MAX_BLOCKS * (len(ss) * len(ts) + 1),), dtype=torch.float32, device=ss[0].device)
+        _check(lib().mmt_mgd_views_forward_ordered(ctypes.byref(S), ctypes.byref(T), _p(m), N, Hh, W, C, _p(acc), _p(ws), _stream()),
+               "mmt_mgd_views_forward_ordered")
+        return acc
     _check(lib().mmt_mgd_views_forward(ctypes.byref(S), ctypes.byref(T), _p(m), N, Hh, W, C, _p(acc), _stream()),
            "mmt_mgd_views_forward")
     return acc

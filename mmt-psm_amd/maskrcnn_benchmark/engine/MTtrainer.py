@@ -357,6 +357,10 @@ class MTtrainer(object):
             self.student.set_rng(self.gen_s)
             self.teacher.set_rng(self.gen_t)
         self.teacher_check_period = int(os.environ.get("MMT_TEACHER_CHECK_PERIOD", "100"))
+        if H.get_deterministic():
+            # a run is repeatable from ITS start: what an earlier trainer of this process taught the host side about tensor ranges
+            # (producers' plane scales, delayed scales, site states) would make this trainer's first steps differ from a fresh process's
+            H.reset_adaptive_state()
 
     def seed_rng(self, seed):
         """re-seed the student's and the teacher's random streams (samplers, dropout)"""
