@@ -62,6 +62,35 @@ int mmt_roi_align_backward(const mmt_pyramid* pyr /*[host]*/, const float* rois,
 int mmt_roi_align_backward_dense(const mmt_pyramid* pyr /*[host]*/, const float* rois, const int32_t* levels,
                                  int K, int PH, int PW, int sampling_ratio, const float* grad_out, void* stream);
 
+/* ROIAlign of every ROI over SEVERAL MAPS into one tensor (the CSPN mask head, roi_mask_feature_extractors.py:60-88: four
+ * single-map poolers over the image-resolution features at scales 1, 1/2, 1/4, 1/8 and a channel concatenation).  No level
+ * mapping: every ROI reads every map.  Map m is NHWC [N, H[m], W[m], C[m]] with its own width and owns channels
+ * c_off[m] .. c_off[m] + C[m] of out [K, PH, PW, out_C]: the concatenated tensor is written once, in one launch; channels no
+ * map owns are not touched.  The bilinear code is that of mmt_roi_align_forward: a map's slice is bit-identical to a single-level
+ * call on that map.  backward: reads the same slices of grad_out (row stride out_C) and adds into grad_feat[m] (zero-initialised
+ * by the caller, or holding what other consumers have added) with fp32 atomics, like mmt_roi_align_backward.
+ * 1 <= num_maps <= 4, N >= 1, H, W >= 1, C[m] % 4 == 0, c_off[m] % 4 == 0, out_C % 4 == 0, slices inside out_C and disjoint,
+ * K >= 0 (0 launches nothing), PH, PW >= 1, sampling_ratio 0 (adaptive, ceil(roi_size / pooled_size)) or > 0; anything else
+ * returns MMT_EINVAL.  A ROI whose image index is outside 0 .. N-1 reads nothing: zeros forward, no gradient.
+ * The forward reads feat[m] only (grad_feat may be null), the backward grad_feat[m] only (feat may be null). */
+typedef struct {
+  const float* feat[4];
+  float* grad_feat[4]; /* backward only */
+  int H[4];
+  int W[4];
+  int C[4];
+  int c_off[4];
+  float scale[4];
+  int num_maps;
+  int N;
+  int out_C;
+} mmt_roi_maps;
+
+int mmt_roi_align_maps_forward(const mmt_roi_maps* maps /*[host]*/, const float* rois, int K, int PH, int PW, int sampling_ratio,
+                               float* out, void* stream);
+int mmt_roi_align_maps_backward(const mmt_roi_maps* maps /*[host]*/, const float* rois, int K, int PH, int PW, int sampling_ratio,
+                                const float* grad_out, void* stream);
+
 /* ---------------------------------------------------------------- batched NMS
  * replaces _C.nms (csrc/nms.h:10-28; CPU semantics cpu/nms_cpu.cpp:37-64: "+1" areas, suppress on
  * IoU >= thr) for B independent segments in one launch pair (RPN: one segment per (image, level),

@@ -43,34 +43,21 @@ __device__ __forceinline__ Bilin bilin(int H, int W, float y, float x) {
   return b;
 }
 
-// HALF (forward only, VEC == 4): the pyramid levels are bf16 tensors (bf16 activation storage, mode 1); taps are widened
-// exactly, arithmetic and output stay fp32
-template <bool BWD, int VEC, bool HALF = false>
-__global__ __launch_bounds__(256) void roi_align_kernel(Pyr p, const float* __restrict__ rois,
-                                                        const int* __restrict__ levels, int K, int PH, int PW,
-                                                        int sr, float* __restrict__ out_or_gout) {
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const long bin = (long)blockIdx.x * 4 + wave;
-  const long nbins = (long)K * PH * PW;
-  if (bin >= nbins) return;
-  const int pw = (int)(bin % PW);
-  const int ph = (int)((bin / PW) % PH);
-  const int k = (int)(bin / ((long)PW * PH));
-  const int lv = levels[k];
-  const float* r = rois + (long)k * 5;
-  const int b = (int)r[0];
-  const float scale = p.scale[lv];
-  const int H = p.H[lv], W = p.W[lv], C = p.C;
+// One (roi, bin) of one map, by one wave: the bilinear device code shared by roi_align_kernel (FPN levels, one level per ROI) and
+// roi_align_maps_kernel (several maps of their own widths, every ROI reads every map).  feat / gfeat point at the ROI's image inside
+// the map, o at the bin's C channels of the pooled tensor (forward: written; backward: the gradient read).
+// HALF (forward only, VEC == 4): the map is a bf16 tensor (bf16 activation storage, mode 1); taps are widened exactly, arithmetic
+// and output stay fp32
+template <bool BWD, int VEC, bool HALF>
+__device__ __forceinline__ void roi_bin(const float* feat, float* gfeat, const int H, const int W, const int C, const float scale,
+                                        const float* r, const int ph, const int pw, const int PH, const int PW, const int sr,
+                                        float* o, const int lane) {
   const float rsw = r[1] * scale, rsh = r[2] * scale, rew = r[3] * scale, reh = r[4] * scale;
   const float rw = fmaxf(rew - rsw, 1.f), rh = fmaxf(reh - rsh, 1.f);
   const float bh = rh / (float)PH, bw = rw / (float)PW;
   const int gh = sr > 0 ? sr : (int)ceilf(rh / PH);
   const int gw = sr > 0 ? sr : (int)ceilf(rw / PW);
   const float count = (float)(gh * gw);
-  const float* feat = HALF ? (const float*)((const unsigned short*)p.feat[lv] + (long)b * H * W * C) : p.feat[lv] + (long)b * H * W * C;
-  float* gfeat = BWD ? p.grad[lv] + (long)b * H * W * C : nullptr;
-  float* o = out_or_gout + bin * C;
 
   if (BWD && gh == 2 && gw == 2) {
     // Backward, 2x2 sampling grid (the only one the model uses).  The sample grid of a bin is a product grid, so
@@ -177,6 +164,68 @@ __global__ __launch_bounds__(256) void roi_align_kernel(Pyr p, const float* __re
       else o[c0] = acc[0];
     }
   }
+}
+
+template <bool BWD, int VEC, bool HALF = false>
+__global__ __launch_bounds__(256) void roi_align_kernel(Pyr p, const float* __restrict__ rois,
+                                                        const int* __restrict__ levels, int K, int PH, int PW,
+                                                        int sr, float* __restrict__ out_or_gout) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const long bin = (long)blockIdx.x * 4 + wave;
+  const long nbins = (long)K * PH * PW;
+  if (bin >= nbins) return;
+  const int pw = (int)(bin % PW);
+  const int ph = (int)((bin / PW) % PH);
+  const int k = (int)(bin / ((long)PW * PH));
+  const int lv = levels[k];
+  const float* r = rois + (long)k * 5;
+  const int b = (int)r[0];
+  const int H = p.H[lv], W = p.W[lv], C = p.C;
+  const float* feat = HALF ? (const float*)((const unsigned short*)p.feat[lv] + (long)b * H * W * C) : p.feat[lv] + (long)b * H * W * C;
+  float* gfeat = BWD ? p.grad[lv] + (long)b * H * W * C : nullptr;
+  roi_bin<BWD, VEC, HALF>(feat, gfeat, H, W, C, p.scale[lv], r, ph, pw, PH, PW, sr, out_or_gout + bin * C, lane);
+}
+
+// ---- several maps into one tensor (the CSPN mask head, reference roi_mask_feature_extractors.py:60-88: four single-map poolers at
+// scales 1 .. 1/8 and a channel concatenation): map m has its own H, W, C and owns channels c_off[m] .. c_off[m] + C[m] of the
+// pooled tensor [K][PH][PW][out_C].  No level mapping: every ROI reads every map.  One wave per (roi, bin, map), the map the fastest
+// index, so the four waves of a block write one bin's row of the concatenated tensor.
+struct Maps {
+  const float* feat[4];
+  float* grad[4];
+  int H[4], W[4], C[4], c_off[4];
+  float scale[4];
+  int n, N, out_C;
+};
+
+// (p is indexed by the wave-uniform m: the compiler reads the kernel-argument segment at a scalar offset -- scalar loads into
+// SGPRs, no copy of the struct in scratch; the code object shows 0 bytes of scratch and no spills, tools/codeobj.py)
+template <bool BWD>
+__global__ __launch_bounds__(256) void roi_align_maps_kernel(Maps p, const float* __restrict__ rois, int K, int PH, int PW, int sr,
+                                                             float* __restrict__ out_or_gout) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const long item = (long)blockIdx.x * 4 + wave;
+  const long nbins = (long)K * PH * PW;
+  if (item >= nbins * p.n) return;
+  const int m = (int)(item % p.n);
+  const long bin = item / p.n;
+  const int pw = (int)(bin % PW);
+  const int ph = (int)((bin / PW) % PH);
+  const int k = (int)(bin / ((long)PW * PH));
+  const float* r = rois + (long)k * 5;
+  const int b = (int)r[0];
+  const int H = p.H[m], W = p.W[m], C = p.C[m];
+  float* o = out_or_gout + bin * p.out_C + p.c_off[m];
+  if (b < 0 || b >= p.N) {   // an image the maps do not hold: nothing is read; the forward writes zeros, the backward adds nothing
+    if (!BWD)
+      for (int c0 = lane * 4; c0 < C; c0 += 256) *(f32x4*)(o + c0) = f32x4{0.f, 0.f, 0.f, 0.f};
+    return;
+  }
+  const float* feat = p.feat[m] + (long)b * H * W * C;
+  float* gfeat = BWD ? p.grad[m] + (long)b * H * W * C : nullptr;
+  roi_bin<BWD, 4, false>(feat, gfeat, H, W, C, p.scale[m], r, ph, pw, PH, PW, sr, o, lane);
 }
 
 // ---- backward without atomics (round 5): one block per 8 x 8 pixel tile of one (level, image) map.  The block
@@ -443,4 +492,49 @@ extern "C" int mmt_roi_align_backward_ordered(const mmt_pyramid* pyr, const floa
                                               void* stream) {
   if (accumulate_mask < 0 || accumulate_mask > 15) return MMT_EINVAL;
   return bwd_tiles_launch(pyr, rois, levels, K, PH, PW, sampling_ratio, grad_out, accumulate_mask, false, stream);
+}
+
+static int fill_maps(Maps& q, const mmt_roi_maps* p, bool bwd, int K, int PH, int PW, int sampling_ratio) {
+  if (!p || p->num_maps < 1 || p->num_maps > 4 || p->N < 1 || p->out_C < 4 || (p->out_C & 3) || K < 0 || PH < 1 || PW < 1 ||
+      sampling_ratio < 0)
+    return MMT_EINVAL;
+  for (int m = 0; m < 4; m++) {
+    const int s = m < p->num_maps ? m : 0;
+    if (m < p->num_maps) {
+      if (p->H[m] < 1 || p->W[m] < 1 || p->C[m] < 4 || (p->C[m] & 3) || p->c_off[m] < 0 || (p->c_off[m] & 3) ||
+          (long)p->c_off[m] + p->C[m] > p->out_C || !(bwd ? (const void*)p->grad_feat[m] : (const void*)p->feat[m]))
+        return MMT_EINVAL;
+      for (int j = 0; j < m; j++)   // (two maps never own the same channel)
+        if (p->c_off[m] < p->c_off[j] + p->C[j] && p->c_off[j] < p->c_off[m] + p->C[m]) return MMT_EINVAL;
+    }
+    q.feat[m] = p->feat[s]; q.grad[m] = p->grad_feat[s];
+    q.H[m] = p->H[s]; q.W[m] = p->W[s]; q.C[m] = p->C[s]; q.c_off[m] = p->c_off[s]; q.scale[m] = p->scale[s];
+  }
+  q.n = p->num_maps; q.N = p->N; q.out_C = p->out_C;
+  return 0;
+}
+
+template <bool BWD>
+static int maps_launch(const mmt_roi_maps* maps, const float* rois, int K, int PH, int PW, int sampling_ratio, float* out_or_gout,
+                       void* stream) {
+  Maps q;
+  int e = fill_maps(q, maps, BWD, K, PH, PW, sampling_ratio);
+  if (e) return e;
+  const long items = (long)K * PH * PW * q.n;
+  if (items == 0) return 0;
+  if (!rois || !out_or_gout || (items + 3) / 4 > 0x7fffffffL) return MMT_EINVAL;
+  hipLaunchKernelGGL((roi_align_maps_kernel<BWD>), dim3(mmt_cdiv(items, 4)), dim3(256), 0, (hipStream_t)stream, q, rois, K, PH, PW,
+                     sampling_ratio, out_or_gout);
+  MMT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmt_roi_align_maps_forward(const mmt_roi_maps* maps, const float* rois, int K, int PH, int PW, int sampling_ratio,
+                                          float* out, void* stream) {
+  return maps_launch<false>(maps, rois, K, PH, PW, sampling_ratio, out, stream);
+}
+
+extern "C" int mmt_roi_align_maps_backward(const mmt_roi_maps* maps, const float* rois, int K, int PH, int PW, int sampling_ratio,
+                                           const float* grad_out, void* stream) {
+  return maps_launch<true>(maps, rois, K, PH, PW, sampling_ratio, const_cast<float*>(grad_out), stream);
 }

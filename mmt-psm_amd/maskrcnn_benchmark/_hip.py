@@ -22,6 +22,11 @@ class Pyramid(ctypes.Structure):
                 ("scale", c_float * 4), ("num_levels", c_int), ("N", c_int), ("C", c_int)]
 
 
+class RoiMaps(ctypes.Structure):   # include/mmtpsm.h: mmt_roi_maps
+    _fields_ = [("feat", c_void_p * 4), ("grad_feat", c_void_p * 4), ("H", c_int * 4), ("W", c_int * 4), ("C", c_int * 4),
+                ("c_off", c_int * 4), ("scale", c_float * 4), ("num_maps", c_int), ("N", c_int), ("out_C", c_int)]
+
+
 class ConvArgs(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("w", c_void_p), ("scale", c_void_p), ("shift", c_void_p), ("res", c_void_p),
                 ("mask", c_void_p), ("mul", c_void_p), ("y", c_void_p),
@@ -86,6 +91,8 @@ _SIGS = {
     "mmt_roi_align_forward_bf16": [ctypes.POINTER(Pyramid), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_roi_align_backward": [ctypes.POINTER(Pyramid), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_roi_align_backward_dense": [ctypes.POINTER(Pyramid), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "mmt_roi_align_maps_forward": [ctypes.POINTER(RoiMaps), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "mmt_roi_align_maps_backward": [ctypes.POINTER(RoiMaps), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_nms_batched": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "mmt_resample_u8": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "mmt_aug_views": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_float),
@@ -1204,6 +1211,65 @@ def _roi_align_backward_ordered(g, shapes, scales, rois, levels, K, ph, pw, sr, 
                                   "C %% 64 == 0, C <= 256 and K <= 8192 (got sampling_ratio %d, C %d, K %d), and the scatter kernel adds "
                                   "with float atomics; set_deterministic(False)" % (sr, shapes[0][1], K))
     _check(rc, "mmt_roi_align_backward_ordered")
+    return grads
+
+
+def _roi_maps(shapes, scales, c_off, out_C, feats=None, grads=None):
+    """mmt_roi_maps of 1..4 maps of the shapes (N, C, H, W); c_off None: the maps side by side in the order given"""
+    n = len(shapes)
+    if not 1 <= n <= 4 or len(scales) != n or (c_off is not None and len(c_off) != n):
+        raise RuntimeError("roi_align_maps: 1..4 maps with one scale (and one channel offset) each, got %d" % n)
+    if any(len(s) != 4 or s[0] != shapes[0][0] for s in shapes):
+        raise RuntimeError("roi_align_maps: maps are (N, C, H, W) tensors of one batch size")
+    if c_off is None:
+        c_off = [sum(s[1] for s in shapes[:i]) for i in range(n)]
+    p = RoiMaps()
+    p.num_maps, p.N = n, shapes[0][0]
+    p.out_C = int(out_C) if out_C is not None else sum(s[1] for s in shapes)
+    for i, s in enumerate(shapes):
+        p.feat[i] = feats[i].data_ptr() if feats is not None else None
+        p.grad_feat[i] = grads[i].data_ptr() if grads is not None else None
+        p.C[i], p.H[i], p.W[i] = s[1], s[2], s[3]
+        p.c_off[i], p.scale[i] = int(c_off[i]), float(scales[i])
+    return p
+
+
+def roi_align_maps_forward(feats, scales, rois, ph, pw, sr, c_off=None, out=None):
+    """include/mmtpsm.h: mmt_roi_align_maps_forward.  feats: 1..4 fp32 (N, C_m, H_m, W_m) NHWC-dense maps; rois (K, 5) fp32; every ROI
+    is pooled from every map -> (K, sum C_m, ph, pw) NHWC-dense, map m at channels c_off[m] .. c_off[m] + C_m (default: side by
+    side).  out: an NHWC-dense fp32 (K, out_C, ph, pw) tensor to write the slices of (channels no map owns stay as they are)"""
+    feats = [nhwc(_dev(f, "feats")) for f in feats]
+    if any(f.dtype != torch.float32 for f in feats):
+        raise RuntimeError("roi_align_maps_forward: fp32 maps only")
+    rois = _dev(rois, "rois").float().contiguous()
+    K = rois.shape[0]
+    if out is None:
+        out = empty_nhwc(K, sum(f.shape[1] for f in feats), ph, pw, rois.device)
+    elif (not out.is_cuda or out.dtype != torch.float32 or out.dim() != 4 or (out.shape[0], out.shape[2], out.shape[3]) != (K, ph, pw)
+          or nhwc(out) is not out):
+        raise RuntimeError("roi_align_maps_forward: `out` is an NHWC-dense fp32 GPU tensor (K, out_C, ph, pw)")
+    p = _roi_maps([tuple(f.shape) for f in feats], scales, c_off, out.shape[1], feats=feats)
+    _check(lib().mmt_roi_align_maps_forward(ctypes.byref(p), _p(rois), K, ph, pw, sr, _p(out), _stream()), "mmt_roi_align_maps_forward")
+    return out
+
+
+def roi_align_maps_backward(grad_out, shapes, scales, rois, ph, pw, sr, c_off=None):
+    """include/mmtpsm.h: mmt_roi_align_maps_backward.  grad_out (K, out_C, ph, pw) -> one zero-initialised-then-accumulated (fp32
+    atomics) gradient per map, (N, C_m, H_m, W_m) NHWC-dense"""
+    g = nhwc(_dev(grad_out, "grad_out"))
+    if g.dtype != torch.float32:
+        raise RuntimeError("roi_align_maps_backward: fp32 gradients only")
+    rois = _dev(rois, "rois").float().contiguous()
+    K = rois.shape[0]
+    if (g.shape[0], g.shape[2], g.shape[3]) != (K, ph, pw):
+        raise RuntimeError("roi_align_maps_backward: grad_out is (K, out_C, ph, pw)")
+    _refuse_unordered("roi_align_maps_kernel", "the CSPN mask head (MODEL.ROI_MASK_HEAD.FEATURE_EXTRACTOR PRCNNFeatureExtractor)")
+    shapes = [tuple(s) for s in shapes]
+    p = _roi_maps(shapes, scales, c_off, g.shape[1])
+    grads = [empty_nhwc(s[0], s[1], s[2], s[3], g.device, zero=True) for s in shapes]
+    for i, t in enumerate(grads):
+        p.grad_feat[i] = t.data_ptr()
+    _check(lib().mmt_roi_align_maps_backward(ctypes.byref(p), _p(rois), K, ph, pw, sr, _p(g), _stream()), "mmt_roi_align_maps_backward")
     return grads
 
 

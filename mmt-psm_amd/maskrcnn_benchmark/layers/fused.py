@@ -576,6 +576,51 @@ class RoiAlignFpnFn(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(out)
 
 
+class RoiAlignMapsFn(torch.autograd.Function):
+    """Every ROI pooled from every one of 1..4 maps of their own widths into one channel-concatenated tensor (the CSPN mask head,
+    roi_mask_feature_extractors.py:60-88): one launch forward (`mmt_roi_align_maps_forward`, no `cat` pass), one backward
+    (`mmt_roi_align_maps_backward`, fp32 atomics into fresh zeroed gradients).
+    ReLU convention: the bilinear gradient comes out UNMASKED.  The maps of the CSPN head are fused-ReLU outputs whose producers (ConvFn
+    with relu=True) expect a masked gradient, so the caller hands them over through `relu_grad_mask`, which applies (map > 0) to what
+    this node returns -- the node itself knows nothing of the maps' history."""
+
+    @staticmethod
+    def forward(ctx, rois, res, scales, sr, *feats):
+        feats = [H.nhwc(f) for f in feats]
+        out = H.roi_align_maps_forward(feats, scales, rois, res, res, sr)
+        ctx.save_for_backward(rois)
+        ctx.cfgv = (res, scales, sr, [tuple(f.shape) for f in feats])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        rois, = ctx.saved_tensors
+        res, scales, sr, shapes = ctx.cfgv
+        grads = H.roi_align_maps_backward(g, shapes, scales, rois, res, res, sr)
+        return (None, None, None, None) + tuple(gr if ctx.needs_input_grad[4 + i] else None for i, gr in enumerate(grads))
+
+
+class MaxPoolFn(torch.autograd.Function):
+    """3x3 / stride 2 / pad 1 max pool of a fused-ReLU output y (`mmt_maxpool3x3s2`).  Backward: `mmt_maxpool3x3s2_backward`, which has
+    y's ReLU mask fused in -- the gradient reaches y's producer masked by (y > 0), as the convention asks (StemFn has the argument
+    for why the mask changes nothing the pool's own gradient would not already have)."""
+
+    @staticmethod
+    def forward(ctx, y):
+        y = H.nhwc(y)
+        ctx.save_for_backward(y)
+        return H.maxpool3x3s2(y)
+
+    @staticmethod
+    def backward(ctx, g):
+        y, = ctx.saved_tensors
+        return H.maxpool3x3s2_backward(y, H.nhwc(g))
+
+
+def maxpool3x3s2(y):
+    return MaxPoolFn.apply(y)
+
+
 class MaskBCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, targets):

@@ -81,9 +81,12 @@ class MaskRelationRefineNet(nn.Module):
         ch = rm.EXTRACTOR_CHANNEL
         self.classifier = Conv2d(ch, 3, 1, 1, 0)
         self.deconv_1 = ConvTranspose2d(ch, ch, 2, 2, 0)
-        if rm.TYPE != "CIAM" or rm.SAME_PREDICTOR:
+        if rm.SAME_PREDICTOR or rm.TYPE == "CAM" or (rm.TYPE != "CIAM" and rm.USE_RELATION):
             raise NotImplementedError("mask relation: only TYPE 'CIAM' with its own predictor is built")
-        self.relation_module = CIAM_Module(cfg)
+        # mask_relation_module.py:42-45 builds a relation_module for 'CAM' / 'CIAM' only: any other TYPE (configs/pap/CSPN.yaml says
+        # 'LIAM' with USE_RELATION False) leaves extractor / classifier / deconv_1 and nothing else in the state dict
+        if rm.TYPE == "CIAM":
+            self.relation_module = CIAM_Module(cfg)
 
     def forward(self, x):
         """(ROI features (P,256,14,14), first mask logits (P,3,28,28), BoxList, target) of ONE image

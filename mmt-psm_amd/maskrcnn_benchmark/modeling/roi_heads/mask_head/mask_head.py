@@ -1,7 +1,8 @@
 """Mask head (reference: modeling/roi_heads/mask_head/{mask_head,roi_mask_feature_extractors,
 roi_mask_predictors,loss,inference}.py).
 
-Module tree kept: feature_extractor.mask_fcn{1-4}, predictor.conv5_mask (2x2 s2 deconv) / mask_fcn_logits.
+Module tree kept: feature_extractor.mask_fcn{1-4}, predictor.conv5_mask (2x2 s2 deconv) / mask_fcn_logits; with the CSPN keys
+(configs/pap/CSPN.yaml) feature_extractor.conv{1-8} / posconv{1,2} on the image and predictor.mask_fcn_logits.
 The two per-ROI CPU Python loops of the reference are single launches here:
   * mask targets  (project_masks_on_boxes + pycocotools rasteriser)  -> `mmt_polygon_targets`
   * teacher pseudo-mask (Masker.paste_mask_in_image per detection)     -> `mmt_paste_masks`
@@ -76,6 +77,98 @@ class MaskRCNNC4Predictor(nn.Module):
     def forward(self, x):
         x = self.conv5_mask(x, relu=True, input_relu=True)
         return self.mask_fcn_logits(x, relu=False, input_relu=True)
+
+
+class PRCNNFeatureExtractor(nn.Module):
+    """The CSPN second stage (roi_mask_feature_extractors.py:9-88; configs/pap/CSPN.yaml): four pairs of 3x3 convolutions on the
+    normalised IMAGE, a 3x3 / 2 max pool between the pairs, every proposal pooled at 25 x 25 from the four pair outputs (scales 1,
+    1/2, 1/4, 1/8; no level mapping) into one 480-channel tensor -- one launch, `fused.RoiAlignMapsFn` --, then posconv1 (+ ReLU) and
+    posconv2 (its ReLU belongs to the predictor).  Gradient routing: a pair's output y is a fused-ReLU output with two consumers,
+    the pool (whose backward kernel has the (y > 0) mask fused in: fused.MaxPoolFn) and the ROIAlign (reached through
+    `fused.relu_grad_mask`), so the convolution nodes receive the masked gradient they expect."""
+    WIDTHS = (32, 64, 128, 256)
+    RES = 25
+
+    def __init__(self, cfg):
+        super().__init__()
+        self._refuse_bf16()
+        self.sampling_ratio = cfg.MODEL.ROI_MASK_HEAD.POOLER_SAMPLING_RATIO
+        self.scales = (1.0, 0.5, 0.25, 0.125)
+        nxt = 3
+        for i, ch in enumerate(self.WIDTHS):
+            self.add_module("conv%d" % (2 * i + 1), Conv2d(nxt, ch, 3, stride=1, padding=1))
+            self.add_module("conv%d" % (2 * i + 2), Conv2d(ch, ch, 3, stride=1, padding=1))
+            nxt = ch
+        self.posconv1 = Conv2d(sum(self.WIDTHS), 256, 3, stride=1, padding=1)
+        self.posconv2 = Conv2d(256, 32, 3, stride=1, padding=1)
+        for i in range(1, 9):
+            self._init(getattr(self, "conv%d" % i))
+        self._init(self.posconv1)
+        self._init(self.posconv2)
+
+    @staticmethod
+    def _refuse_bf16():
+        """asked at construction and before every forward (the storage mode is a process-wide switch that may come later)"""
+        if H.bf16_storage():
+            raise NotImplementedError("MODEL.ROI_MASK_HEAD.FEATURE_EXTRACTOR PRCNNFeatureExtractor is not offered with bf16 "
+                                      "activation storage (its ROIAlign reads fp32 maps): set_bf16_storage(False)")
+
+    @staticmethod
+    def _init(layer):
+        nn.init.kaiming_normal_(layer.weight, mode="fan_out", nonlinearity="relu")
+        nn.init.constant_(layer.bias, 0)
+
+    def maps(self, x):
+        """the four pair outputs for the image batch x (N, 3, H, W)"""
+        n, c, h, w = x.shape
+        # RGB -> 4 channels with a zero weight slice (the kernels take Cin % 4 == 0); autograd slices conv1's weight gradient back.
+        # Per forward this costs a copy of the image (N x H x W x 16 B: 33 MB at 2 x 1024^2, beside the 268 MB conv1 writes), a pad
+        # and a layout copy of a 32 x 3 x 3 x 3 weight, and -- the padded weight being a new object every time -- conv1 never
+        # finds a kept packed or flipped form (none is used: 4 input channels run on the fp32-input kernel, and the image asks for
+        # no data gradient); its weight gradient is a fresh 4.6 KB tensor that autograd slices and adds into the flat buffer
+        # instead of the kernel writing there.  Not timed on its own; a padded weight kept in the flat buffer would remove it
+        x4 = x.new_zeros((n, h, w, 4))
+        x4[..., :3] = x.permute(0, 2, 3, 1)
+        w4 = torch.nn.functional.pad(self.conv1.weight, (0, 0, 0, 0, 0, 1)).contiguous(memory_format=torch.channels_last)
+        y = fused.conv(x4.permute(0, 3, 1, 2), w4, self.conv1.bias, 1, 1, True, False)
+        out = []
+        for i in range(4):
+            if i:
+                y = getattr(self, "conv%d" % (2 * i + 1))(fused.maxpool3x3s2(y), relu=True, input_relu=False)
+            y = getattr(self, "conv%d" % (2 * i + 2))(y, relu=True, input_relu=True)
+            out.append(y)
+        return out
+
+    def forward(self, x, proposals):
+        pre = x
+        self._refuse_bf16()
+        if all(b.mode == "xyxy" for b in proposals) and len(proposals) <= 32 and proposals[0].bbox.is_cuda:
+            rois, _ = H.roi_format_levels([b.bbox for b in proposals])   # one launch (modeling/poolers.py)
+        else:
+            rois = Pooler.convert_to_roi_format(proposals)
+        maps = [fused.relu_grad_mask(y) for y in self.maps(x)]
+        x = fused.RoiAlignMapsFn.apply(rois, self.RES, self.scales, self.sampling_ratio, *maps)
+        x = self.posconv1(x, relu=True, input_relu=False)
+        return self.posconv2(x, relu=False, input_relu=True), pre
+
+
+class PRCNNPredictor(nn.Module):
+    """roi_mask_predictors.py:39-53: ReLU, then a 1x1 convolution 32 -> 3 (three classes, as the reference hard-codes them)"""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.mask_fcn_logits = Conv2d(32, 3, 1, 1, 0)
+        nn.init.constant_(self.mask_fcn_logits.bias, 0)
+        nn.init.kaiming_normal_(self.mask_fcn_logits.weight, mode="fan_out", nonlinearity="relu")
+
+    def forward(self, x):
+        # posconv2's output carries no fused ReLU: the ReLU here is an elementwise pass of torch's own (with its own backward), and
+        # the 1x1 layer reads a plain tensor
+        return self.mask_fcn_logits(torch.relu(x), relu=False, input_relu=False)
+
+
+_ROI_MASK_FEATURE_EXTRACTORS = {"MaskRCNNFPNFeatureExtractor": MaskRCNNFPNFeatureExtractor, "PRCNNFeatureExtractor": PRCNNFeatureExtractor}
+_ROI_MASK_PREDICTORS = {"MaskRCNNC4Predictor": MaskRCNNC4Predictor, "PRCNNPredictor": PRCNNPredictor}
 
 
 class MaskRCNNLossComputation(object):
@@ -226,8 +319,11 @@ class ROIMaskHead(nn.Module):
     def __init__(self, cfg, is_student=False):
         super().__init__()
         self.cfg = cfg.clone()
-        self.feature_extractor = MaskRCNNFPNFeatureExtractor(cfg)
-        self.predictor = MaskRCNNC4Predictor(cfg)
+        m = cfg.MODEL.ROI_MASK_HEAD
+        # a name that is not built raises KeyError (the reference's own lookup, roi_mask_feature_extractors.py:222-224)
+        self.feature_extractor = _ROI_MASK_FEATURE_EXTRACTORS[m.FEATURE_EXTRACTOR](cfg)
+        self.predictor = _ROI_MASK_PREDICTORS[m.PREDICTOR](cfg)
+        self.on_image = m.FEATURE_EXTRACTOR == "PRCNNFeatureExtractor"   # mask_head.py:82-85: this extractor reads the image
         self.post_processor = make_roi_mask_post_processor(cfg)
         self.mask_generator = make_roi_mask_generator(cfg)
         self.loss_evaluator = make_roi_mask_loss_evaluator(cfg)
@@ -246,7 +342,7 @@ class ROIMaskHead(nn.Module):
         all_proposals = proposals
         if self.training:
             proposals, _ = keep_only_positive_boxes(proposals)
-        x, _ = self.feature_extractor(features, proposals)
+        x, _ = self.feature_extractor(images.tensors if self.on_image else features, proposals)
         mask_logits = self.predictor(x)
         loss_1 = self.loss_evaluator(proposals, mask_logits, targets) if self.training else None
         if self.use_relation:
