@@ -453,7 +453,9 @@ int mmt_stem_fused(const float* x, int N, int H, int W, const float* w_s2d, cons
  * kernel with pad (k - 1) / 2, stride 1, mode 3; MMT_WGRAD_PLANES=0), else the number of pixel ranges across blocks: workspace
  * (device, splits * Cout * KH * KW * Cin floats) is needed when it is > 1.  mmt_conv_wgrad_planes returns 1 and touches nothing
  * when the layer is not taken.  Products (h l), (l h), (h h) per 16 pixels, fp32 accumulation: the arithmetic of mmt_conv_wgrad's
- * fp16-split form, another summation order. */
+ * fp16-split form, another summation order.  A 3x3 layer runs the three-tap form (one block = 128 co x (kh, 128 ci) x the three kw
+ * taps from one copy of the operands, Cout / 128 x KH Cin / 128 tiles, 0.12 KB copied per MFMA); other kernel sizes the one-tap form
+ * (Cout / 128 x KH KW Cin / 128 tiles, 0.33 KB per MFMA).  The meaning of the split count is the same for both. */
 int mmt_conv_wgrad_planes_splits(const mmt_conv_args* a /*[host]*/);
 int mmt_conv_wgrad_planes(const mmt_conv_args* a /*[host]*/, const float* dy, const void* x_planes, long x_plane_stride,
                           const void* dy_planes, long dy_plane_stride, const float* s_x, const float* s_dy, const float* rowscale,

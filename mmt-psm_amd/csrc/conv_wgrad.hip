@@ -997,7 +997,9 @@ static long wg_plan(const mmt_wgrad_job* jobs, int n, WgJobPlan* plan) {
   // section 7): filling the chip as a group makes blocks that own a CU for ~150 us and hold up the step stream's latency-bound chain
   // (+2 ms); the jobs' own ranges only save launches and reduces (-0.3 ms); a quarter of them is the optimum (-0.5 ... -0.75 ms):
   // blocks four times as long, a quarter of the slab traffic, still short
-  constexpr int WG_DIV = 4;
+  // (WG_DIV_PL: the plane-fed jobs' divisor.  The three-tap form has a third of the tiles and three times the ranges of the one-tap
+  // form at equal block duration; swept again in the step with it, 2 / 4 / 8 are not separable: profiles/wgrad_kw3_ab.txt)
+  constexpr int WG_DIV = 4, WG_DIV_PL = 4;
   int kind[WGJ_MAX];
   for (int i = 0; i < n; i++) {
     ConvP p;
@@ -1025,7 +1027,7 @@ static long wg_plan(const mmt_wgrad_job* jobs, int n, WgJobPlan* plan) {
       WgJobPlan& pl = plan[i];
       pl.kind = k; pl.mps = 0;
       if (k == 1) {
-        long ks = (wgpl_eligible_splits(&a) + WG_DIV - 1) / WG_DIV;
+        long ks = (wgpl_eligible_splits(&a) + WG_DIV_PL - 1) / WG_DIV_PL;
         const long T = wgpl_super_steps(&a);
         if (ks > T / 8) ks = T / 8;
         if (ks < 1) ks = 1;
