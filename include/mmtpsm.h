@@ -718,6 +718,15 @@ int mmt_polygon_targets(const float* poly_xy, const int32_t* poly_off, const int
  * mmt_paste_mask_stack writes them, non-zero = set -> words [n][ceil(H*W/64)], rec [n][8]. */
 #define MMT_MASK_REC_INTS 8
 int mmt_mask_pack(const uint8_t* masks, int n, int H, int W, uint64_t* words, int32_t* rec, void* stream);
+/* paste straight into words (csrc/masks.hip): exactly the words and records that mmt_paste_mask_stack into a zeroed stack
+ * followed by mmt_mask_pack give, bit for bit -- the same geometry and bilinear code, built without FMA contraction -- but the
+ * [D][IH][IW] bytes are never allocated, cleared, written or re-read.  prob [D][M][M], boxes [D][4] as mmt_paste_mask_stack takes
+ * them; every word of words [D][ceil(IH*IW/64)] and every record is written, zeros included: the caller clears nothing.  No
+ * atomics.  Besides the refusals above (D for the count): MMT_EINVAL for M <= 0 or (M+2)^2 * 4 > 64 KiB (the padded plane is kept
+ * in LDS). */
+int mmt_paste_mask_words(const float* prob /*[D][M][M]*/, const float* boxes /*[D][4]*/, int D, int M, int IH, int IW,
+                         float thresh, uint64_t* words /*[D][ceil(IH*IW/64)]*/, int32_t* rec /*[D][MMT_MASK_REC_INTS]*/,
+                         void* stream);
 /* expand from runs (pycoco/_mask.pyx:160 decode): ends = the concatenated INCLUSIVE PREFIX SUMS of every mask's run lengths
  * (runs alternate 0 / 1 starting with zeros; the host parses the strings and checks that the last sum is H*W), mask i owns
  * ends[off[i] .. off[i+1]) -> the same words and records.  Positions behind a mask's last sum stay zero. */

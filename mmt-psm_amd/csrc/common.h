@@ -20,3 +20,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+
+// csrc/maskeval.hip: the records (area, extent, wrap) of n finished stacks of mask words, one launch; arguments checked by the caller
+int mmt_mask_records(const uint64_t* words, int n, int H, int W, int32_t* rec, hipStream_t s);

@@ -256,6 +256,11 @@ static int records(const u64* words, int n, int H, int W, int32_t* rec, hipStrea
   return 0;
 }
 
+// for mmt_paste_mask_words (csrc/masks.hip), whose kernel writes words and leaves the records to this one
+int mmt_mask_records(const uint64_t* words, int n, int H, int W, int32_t* rec, hipStream_t s) {
+  return records((const u64*)words, n, H, W, rec, s);
+}
+
 extern "C" int mmt_mask_pack(const uint8_t* masks, int n, int H, int W, uint64_t* words, int32_t* rec, void* stream) {
   if (n < 0 || n > MAX_MASKS || bad_size(H, W)) return MMT_EINVAL;
   if (n == 0) return 0;

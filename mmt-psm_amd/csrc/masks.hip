@@ -12,6 +12,61 @@
 #include "common.h"
 
 // ------------------------------------------------------------------------------------ paste
+// The geometry and the bilinear value live in two functions that every paste kernel calls (the integral map, the byte stack and
+// the mask words), so the forms cannot drift apart by a bit.
+struct PasteGeom {
+  int x0, y0;                  // the expanded integer box's corner (may lie outside the canvas)
+  int cx0, cx1, cy0, cy1;      // the box clipped to the canvas, half open
+  float sx, sy;                // source pixels per destination pixel
+};
+
+// expand_boxes (inference.py:120-135) with scale = (M+2)/M, then .to(int32) (truncation); false: nothing lands on the canvas
+__device__ __forceinline__ bool paste_geom(const float* __restrict__ box, int M, int IH, int IW, PasteGeom& g) {
+  const int P = M + 2;
+  const float scale = (float)(M + 2) / (float)M;
+  const float bx0 = box[0], by0 = box[1], bx1 = box[2], by1 = box[3];
+  float wh = (bx1 - bx0) * .5f, hh = (by1 - by0) * .5f;
+  const float xc = (bx1 + bx0) * .5f, yc = (by1 + by0) * .5f;
+  wh *= scale; hh *= scale;
+  const int x0 = (int)(xc - wh), x1 = (int)(xc + wh), y0 = (int)(yc - hh), y1 = (int)(yc + hh);
+  const int w = max(x1 - x0 + 1, 1), h = max(y1 - y0 + 1, 1);
+  g.x0 = x0; g.y0 = y0;
+  g.cx0 = max(x0, 0); g.cx1 = min(x1 + 1, IW); g.cy0 = max(y0, 0); g.cy1 = min(y1 + 1, IH);
+  // F.interpolate(bilinear, align_corners=False): src = (dst+0.5)*in/out - 0.5 clamped at 0
+  g.sy = (float)P / (float)h; g.sx = (float)P / (float)w;
+  return g.cx1 - g.cx0 > 0 && g.cy1 - g.cy0 > 0;
+}
+
+// the resized probability at canvas pixel (xx, yy) of the clipped box; pm = the (M+2)^2 padded probabilities
+__device__ __forceinline__ float paste_value(const float* pm, int P, const PasteGeom& g, int xx, int yy) {
+  const int dy = yy - g.y0, dx = xx - g.x0;
+  float fy = g.sy * ((float)dy + 0.5f) - 0.5f;
+  if (fy < 0.f) fy = 0.f;
+  float fx = g.sx * ((float)dx + 0.5f) - 0.5f;
+  if (fx < 0.f) fx = 0.f;
+  // inside the box fy, fx < P - 0.5; the min only keeps a box of non-finite or overflowing corners inside pm
+  const int iy0 = min((int)fy, P - 1), ix0 = min((int)fx, P - 1);
+  const int iy1 = iy0 + (iy0 < P - 1 ? 1 : 0), ix1 = ix0 + (ix0 < P - 1 ? 1 : 0);
+  const float ly1 = fy - (float)iy0, ly0 = 1.f - ly1, lx1 = fx - (float)ix0, lx0 = 1.f - lx1;
+  return ly0 * (lx0 * pm[iy0 * P + ix0] + lx1 * pm[iy0 * P + ix1]) +
+         ly1 * (lx0 * pm[iy1 * P + ix0] + lx1 * pm[iy1 * P + ix1]);
+}
+
+// detection d's M x M plane, zero-padded by one, into LDS; PROB: the input holds probabilities already (one class)
+template <bool PROB>
+__device__ __forceinline__ void paste_fill(float* pm, const float* __restrict__ logits, int d, int M, int NC, int lab) {
+  const int P = M + 2;
+  for (int i = threadIdx.x; i < P * P; i += 256) {
+    const int y = i / P, x = i - y * P;
+    float v = 0.f;
+    if (y >= 1 && y <= M && x >= 1 && x <= M) {
+      const float z = logits[(((long)d * M + (y - 1)) * M + (x - 1)) * NC + lab];
+      v = PROB ? z : 1.f / (1.f + expf(-z));
+    }
+    pm[i] = v;
+  }
+}
+
 // STACK: the evaluator's form (mask_head/inference.py:209-246 as pap_eval.py:107-109 calls it): the input holds the
 // PROBABILITIES of the predicted class ((D, 1, M, M): MaskPostProcessor's `mask` field), and every detection gets its own
 // binary canvas stack[d] (bytes) instead of a vote in the integral map of its image.
@@ -24,49 +79,78 @@ __global__ __launch_bounds__(256) void paste_kernel(const float* __restrict__ lo
   const int d = blockIdx.x;
   if (!STACK && img[d] < 0) return;   // a row behind its image's count in a fixed-capacity detection list: no vote
   const int P = M + 2;
-  const int lab = STACK ? 0 : labels[d];
-  for (int i = threadIdx.x; i < P * P; i += 256) {
-    const int y = i / P, x = i - y * P;
-    float v = 0.f;
-    if (y >= 1 && y <= M && x >= 1 && x <= M) {
-      const float z = logits[(((long)d * M + (y - 1)) * M + (x - 1)) * NC + lab];
-      v = STACK ? z : 1.f / (1.f + expf(-z));
-    }
-    pm[i] = v;
-  }
+  paste_fill<STACK>(pm, logits, d, M, NC, STACK ? 0 : labels[d]);
   __syncthreads();
-  // expand_boxes (inference.py:120-135) with scale = (M+2)/M, then .to(int32) (truncation)
-  const float scale = (float)(M + 2) / (float)M;
-  const float bx0 = boxes[d * 4 + 0], by0 = boxes[d * 4 + 1], bx1 = boxes[d * 4 + 2], by1 = boxes[d * 4 + 3];
-  float wh = (bx1 - bx0) * .5f, hh = (by1 - by0) * .5f;
-  const float xc = (bx1 + bx0) * .5f, yc = (by1 + by0) * .5f;
-  wh *= scale; hh *= scale;
-  const int x0 = (int)(xc - wh), x1 = (int)(xc + wh), y0 = (int)(yc - hh), y1 = (int)(yc + hh);
-  const int w = max(x1 - x0 + 1, 1), h = max(y1 - y0 + 1, 1);
-  const int cx0 = max(x0, 0), cx1 = min(x1 + 1, IW), cy0 = max(y0, 0), cy1 = min(y1 + 1, IH);
-  const int cw = cx1 - cx0, ch = cy1 - cy0;
-  if (cw <= 0 || ch <= 0) return;
-  // F.interpolate(bilinear, align_corners=False): src = (dst+0.5)*in/out - 0.5 clamped at 0
-  const float sy = (float)P / (float)h, sx = (float)P / (float)w;
+  PasteGeom g;
+  if (!paste_geom(boxes + d * 4, M, IH, IW, g)) return;
+  const int cw = g.cx1 - g.cx0, ch = g.cy1 - g.cy0;
   int* out = STACK ? nullptr : seg + (long)img[d] * IH * IW;
   unsigned char* outb = STACK ? stack + (long)d * IH * IW : nullptr;
   for (int i = threadIdx.x; i < cw * ch; i += 256) {
-    const int yy = cy0 + i / cw, xx = cx0 + i % cw;
-    const int dy = yy - y0, dx = xx - x0;
-    float fy = sy * ((float)dy + 0.5f) - 0.5f;
-    if (fy < 0.f) fy = 0.f;
-    float fx = sx * ((float)dx + 0.5f) - 0.5f;
-    if (fx < 0.f) fx = 0.f;
-    const int iy0 = (int)fy, ix0 = (int)fx;
-    const int iy1 = iy0 + (iy0 < P - 1 ? 1 : 0), ix1 = ix0 + (ix0 < P - 1 ? 1 : 0);
-    const float ly1 = fy - (float)iy0, ly0 = 1.f - ly1, lx1 = fx - (float)ix0, lx0 = 1.f - lx1;
-    const float v = ly0 * (lx0 * pm[iy0 * P + ix0] + lx1 * pm[iy0 * P + ix1]) +
-                    ly1 * (lx0 * pm[iy1 * P + ix0] + lx1 * pm[iy1 * P + ix1]);
-    if (v > thresh) {
+    const int yy = g.cy0 + i / cw, xx = g.cx0 + i % cw;
+    if (paste_value(pm, P, g, xx, yy) > thresh) {
       if (STACK) outb[(long)yy * IW + xx] = 1;
       else atomicAdd(out + (long)yy * IW + xx, 1);
     }
   }
+}
+
+// WORDS: the same paste written straight into the run-length codec's mask words (csrc/maskeval.hip: bit k = pixel
+// (y = k % IH, x = k / IH), tail bits zero) -- what mmt_paste_mask_stack into a zeroed stack followed by mmt_mask_pack gives,
+// without the bytes.  A thread owns one word and stores it, zero or not, so the caller clears nothing and no two threads meet.
+// Most words lie in columns the box does not reach: a block of such words never fills the LDS.  The few words that do hold
+// pixels of the clipped box are evaluated by their whole wave, one word at a time: lane = bit, one bilinear value per lane, and
+// a ballot is the word (a thread that walked its own 64 bits would keep the 63 lanes beside it waiting).
+__global__ __launch_bounds__(256) void paste_words_kernel(const float* __restrict__ prob, const float* __restrict__ boxes, int M,
+                                                          int IH, int IW, long nw, float thresh,
+                                                          unsigned long long* __restrict__ words) {
+  extern __shared__ float pm[];  // (M+2)^2 padded probabilities
+  const int d = blockIdx.y, P = M + 2;
+  const long hw = (long)IH * IW;
+  PasteGeom g;
+  const bool some = paste_geom(boxes + d * 4, M, IH, IW, g);
+  // columns [cx0, cx1) are positions [p0, p1) of the flattening; everything before and behind them is zero.  The block's words
+  // cover positions [b0, b1) (block-uniform), a thread's word [kw, ke): compared as positions, so that the great majority of
+  // threads, whose word is a plain zero, never divide
+  const long p0 = (long)g.cx0 * IH, p1 = (long)g.cx1 * IH;
+  const long b0 = blockIdx.x * 256L * 64, b1 = min(b0 + 256L * 64, hw);
+  const bool hit = some && b0 < p1 && b1 > p0;
+  const long j = blockIdx.x * 256L + threadIdx.x;
+  const long kw = j * 64, ke = min(kw + 64, hw);
+  unsigned long long w = 0;
+  if (hit) {   // whole blocks, so every wave below is complete for its ballots and shuffles
+    paste_fill<true>(pm, prob, d, M, 1, 0);
+    __syncthreads();
+    // does this thread's word hold a pixel of the clipped box?  Its first pixel is (x0, y0)
+    int x0 = 0, y0 = 0;
+    bool mine = false;
+    if (kw < p1 && ke > p0) {   // (ke > p0 >= 0 leaves out the threads behind the last word)
+      x0 = (int)((unsigned)kw / (unsigned)IH); y0 = (int)(kw - (long)x0 * IH);   // (kw < IH * IW < 2^31)
+      int x = x0, y = y0;
+      for (long k = kw; k < ke && x < g.cx1 && !mine;) {   // the word column by column: rows [y, y + len) of column x
+        const int len = (int)min((long)(IH - y), ke - k);
+        mine = x >= g.cx0 && max(y, g.cy0) < min(y + len, g.cy1);
+        k += len; x++; y = 0;
+      }
+    }
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(mine);   // wave-uniform
+    while (todo) {
+      const int src = __builtin_ctzll(todo);
+      todo &= todo - 1;
+      // lane b is bit b of lane src's word: position kw_src + b = pixel (xx, yy)
+      int xx = __shfl(x0, src, 64), yy = __shfl(y0, src, 64) + lane;
+      if (yy >= IH) {
+        if (IH >= 64) { yy -= IH; xx++; }   // (yy < IH + 64: one column further at the most)
+        else { const int q = yy / IH; xx += q; yy -= q * IH; }
+      }
+      // (a position behind the last pixel has xx >= IW >= cx1: the tail bits stay zero)
+      const bool in = xx >= g.cx0 && xx < g.cx1 && yy >= g.cy0 && yy < g.cy1;
+      const unsigned long long bits = __ballot(in && paste_value(pm, P, g, xx, yy) > thresh);
+      if (lane == src) w = bits;
+    }
+  }
+  if (j < nw) words[(long)d * nw + j] = w;
 }
 
 extern "C" int mmt_paste_masks(const float* logits, const int32_t* labels, const float* boxes, const int32_t* img,
@@ -88,6 +172,21 @@ extern "C" int mmt_paste_mask_stack(const float* prob, const float* boxes, int D
                      (const int*)nullptr, M, 1, IH, IW, thresh, (int*)nullptr, stack);
   MMT_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int mmt_paste_mask_words(const float* prob, const float* boxes, int D, int M, int IH, int IW, float thresh,
+                                    uint64_t* words, int32_t* rec, void* stream) {
+  const long P = (long)M + 2;
+  if (D < 0 || D > 65535 || M <= 0 || P * P * (long)sizeof(float) > 65536 || IH <= 0 || IW <= 0 ||
+      (long)IH * (long)IW >= (1L << 31))
+    return MMT_EINVAL;
+  if (D == 0) return 0;
+  if (!prob || !boxes || !words || !rec) return MMT_EINVAL;
+  const long nw = ((long)IH * IW + 63) >> 6;
+  hipLaunchKernelGGL(paste_words_kernel, dim3(mmt_cdiv(nw, 256), D), dim3(256), (size_t)(P * P) * sizeof(float),
+                     (hipStream_t)stream, prob, boxes, M, IH, IW, nw, thresh, (unsigned long long*)words);
+  MMT_LAUNCH_CHECK();
+  return mmt_mask_records(words, D, IH, IW, rec, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------ polygons

@@ -191,6 +191,7 @@ _SIGS = {
     "mmt_paste_mask_stack": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
     "mmt_polygon_targets": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "mmt_mask_pack": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "mmt_paste_mask_words": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "mmt_mask_expand": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "mmt_mask_transition_counts": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_mask_transition_positions": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
@@ -2863,6 +2864,18 @@ def mask_pack(masks):
     n, H, W = masks.shape
     words, rec = _mask_buffers(n, H, W, masks.device)
     _check(lib().mmt_mask_pack(_p(masks), n, H, W, _p(words), _p(rec), _stream()), "mmt_mask_pack")
+    return words, rec
+
+
+def paste_mask_words(prob, boxes, IH, IW, thresh):
+    """prob (D,1,M,M) or (D,M,M) probabilities of the predicted class, boxes (D,4) -> (words, records): what
+    mask_pack(paste_mask_stack(...)[:, 0]) gives, bit for bit, without the (D, IH, IW) bytes (mmt_paste_mask_words)"""
+    prob = _dev(prob, "prob").float().contiguous()
+    D, M = prob.shape[0], prob.shape[-1]
+    boxes = _dev(boxes, "boxes").float().contiguous()
+    words, rec = _mask_buffers(D, IH, IW, prob.device)
+    _check(lib().mmt_paste_mask_words(_p(prob), _p(boxes), D, M, IH, IW, float(thresh), _p(words), _p(rec), _stream()),
+           "mmt_paste_mask_words")
     return words, rec
 
 

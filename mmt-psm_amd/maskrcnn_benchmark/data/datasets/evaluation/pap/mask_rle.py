@@ -157,12 +157,29 @@ def encode_device(masks):
     if h * w == 0:
         return [{"size": [h, w], "counts": _to_string([0]).encode("ascii")} for _ in range(n)]
     words, _ = H.mask_pack(masks)
+    return _strings_of_words(H, words, h, w)
+
+
+def _strings_of_words(H, words, h, w):
+    """mask words on the device -> the list of RLE dicts; only the transition counts and positions cross to the host"""
     counts, pos = H.mask_transitions(words, h, w)
     pos, out, at = pos.numpy(), [], 0
     for c in counts.tolist():
         out.append({"size": [h, w], "counts": _to_string(_runs_of_positions(pos[at:at + c], h * w)).encode("ascii")})
         at += c
     return out
+
+
+def encode_pasted_device(prob, boxes, h, w, thresh=0.5):
+    """M x M probabilities (D, 1, M, M) or (D, M, M) and their boxes (D, 4) in an h x w image -> what
+    encode_device(paste_mask_stack(prob, boxes, h, w, thresh)) returns, byte for byte, with the paste written straight into
+    the codec's words (mmt_paste_mask_words): the (D, h, w) byte stack is never made"""
+    H = _backend()
+    h, w = int(h), int(w)
+    if int(prob.shape[0]) == 0:
+        return []
+    words, _ = H.paste_mask_words(prob, boxes, h, w, thresh)
+    return _strings_of_words(H, words, h, w)
 
 
 def _expand_device(H, rles, device):

@@ -358,8 +358,9 @@ def prepare_for_pap_segmentation(predictions, dataset, on_device=False):
     lists (pap_eval.py:79-143).  Masks that are not window-sized yet -- the M x M probabilities of MaskPostProcessor, as in a
     predictions.pth -- are pasted first, as the reference does (pap_eval.py:107-109: Masker(threshold=0.5, padding=1)); the
     paste is the device kernel `mmt_paste_mask_stack`, so that case needs the GPU (no host implementation: it raises).
-    on_device=True: the masks, pasted or not, stay on (or go to) the GPU and are encoded by `mask_rle.encode_device`; only the
-    positions of their run boundaries come back.  It raises without a GPU."""
+    on_device=True: window-sized masks stay on (or go to) the GPU and are encoded by `mask_rle.encode_device`; M x M masks are
+    pasted and encoded in one go by `mask_rle.encode_pasted_device` (`mmt_paste_mask_words`: the same strings, without the byte
+    stack).  Only the positions of the run boundaries come back.  It raises without a GPU."""
     if on_device:
         maskUtils._backend()
     masker = None
@@ -375,6 +376,7 @@ def prepare_for_pap_segmentation(predictions, dataset, on_device=False):
             gts.append({"image_id": original_id, "category_id": labels[k], "segmentation": rle, "bbox": boxes[k]})
         prediction = prediction.resize((dataset.maxWS, dataset.maxWS))
         masks = prediction.get_field("mask")
+        rles = None
         if tuple(masks.shape[-2:]) != (dataset.maxWS, dataset.maxWS):
             if not torch.cuda.is_available():
                 raise RuntimeError("predictions carry %dx%d masks and pasting them into the %d-pixel window runs on the GPU "
@@ -383,13 +385,14 @@ def prepare_for_pap_segmentation(predictions, dataset, on_device=False):
                 from maskrcnn_benchmark.modeling.roi_heads.mask_head.mask_head import Masker
                 masker = Masker(threshold=0.5, padding=1)
             dev = torch.device("cuda", torch.cuda.current_device())
-            masks = masker.forward_single_image(masks.to(dev), prediction.to(dev))
-            if not on_device:
-                masks = masks.cpu()
+            if on_device:   # pasted straight into the codec's words: the same strings, no (D, maxWS, maxWS) bytes in between
+                rles = masker.rle_single_image(masks.to(dev), prediction.to(dev))
+            else:
+                masks = masker.forward_single_image(masks.to(dev), prediction.to(dev)).cpu()
         scores = prediction.get_field("scores").tolist()
         labels = [dataset.contiguous_category_id_to_json_id[i] for i in prediction.get_field("labels").tolist()]
         boxes = prediction.bbox.tolist()
-        if on_device:
+        if on_device and rles is None:
             masks = torch.as_tensor(masks).to(torch.device("cuda", torch.cuda.current_device()))
             rles = maskUtils.encode_device(masks.to(torch.uint8))   # (the host path's np.asarray(..., dtype=np.uint8))
         for k, m in enumerate(masks):

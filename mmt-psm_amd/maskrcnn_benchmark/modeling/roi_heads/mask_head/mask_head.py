@@ -240,11 +240,13 @@ class MaskPostProcessor(nn.Module):
     def forward(self, x, boxes):
         labels = torch.cat([b.get_field("labels") for b in boxes])
         per = [len(b) for b in boxes]
-        if self.masker is not None:
+        if self.masker is not None and not isinstance(self.masker, DetectionMasker):
             segs = self.masker(x, labels, boxes)
         else:
             prob = x.sigmoid()[torch.arange(x.shape[0], device=x.device), labels][:, None]
             segs = prob.split(per, 0)
+            if self.masker is not None:   # POSTPROCESS_MASKS (inference.py:62-63): the same rows, pasted into their image
+                segs = self.masker(segs, boxes)
         out = []
         for s, b in zip(segs, boxes):
             r = BoxList(b.bbox, b.size, "xyxy")
@@ -294,6 +296,24 @@ class Masker(object):
             return torch.zeros((0, 1, h, w), dtype=torch.uint8, device=masks.device)
         return H.paste_mask_stack(masks, boxes.convert("xyxy").bbox, h, w, self.threshold)
 
+    def rle_single_image(self, masks, boxes):
+        """the run-length twin of forward_single_image: the list of RLE dicts that mask_rle.encode_device gives for its stack,
+        byte for byte, pasted straight into the codec's words (`mmt_paste_mask_words`); zero detections give []"""
+        from maskrcnn_benchmark.data.datasets.evaluation.pap import mask_rle
+        w, h = boxes.size
+        if len(boxes) == 0:
+            return []
+        return mask_rle.encode_pasted_device(masks, boxes.convert("xyxy").bbox, h, w, self.threshold)
+
+
+class DetectionMasker(Masker):
+    """Masker.__call__ of the reference (mask_head/inference.py:231-246) as MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS uses it: per
+    image, the (D, 1, M, M) probabilities of the predicted class -> the uint8 (D, 1, h, w) stack of pasted binary masks, (w, h)
+    the BoxList's size.  Images of one batch may differ in size."""
+
+    def __call__(self, probs, boxes):
+        return [self.forward_single_image(p, b) for p, b in zip(probs, boxes)]
+
 
 class IntegralMask(object):
     """stands in for the (D,1,H,W) uint8 stack of the reference: `.sum(0)[0]` gives the integral mask"""
@@ -307,7 +327,7 @@ class IntegralMask(object):
 
 
 def make_roi_mask_post_processor(cfg):
-    return MaskPostProcessor(Masker(cfg.MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS_THRESHOLD, 1)
+    return MaskPostProcessor(DetectionMasker(cfg.MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS_THRESHOLD, 1)
                              if cfg.MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS else None)
 
 
