@@ -810,7 +810,9 @@ def get_deterministic():
 def reset_adaptive_state():
     """forget what earlier launches taught the host side about tensors' ranges -- the sites' fp16 / bf16 states, the delayed scales of
     f16_split, the producers' plane scales: the state a fresh process starts from (MTtrainer calls this when it is built in
-    deterministic mode, so that a second trainer of a process repeats the first)"""
+    deterministic mode, so that a second trainer of a process repeats the first, after a checkpoint is written in that mode and when a
+    run is resumed: a checkpoint is a restart point).  rb_reset moves _RB_EPOCH, which is part of a launch plan's key:
+    no plan recorded before, with a site's scale address in it, is replayed afterwards"""
     _F16SITE.clear()
     _SITES.clear()
     rb_reset()

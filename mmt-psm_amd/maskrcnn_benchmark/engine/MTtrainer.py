@@ -7,9 +7,11 @@ storage; with WORLD_SIZE > 1 the student gradients are averaged by ONE RCCL all-
 buffer (new functionality: the reference has no gradient synchronisation at all)."""
 import logging
 import os
+import random
 import time
 from functools import partial
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -17,6 +19,7 @@ from maskrcnn_benchmark import _hip as H
 from maskrcnn_benchmark.engine.flat import flatten_model
 from maskrcnn_benchmark.layers import fused
 from maskrcnn_benchmark.utils.miscellaneous import sigmoid_rampdown, sigmoid_rampup
+from maskrcnn_benchmark.utils.model_serialization import load_state_dict, refresh_derived, strip_prefix_if_present
 
 
 # priority -1: HIP maps streams of one priority onto a few hardware queues round-robin; once RCCL has created its own
@@ -295,6 +298,23 @@ def teacher_checksum(flat):
     return flat.data.view(torch.int32).to(torch.int64).sum()
 
 
+RESUME_FORMAT = 1   # of the `trainer` entry MTtrainer.save_model adds to the student's checkpoint file
+
+
+def _word_sum(t):
+    """`teacher_checksum` of any fp32 buffer, as a Python int"""
+    return int(t.view(torch.int32).to(torch.int64).sum())
+
+
+def _name_problems(what, saved, have):
+    """-> one line per name of `saved` / `have` (name -> shape) that the other side lacks or holds in another shape"""
+    out = ["%s %s: in this model, not in the file" % (what, n) for n in sorted(set(have) - set(saved))]
+    out += ["%s %s: in the file, not in this model" % (what, n) for n in sorted(set(saved) - set(have))]
+    out += ["%s %s: shape %s in the file, %s in this model" % (what, n, list(saved[n]), list(have[n]))
+            for n in sorted(set(saved) & set(have)) if tuple(saved[n]) != tuple(have[n])]
+    return out
+
+
 def check_teacher_identity(flat_t):
     """the teachers are never exchanged -- they stay identical on all ranks because every rank applies the
     same EMA to the same (all-reduced) student from the same initial weights.  Asserted here with ONE small collective:
@@ -316,10 +336,14 @@ class MTtrainer(object):
         self.logger = logging.getLogger("maskrcnn_benchmark.trainer")
         self.scheduler, self.optimizer = scheduler, optimizer
         self.max_iter = len(data_loader["source"])
-        self.start_iter = 0
+        self.start_iter = 0          # `resume` moves it behind the checkpoint's iteration
+        self.last_iteration = -1     # the last completed iteration (what a checkpoint records)
+        self.unlabeled_seen = 0      # batches drawn from the unlabeled loader so far
+        self._unl_skip = 0           # batches the first use of the unlabeled loader after a `resume` passes over
         self.student, self.teacher = model_s, model_t
         self.student_bs, self.teacher_bs = cfg.MT.AUG_S, cfg.MT.AUG_K
-        self.device = torch.device("cuda", torch.cuda.current_device())
+        # (without a device: the host-side halves -- state_dict, resume and their refusals -- on CPU tensors; a step needs the device)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.checkpoint_period, self.ckpt_s, self.ckpt_t = checkpoint_period, ckpt_s, ckpt_t
         self.lambda_value, self.alpha = cfg.MT.LAMBDA, cfg.MT.ALPHA
         self.start_mt = cfg.MT.START_MT
@@ -479,6 +503,7 @@ class MTtrainer(object):
             if self.teacher_check_period > 0 and iteration % self.teacher_check_period == 0:
                 self.sync_teacher()
                 check_teacher_identity(self.flat_t)
+        self.last_iteration = iteration
         return losses_dict
 
     def _pad_mt_keys(self, losses):
@@ -520,19 +545,174 @@ class MTtrainer(object):
 
     def _next_unlabeled(self):
         if self._unl_iter is None:
+            skip, self._unl_skip = self._unl_skip, 0
+            if skip and hasattr(self.dataloader_u, "fast_forward"):
+                self.dataloader_u.fast_forward(skip)   # (a loader that can seek: told before it is iterated)
+                skip = 0
             self._unl_iter = iter(self.dataloader_u)
+            for _ in range(skip):                      # after a resume: where the interrupted run stood in the loader's current pass
+                next(self._unl_iter)
         try:
-            return next(self._unl_iter)[0]
+            batch = next(self._unl_iter)[0]
         except StopIteration:
             self._unl_iter = iter(self.dataloader_u)
-            return next(self._unl_iter)[0]
+            batch = next(self._unl_iter)[0]
+        self.unlabeled_seen += 1
+        return batch
 
     def save_model(self, iteration=0, final=False):
+        """the student's checkpoint (the reference's layout: model / optimizer / scheduler) with two extra entries, `iteration` and
+        `trainer` (`state_dict`: everything `resume` needs); the teacher's own file as before.  Deterministic mode: the checkpoint is
+        a restart point -- the adaptive arithmetic state is dropped once the file is written, so the step after it starts from what a
+        resumed process starts from."""
         self.sync_teacher()
         name = "model_final" if final else "model_{:07d}".format(iteration)
-        self.ckpt_s.save(name)
+        extra = {"iteration": iteration, "trainer": self.state_dict(iteration)}
+        if getattr(self.ckpt_s, "optimizer", None) is self.optimizer:
+            # the file's own `optimizer` / `scheduler` entries are the same objects: the momentum is stored once
+            extra["optimizer"], extra["scheduler"] = extra["trainer"]["optimizer"], extra["trainer"]["scheduler"]
+        self.ckpt_s.save(name, **extra)
         if iteration > self.start_mt and self.ckpt_t is not None:
             self.ckpt_t.save("t_" + name)
+        if H.get_deterministic():
+            H.reset_adaptive_state()
+            self._forget_stem_forms()
+
+    # ---- checkpoints as restart points
+    def _forget_stem_forms(self):
+        """the stems' cached space-to-depth filters and their planes are made again from the weights as they are NOW.  A frozen stem
+        caches them by the parameter's version alone, and the EMA rewrites the teacher's whole flat buffer through raw pointers -- the
+        frozen region too, where alpha t + (1 - alpha) s with t == s still rounds: the teacher's filter bytes drift by an ulp now and
+        then while its cached form keeps the values of its first use.  A resumed process derives the form from the saved bytes, so a
+        restart point makes the continuing run do the same."""
+        for model in (self.student, self.teacher):
+            stem = getattr(getattr(getattr(model, "backbone", None), "body", None), "stem", None)
+            if stem is not None:
+                stem._s2d_key = None
+    def rng_state(self):
+        """the six random streams a step can draw from, as CPU tensors and plain values: the student's and the teacher's device
+        generators, torch's CPU generator, the current device's default generator, Python's `random`, `numpy.random`"""
+        name, keys, pos, has_gauss, cached = np.random.get_state()
+        version, words, gauss = random.getstate()
+        on_device = self.device.type == "cuda"
+        return {"gen_s": self.gen_s.get_state() if self.gen_s is not None else None,
+                "gen_t": self.gen_t.get_state() if self.gen_t is not None else None,
+                "torch_cpu": torch.get_rng_state(),
+                "torch_device": torch.cuda.get_rng_state(self.device) if on_device else None,
+                "python": [int(version), [int(w) for w in words], gauss],
+                "numpy": {"name": str(name), "keys": torch.from_numpy(keys.astype(np.int64)), "pos": int(pos),
+                          "has_gauss": int(has_gauss), "cached_gaussian": float(cached)}}
+
+    def set_rng_state(self, state):
+        """`rng_state` restored; a stream the saving process did not have (no device) is left alone"""
+        if state.get("gen_s") is not None and self.gen_s is not None:
+            self.gen_s.set_state(state["gen_s"])
+            self.gen_t.set_state(state["gen_t"])
+        torch.set_rng_state(state["torch_cpu"])
+        if state.get("torch_device") is not None and self.device.type == "cuda":
+            torch.cuda.set_rng_state(state["torch_device"], self.device)
+        version, words, gauss = state["python"]
+        random.setstate((version, tuple(words), gauss))
+        n = state["numpy"]
+        np.random.set_state((n["name"], n["keys"].numpy().astype(np.uint32), n["pos"], n["has_gauss"], n["cached_gaussian"]))
+
+    def state_dict(self, iteration=None):
+        """what `save_model` stores under `trainer` (plain values and CPU tensors): the whole run state that is not the student's
+        `model` entry.  iteration: the last completed one (default: the last `train_step`'s).  Collective when torch.distributed is
+        initialised: every rank's random streams are gathered, one entry per rank."""
+        self.sync_teacher()
+        rng = [self.rng_state()]
+        if dist.is_available() and dist.is_initialized():
+            rng = [None] * dist.get_world_size()
+            dist.all_gather_object(rng, self.rng_state())
+        teacher = self.teacher.state_dict()
+        return {"format": RESUME_FORMAT,
+                "iteration": int(self.last_iteration if iteration is None else iteration),
+                "optimizer": self.optimizer.state_dict(),
+                "scheduler": self.scheduler.state_dict(),
+                "teacher": type(teacher)((k, v.detach().cpu()) for k, v in teacher.items()),
+                "rng": rng,
+                "unlabeled_seen": int(self.unlabeled_seen),
+                "skipped_pairs": int(self.skipped_pairs),
+                "world_size": get_world_size(),
+                "deterministic": bool(H.get_deterministic()),
+                "checksums": self.checksums()}
+
+    def checksums(self):
+        """`teacher_checksum` of the student's flat buffer, its momentum buffer and the teacher's flat buffer, as Python ints"""
+        self.sync_teacher()
+        return {"student": _word_sum(self.flat_s.data), "momentum": _word_sum(self.flat_s.momentum),
+                "teacher": _word_sum(self.flat_t.data)}
+
+    def resume(self, f=None):
+        """continue the run a `save_model` file was written by: student, teacher, momentum, schedule, random streams and counters as
+        they were after the saved iteration -> that iteration (`start_iter` is one more).  f: the file; default: the `last_checkpoint`
+        of the student checkpointer's directory.  Refuses what it cannot restore exactly ("Resuming a run").  The
+        labeled loader is the caller's to position at `start_iter`; the unlabeled one is fast-forwarded on first use."""
+        if f is None:
+            f = self.ckpt_s.get_checkpoint_file() if self.ckpt_s is not None and self.ckpt_s.has_checkpoint() else None
+            if not f:
+                raise FileNotFoundError("resume: no last_checkpoint in %r" % (getattr(self.ckpt_s, "save_dir", None),))
+            # both checkpointers writing into one directory: past START_MT the tag names the teacher's t_<name> file, written second
+            d, base = os.path.split(f)
+            if base.startswith("t_") and os.path.isfile(os.path.join(d, base[2:])):
+                f = os.path.join(d, base[2:])
+        if not os.path.isfile(f):
+            raise FileNotFoundError("resume: no checkpoint file %r" % (f,))
+        ckpt = torch.load(f, map_location=torch.device("cpu"))
+        tr = ckpt.get("trainer") if isinstance(ckpt, dict) else None
+        if not isinstance(tr, dict) or "model" not in ckpt:
+            raise ValueError("resume: %s has no `trainer` entry -- a checkpoint of the reference, or one written before runs could be "
+                             "resumed, holds the weights only: load those with Checkpointer.load and start at iteration 0" % f)
+        if tr.get("format") != RESUME_FORMAT:
+            raise ValueError("resume: %s holds trainer format %r, this build reads format %d" % (f, tr.get("format"), RESUME_FORMAT))
+        # names and shapes, every mismatch in one message, before anything is written
+        model_sd = strip_prefix_if_present(ckpt["model"], prefix="module.")
+        teacher_sd = strip_prefix_if_present(tr["teacher"], prefix="module.")
+        named = dict(self.flat_s._named)
+        shape = lambda d: {k: tuple(v.shape) for k, v in d.items()}
+        bad = _name_problems("student", shape(model_sd), shape(strip_prefix_if_present(self.student.state_dict(), "module.")))
+        bad += _name_problems("teacher", shape(teacher_sd), shape(strip_prefix_if_present(self.teacher.state_dict(), "module.")))
+        bad += _name_problems("momentum", shape(tr["optimizer"].get("momentum_buffers", {})),
+                              {n: tuple(named[n].shape) for n, (o, _) in self.flat_s.index.items() if o < self.flat_s.n_trainable})
+        if bad:
+            raise ValueError("resume: %s does not fit this trainer:\n  %s" % (f, "\n  ".join(bad)))
+        if tr["world_size"] != get_world_size():
+            raise RuntimeError("resume: %s was written at world size %d, this run has %d (the per-rank random streams and the data "
+                               "split do not carry over)" % (f, tr["world_size"], get_world_size()))
+        if bool(tr["deterministic"]) != bool(H.get_deterministic()):
+            self.logger.warning("resume: %s was saved with deterministic mode %s and is resumed with it %s: the bit-for-bit guarantee "
+                                "does not apply to this run", f, "on" if tr["deterministic"] else "off",
+                                "on" if H.get_deterministic() else "off")
+        self.sync_teacher()
+        load_state_dict(self.student, model_sd)
+        load_state_dict(self.teacher, teacher_sd)
+        self.optimizer.load_state_dict(tr["optimizer"])
+        self.scheduler.load_state_dict(tr["scheduler"])
+        self.optimizer.lr_factor = float(tr["optimizer"]["lr_factor"])
+        self.optimizer.param_groups[0]["lr"] = self.optimizer.base_lr * self.optimizer.lr_factor
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        self.set_rng_state(tr["rng"][rank])
+        self.unlabeled_seen, self.skipped_pairs = int(tr["unlabeled_seen"]), int(tr["skipped_pairs"])
+        self._unl_iter = None
+        n_unl = len(self.dataloader_u) if hasattr(self.dataloader_u, "__len__") else 0   # (no unlabeled loader, or one without a length)
+        self._unl_skip = self.unlabeled_seen % n_unl if n_unl else 0
+        self.last_iteration = int(tr["iteration"])
+        self.start_iter = self.last_iteration + 1
+        # everything made from weights, again: packed planes of both buffers, what the models derive, the stem's cached filter forms
+        for model, flat in ((self.student, self.flat_s), (self.teacher, self.flat_t)):
+            flat.refresh_planes()
+            refresh_derived(model)
+        self._forget_stem_forms()
+        # ... and nothing an earlier life of this process learnt about tensor ranges: a resumed run starts where a fresh process does
+        H.reset_adaptive_state()
+        got = self.checksums()
+        for k in ("student", "momentum", "teacher"):
+            if got[k] != int(tr["checksums"][k]):
+                raise RuntimeError("resume: the restored %s buffer does not match %s (checksum %d, saved %d)"
+                                   % (k, f, got[k], int(tr["checksums"][k])))
+        self.logger.info("resumed from %s: iteration %d, %d unlabeled batches seen", f, self.last_iteration, self.unlabeled_seen)
+        return self.last_iteration
 
     def forward_source(self, image, target, features=None):
         return self.student(image.to(self.device), [t.to(self.device) for t in target], features=features)

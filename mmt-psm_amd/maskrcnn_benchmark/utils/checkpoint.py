@@ -1,7 +1,7 @@
 """Checkpoint I/O (reference: utils/checkpoint.py:13-205).
 
 Same file format as the reference -- `torch.save({"model": state_dict, "optimizer": ..., "scheduler": ..., **extra})`
-plus a `last_checkpoint` tag file in the save directory -- and the same state-dict KEYS, so the `model` entry
+plus a `last_checkpoint` tag file in the save directory; the file is written as `<name>.pth.tmp` and renamed -- and the same state-dict KEYS, so the `model` entry
 of a checkpoint moves between the reference and this build in both directions (the one layout difference inside this build,
 fc6's column order, is converted at the state-dict boundary: modeling/roi_heads/box_head/box_head.py).  The `optimizer` entry is
 this build's own (FlatSGD: momentum by parameter name), not torch.optim.SGD's state/param_groups: the fork never restores it
@@ -47,7 +47,16 @@ class Checkpointer(object):
         data.update(kwargs)
         save_file = os.path.join(self.save_dir, "{}.pth".format(name))
         self.logger.info("Saving checkpoint to {}".format(save_file))
-        torch.save(data, save_file)
+        # written under another name and moved into place: a process killed in the middle leaves no partial .pth, and
+        # `last_checkpoint` -- tagged last -- still names the previous, complete file
+        tmp_file = save_file + ".tmp"
+        try:
+            torch.save(data, tmp_file)
+            os.replace(tmp_file, save_file)
+        except BaseException:
+            if os.path.exists(tmp_file):
+                os.remove(tmp_file)
+            raise
         self.tag_last_checkpoint(save_file)
 
     def load_extra_data(self, f=None):
