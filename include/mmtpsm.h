@@ -680,6 +680,29 @@ int mmt_ema_update(float* teacher, const float* student, int64_t n, double alpha
  * p -= lr*buf */
 int mmt_sgd_momentum(float* p, const float* g, float* buf, int64_t n, float lr, float wd, float momentum,
                      int first, void* stream);
+/* The guarded step: the optimiser neither applies a non-finite gradient nor, with max_norm > 0, one whose L2 norm exceeds max_norm
+ * unscaled -- decided on the device, nothing is read back.  mmt_grad_guard reads g[0:n] once, in two launches: stage one writes one
+ * fp64 partial sum of squares per block to ws (MMT_GRAD_GUARD_WS doubles, defined with the workspaces below; the block count is
+ * a function of n alone, the trees inside a lane, a wave and a block have a fixed shape), stage two adds the partials in block
+ * order and writes `state`.  The
+ * total is kept in fp64 because a squared fp32 value cannot overflow there: it is non-finite if and only if an element of g is,
+ * and it does not depend on timing, so every rank draws the same conclusion from the same all-reduced gradient.
+ * state: MMT_GRAD_GUARD_STATE_WORDS 32-bit words, zeroed once by the caller and carried from step to step:
+ *   [0] float  coef: 0 when the total is non-finite (the skip flag is then set); else min(1, max_norm / (norm + 1e-6)) in fp32
+ *              -- torch.nn.utils.clip_grad_norm_'s formula -- when max_norm > 0; else exactly 1.0f
+ *   [1] float  norm: the square root of the total, rounded to fp32 once (NaN or Inf on a skipped step; Inf with coef 0 and no
+ *              skip when finite elements have a norm beyond fp32's range)
+ *   [2] int32  skip this step        [3] int32  steps seen        [4] int32  steps skipped        [5] int32  steps clipped (coef < 1)
+ *   [6] int32  consecutive skips, reset by a step that is not skipped                             [7] reserved
+ * n == 0 is a step with norm 0.  MMT_EINVAL: n < 0, a null pointer, g off the 16-byte grid, ws off the 8-byte grid. */
+#define MMT_GRAD_GUARD_STATE_WORDS 8
+int mmt_grad_guard(const float* g, int64_t n, double* ws, float* state, float max_norm, void* stream);
+/* mmt_sgd_momentum under the verdict mmt_grad_guard left in `state` (read on the device): with the skip flag set every block
+ * returns before its first store -- p and buf keep their bits --; otherwise the update of mmt_sgd_momentum on
+ * g' = round_fp32(g * coef), the product rounded before anything can contract with it, as torch's in-place grad.mul_ leaves it.
+ * coef == 1.0f: the results of mmt_sgd_momentum bit for bit.  g is not modified. */
+int mmt_sgd_momentum_guarded(float* p, const float* g, float* buf, int64_t n, float lr, float wd, float momentum,
+                             int first, const float* state, void* stream);
 
 /* teacher pseudo-mask (mask_head/inference.py:29-65,169-246 + generalized_rcnn.py:129-132): for every detection
  * d of image img[d]: prob = sigmoid(logits[d,:,:,label[d]]) (logits NHWC [D,M,M,NC]), zero-pad by 1, expand the
@@ -754,6 +777,7 @@ int mmt_mask_pair_intersections(const uint64_t* dwords, const int32_t* drec, int
  * 8 + 3 * MMT_RPN_LOSS_MAX_BLOCKS floats (sums [0:3], the caller's `out` may sit at [4:6], block partials from [8]) and adds the
  * partials in block order.  Always returns 0.  mmt_get_deterministic: the flag. */
 #define MMT_COLSUM_MAX_BLOCKS 256      /* mmt_colsum_ordered: ws = MMT_COLSUM_MAX_BLOCKS * C floats */
+#define MMT_GRAD_GUARD_WS 4096         /* mmt_grad_guard: ws = MMT_GRAD_GUARD_WS doubles (its block limit), in either mode */
 #define MMT_MASK_BCE_WS 2048           /* mmt_mask_bce_ordered: MMT_MASK_BCE_WS floats (its block limit) */
 #define MMT_MGD_MAX_BLOCKS 4096        /* mmt_mgd_level_forward_ordered: MMT_MGD_MAX_BLOCKS * (nt + 1); views: * (ns * nt + 1) */
 #define MMT_RPN_LOSS_MAX_BLOCKS 1024

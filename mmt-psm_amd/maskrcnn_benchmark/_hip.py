@@ -187,6 +187,8 @@ _SIGS = {
     "mmt_psm_variance": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_ema_update": [c_void_p, c_void_p, c_int64, c_double, c_void_p],
     "mmt_sgd_momentum": [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_int, c_void_p],
+    "mmt_grad_guard": [c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p],
+    "mmt_sgd_momentum_guarded": [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_int, c_void_p, c_void_p],
     "mmt_paste_masks": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
     "mmt_paste_mask_stack": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
     "mmt_polygon_targets": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
@@ -2805,6 +2807,64 @@ def sgd_momentum(p, g, buf, lr, wd, momentum, first):
     LOOSE.forget(p)
     _check(lib().mmt_sgd_momentum(_p(p), _p(g), _p(buf), p.numel(), float(lr), float(wd), float(momentum),
                                   1 if first else 0, _stream()), "mmt_sgd_momentum")
+
+
+# ---- the guarded step (include/mmtpsm.h: mmt_grad_guard; solver/build.py: FlatSGD.enable_guard)
+GRAD_GUARD_WS, GRAD_GUARD_STATE_WORDS = 4096, 8   # include/mmtpsm.h
+GUARD_COEF, GUARD_NORM, GUARD_SKIP, GUARD_SEEN, GUARD_SKIPPED, GUARD_CLIPPED, GUARD_CONSECUTIVE = range(7)   # the state words
+
+
+def grad_guard_buffers(device):
+    """-> (state, ws) as mmt_grad_guard takes them: state = GRAD_GUARD_STATE_WORDS zeroed fp32 words (words 2..6 hold int32 values:
+    read them through `state.view(torch.int32)`), ws = GRAD_GUARD_WS doubles"""
+    return (torch.zeros((GRAD_GUARD_STATE_WORDS,), dtype=torch.float32, device=device),
+            torch.empty((GRAD_GUARD_WS,), dtype=torch.float64, device=device))
+
+
+def _guard_state(state):
+    _dev(state, "state")
+    if state.dtype != torch.float32 or state.numel() != GRAD_GUARD_STATE_WORDS or not state.is_contiguous() or state.data_ptr() & 15:
+        raise RuntimeError("grad guard: state must be %d contiguous, 16-byte aligned fp32 words (grad_guard_buffers), got %s of %d"
+                           % (GRAD_GUARD_STATE_WORDS, state.dtype, state.numel()))
+    return state
+
+
+def _flat_f32(t, name):
+    _dev(t, name)
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() & 15:
+        raise RuntimeError("%s must be a dense fp32 tensor on the 16-byte grid, got %s%s" % (name, t.dtype, "" if t.is_contiguous() else
+                                                                                           " (not contiguous)"))
+    return t
+
+
+def grad_guard(g, state, ws, max_norm):
+    """the L2 norm of g in fp64 and the step's verdict, into `state` on the device (two launches, no read-back): skip when g holds
+    a non-finite value; max_norm > 0: clip coefficient of torch.nn.utils.clip_grad_norm_; max_norm 0: observe only"""
+    _flat_f32(g, "g")
+    _guard_state(state)
+    _dev(ws, "ws")
+    if ws.dtype != torch.float64 or ws.numel() < GRAD_GUARD_WS or not ws.is_contiguous() or ws.data_ptr() & 15:
+        raise RuntimeError("grad guard: ws must be %d contiguous, 16-byte aligned doubles (grad_guard_buffers), got %s of %d"
+                           % (GRAD_GUARD_WS, ws.dtype, ws.numel()))
+    if g.device != state.device or g.device != ws.device:
+        raise RuntimeError("grad guard: g, state and ws live on different devices")
+    max_norm = float(max_norm)
+    if not max_norm >= 0.0:
+        raise ValueError("grad guard: max_norm must be >= 0 (0: no clipping), got %r" % (max_norm,))
+    _check(lib().mmt_grad_guard(_p(g), g.numel(), _p(ws), _p(state), max_norm, _stream()), "mmt_grad_guard")
+
+
+def sgd_momentum_guarded(p, g, buf, lr, wd, momentum, first, state):
+    """`sgd_momentum` on g * state[coef], or nothing at all when `grad_guard` set the skip flag; g is left as it is"""
+    _flat_f32(p, "p")
+    _flat_f32(g, "g")
+    _flat_f32(buf, "buf")
+    _guard_state(state)
+    if not (p.numel() == g.numel() == buf.numel()):
+        raise RuntimeError("sgd_momentum_guarded: p, g and buf differ in size (%d, %d, %d)" % (p.numel(), g.numel(), buf.numel()))
+    LOOSE.forget(p)
+    _check(lib().mmt_sgd_momentum_guarded(_p(p), _p(g), _p(buf), p.numel(), float(lr), float(wd), float(momentum),
+                                          1 if first else 0, _p(state), _stream()), "mmt_sgd_momentum_guarded")
 
 
 # ------------------------------------------------------------------------------------------ masks

@@ -140,7 +140,11 @@ _DEFAULTS = {
     "DATASETS": {"NO_LABEL": True, "SYN": False},
     "SOLVER": {"BASE_LR": 0.005, "BIAS_LR_FACTOR": 2, "MOMENTUM": 0.9, "WEIGHT_DECAY": 0.0001,
                "WEIGHT_DECAY_BIAS": 0, "GAMMA": 0.1, "STEPS": (5000,), "MAX_ITER": 7000, "WARMUP_FACTOR": 1.0 / 3,
-               "WARMUP_ITERS": 500, "WARMUP_METHOD": "linear", "CHECKPOINT_PERIOD": 50, "IMS_PER_BATCH": 4},
+               "WARMUP_ITERS": 500, "WARMUP_METHOD": "linear", "CHECKPOINT_PERIOD": 50, "IMS_PER_BATCH": 4,
+               # the guarded optimiser step (solver/build.py: FlatSGD.enable_guard; not in the reference): a step whose gradient
+               # holds a NaN or an Inf is skipped; MAX_NORM > 0 also clips by the L2 norm, 0 only skips.  train() gives up after
+               # MAX_CONSECUTIVE_SKIPS skipped steps in a row (a policy default, not a measurement)
+               "GRAD_GUARD": {"ENABLED": False, "MAX_NORM": 0.0, "MAX_CONSECUTIVE_SKIPS": 50}},
     "MT": {"ALPHA": 0.99, "ALPHA_RAMPUP": 0.99, "LAMBDA": 5.0, "RAMPUP_STEP": 250, "RAMPDOWN_STEP": 250,
            "CLS_LOSS": 0.2, "CLS_LOSS_TYPE": "bce", "TEMP": 0.5, "SHARPEN": True, "FLIP": True, "HARD_NEG": True,
            "CLS_BALANCE_WEIGHT": 1.5, "RANK_FILTER": 0.2, "FG_HINT": 1.0, "T_ADAPT": True, "AUG_K": 2, "AUG_S": 1,

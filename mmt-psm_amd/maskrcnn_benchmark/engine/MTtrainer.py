@@ -536,12 +536,28 @@ class MTtrainer(object):
             losses_dict = self.train_step(iteration, data_s, target_s, data_u)
             if iteration % 20 == 0 or iteration == self.max_iter:
                 red = reduce_loss_dict(losses_dict)
-                self.logger.info("iter: %d  %s  lr: %.6f  max mem: %.0f", iteration,
+                guard = self._guard_report()   # (here, where the log line synchronises anyway: the guard's one read-back)
+                self.logger.info("iter: %d  %s  lr: %.6f  max mem: %.0f%s", iteration,
                                  "  ".join("%s: %.4f" % (k, float(v)) for k, v in red.items()),
-                                 self.optimizer.param_groups[0]["lr"], torch.cuda.max_memory_allocated() / 2 ** 20)
+                                 self.optimizer.param_groups[0]["lr"], torch.cuda.max_memory_allocated() / 2 ** 20, guard)
             if self.ckpt_s is not None and iteration > 0 and iteration % self.checkpoint_period == 0:
                 self.save_model(iteration)
         self.logger.info("Total training time: %.1f s", time.time() - t0)
+
+    def _guard_report(self):
+        """the guarded optimiser's part of the log line ("" with the guard off); raises once the run has skipped
+        MAX_CONSECUTIVE_SKIPS steps in a row: every gradient since then was non-finite, and the weights have not moved.  The same
+        on every rank: the verdicts come from the all-reduced gradient."""
+        if getattr(self.optimizer, "guard", None) is None:
+            return ""
+        st = self.optimizer.guard_stats()
+        limit = self.optimizer.guard["max_consecutive_skips"]
+        if st["consecutive"] >= limit:
+            raise RuntimeError("the last %d optimiser steps in a row were skipped for a non-finite gradient (SOLVER.GRAD_GUARD."
+                               "MAX_CONSECUTIVE_SKIPS %d; %d of %d steps skipped in all): the run has diverged -- resume from a "
+                               "checkpoint with a lower learning rate or a SOLVER.GRAD_GUARD.MAX_NORM"
+                               % (st["consecutive"], limit, st["skipped"], st["seen"]))
+        return "  grad_norm: %.4f  skipped: %d  clipped: %d" % (st["norm"], st["skipped"], st["clipped"])
 
     def _next_unlabeled(self):
         if self._unl_iter is None:
