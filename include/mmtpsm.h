@@ -445,6 +445,36 @@ int mmt_get_conv_precision(void);
 int mmt_stem_fused(const float* x, int N, int H, int W, const float* w_s2d, const void* w_planes, long w_plane_stride,
                    const float* s_w /*device*/, const float* scale, const float* shift, const float* x_slot /*device*/, float* y,
                    float* y_slot /*device, zeroed, or NULL*/, void* stream);
+/* A frozen layer1 bottleneck's conv2 and conv3 as one launch (csrc/conv_stem.hip; reference modeling/backbone/resnet.py:254-274 with
+ * 64 bottleneck and 256 output channels, stride 1, forward only): out = relu(conv1x1(relu(conv3x3(x) * scale2 + shift2), w3) * scale3 +
+ * shift3 + res).  x [N][H][W][64], res / out [N][H][W][256], fp32 NHWC; w2 [64][3][3][64] and w3 [256][64] in fp32 (exact path) and
+ * as packed fp16 planes with their device scales (mmt_pack_weight_f16); x_slot: the 33-float statistics slot of x (scale and range
+ * guard, as in mmt_conv_forward_f16x2).  The 3x3's output o2 never reaches memory; it is split with the scale *o2_scale, a power of
+ * two the CALLER chose before the values exist (the producing site's, as for mmt_conv_args.y_rb), and every tile tests its own o2
+ * against it: a tile that leaves the fp16 range at that scale computes its 1x1 products with fp32 FMAs.  The caller must NOT pass
+ * a site that has no scale yet: a site's initial 1.0 is a scale like any other here (the tile test decides with it: accuracy
+ * holds, but tiles whose values it does not fit run at the exact path's speed) -- the binding gives a site's first step to the two
+ * launches, whose conv2 records the maximum through mmt_conv_args.y_amax_next.  A scale that is
+ * not a positive number (0, negative, NaN) sends every tile to the exact path.  o2_scale_is_amax != 0:
+ * *o2_scale is a maximum of |o2| instead, the scale is derived from it as the un-fused launch would and no tile test is made (then
+ * `out` is bit-identical to mmt_conv_forward_f16x2 on conv2 followed by conv3).  o2_amax_next (optional): receives max |o2| like
+ * mmt_conv_args.y_amax_next; out_slot (optional, zeroed): statistics of `out` like y_amax with y_amax_stats.  Mode 3 only;
+ * N * H * W < 2^21.
+ * w1_planes != NULL: conv1 of the NEXT bottleneck (1x1, 256 -> 64 channels, FrozenBN, ReLU; stride 1) behind conv3 in the same launch --
+ * o1_next [N][H][W][64] = relu(conv1x1(out, w1) * scale1 + shift1), each finished 64-channel panel of `out` being one K chunk of it;
+ * `out` is stored as before.  w1 [64][256] fp32 and its packed fp16 planes with their scale s_w1; *out_scale: the scale `out` is split
+ * with as an operand, chosen before the values exist like *o2_scale (under o2_scale_is_amax: a maximum of |out|, no test) -- every
+ * wave tests its own 32 pixels of `out` against it and computes their o1_next with fp32 FMAs when they fail; o1_next_slot (optional,
+ * zeroed): statistics of o1_next, which the next 3x3 launch takes as its x_slot.  res must not alias out.  out_amax_next (optional,
+ * either form): receives max |out|, the pending maximum of the site out_scale belongs to. */
+int mmt_c64_conv3_fused(const float* x, int N, int H, int W, const float* w2, const void* w2_planes, long w2_plane_stride,
+                        const float* s_w2 /*device*/, const float* scale2, const float* shift2, const float* x_slot /*device*/,
+                        const float* w3, const void* w3_planes, long w3_plane_stride, const float* s_w3 /*device*/, const float* scale3,
+                        const float* shift3, const float* res, float* out, float* out_slot /*device, or NULL*/,
+                        const float* o2_scale /*device*/, int o2_scale_is_amax, float* o2_amax_next /*device, or NULL*/,
+                        float* out_amax_next /*device, or NULL*/, const float* w1, const void* w1_planes, long w1_plane_stride,
+                        const float* s_w1 /*device*/, const float* scale1, const float* shift1, const float* out_scale /*device*/,
+                        float* o1_next, float* o1_next_slot /*device, or NULL*/, void* stream);
 /* Weight gradient of a stride-1, "same"-padded convolution from ROW-BLOCKED fp16 planes of both operands (round 5; replaces the
  * conv2d weight gradient behind layers/misc.py:30-43 where the planes exist anyway: the forward launch's input planes and the
  * data-gradient launch's gradient planes, mmt_split_planes_f16_rb): dw += rowscale[co] * dy^T im2col(x), dbias += column sums of dy.

@@ -169,6 +169,10 @@ _SIGS = {
     "mmt_conv_pg_wanted": [ctypes.POINTER(ConvArgs)],
     "mmt_stem_fused": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_void_p, c_void_p],
+    "mmt_c64_conv3_fused": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                            c_void_p, c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p],
     "mmt_maxpool3x3s2_bf16": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "mmt_gconv3x3_forward": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "mmt_gconv3x3_dgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
@@ -2018,6 +2022,100 @@ def stem_fused(x, w_s2d, scale, shift):
                                 am[0].ptr, y.data_ptr(), slot.ptr, _stream()), "mmt_stem_fused")
     y._mmt_amax = (slot, y._version)
     return y
+
+
+C64_FUSE = os.environ.get("MMT_C64_FUSE", "1") != "0"   # a frozen layer1 block's conv2 + conv3 as one launch (A/B timing, parity tests: 0)
+
+
+def o2_site(w3):
+    """the producing site of a layer1 block's o2 (conv2's output): keyed by the weight that consumes it"""
+    return ("o2", w3.data_ptr())
+
+
+def c64_fuse_enabled():
+    """do the process's switches and arithmetic allow the fused launch at all?  (Only then does conv2 of a frozen layer1 block record
+    o2's maximum at its site on the two-launch path: a site that becomes ready with the fused launch switched off -- MMT_C64=0, a
+    profiling leg -- would make conv2 write planes of o2 that nobody reads)"""
+    return bool(C64_FUSE and F16X2 and RB_EPI and PROFILE is None and os.environ.get("MMT_C64") != "0" and get_conv_precision() == 3)
+
+
+def out_site(w1_next):
+    """the site of a layer1 block's `out` in its role as the operand of the NEXT block's conv1: keyed by that weight"""
+    return ("out1", w1_next.data_ptr())
+
+
+def c64_conv3_fused(x, w2, scale2, shift2, w3, scale3, shift3, res, o2_amax=None, nxt=None, out_amax=None):
+    """conv2 (3x3, 64 -> 64, FrozenBN, ReLU) and conv3 (1x1, 64 -> 256, FrozenBN, + res, ReLU) of a layer1 bottleneck in one launch
+    (include/mmtpsm.h: mmt_c64_conv3_fused); o2 never reaches memory.  -> out with its statistics attached, or None when this is not
+    a call for the fused launch -- other shapes / arithmetic, a site without a scale yet (its first step: the two launches record the
+    maximum the scale is folded from, `rb_site=o2_site(w3)` on conv2) -- and the caller takes the two launches.
+    nxt = (w1, scale1, shift1) of the NEXT block (256 -> 64, stride 1): its conv1 runs behind conv3 in the same launch -> (out, o1_next);
+    o1_next is None while the site of `out` as that operand has no scale yet (this launch then records the maximum it is folded from).
+    o2_amax / out_amax (tests): device maxima of |o2| / |out| to derive the scales from, as the un-fused chain does, instead of the
+    sites' lagged scales."""
+    if not c64_fuse_enabled():
+        return None
+    N, C, Hh, W = x.shape
+    if (C != 64 or tuple(w2.shape) != (64, 64, 3, 3) or tuple(w3.shape) != (256, 64, 1, 1) or tuple(res.shape) != (N, 256, Hh, W)
+            or x.dtype != torch.float32 or res.dtype != torch.float32 or N * Hh * W >= (1 << 21) or N * Hh * W == 0):
+        return None
+    if nxt is not None and tuple(nxt[0].shape) != (64, 256, 1, 1):
+        return None
+    site = o2_site(w3)
+    x, res, w2, w3 = nhwc(x), nhwc(res), nhwc(w2), nhwc(w3)
+    if not _site_ok((w2.data_ptr(), False), x, count=False):
+        return None   # (the lagged crest-factor test sent conv2's site to the 3-term bf16 split)
+    pend = None
+    if o2_amax is None:
+        t, i = _rb_site(site, x.device)
+        if t is None or i not in t.ready:
+            return None
+        t.produced.add(i)
+        sc, pend = t.base + 8 * i, t.base + 8 * i + 4
+    else:
+        sc = o2_amax.data_ptr()
+    am = _amax_of(x)
+    if type(am[0]) is not _Slot:
+        return None
+    wp2, sw2 = f16_weight_planes(w2)
+    wp3, sw3 = f16_weight_planes(w3)
+    out = empty_nhwc(N, 256, Hh, W, x.device)
+    slot = _amax_slot(x.device)
+    # the next block's conv1: its operand's site must have a scale (else this launch only records max |out| there)
+    nx = [None] * 10   # out_amax_next, w1, w1_planes, stride, s_w1, scale1, shift1, out_scale, o1_next, o1_next_slot
+    nx[3] = 0
+    o1n = nslot = None
+    if nxt is not None:
+        w1 = nhwc(nxt[0])
+        go = True
+        if out_amax is None:
+            t1, i1 = _rb_site(out_site(nxt[0]), x.device)
+            go = t1 is not None and o2_amax is None
+            if go:
+                t1.produced.add(i1)
+                nx[0] = t1.base + 8 * i1 + 4
+                go = i1 in t1.ready
+                osc = t1.base + 8 * i1
+        else:
+            go, osc = o2_amax is not None, out_amax.data_ptr()
+        ent = _SITES.get((w1.data_ptr(), False))   # (the host's lagged crest-factor verdict on the next conv1's site, if any)
+        if go and (ent is None or ent[0]):
+            wp1, sw1 = f16_weight_planes(w1)
+            o1n = empty_nhwc(N, 64, Hh, W, x.device)
+            nslot = _amax_slot(x.device)
+            nx[1:] = [w1.data_ptr(), wp1.data_ptr(), wp1.stride(0), sw1.data_ptr(), _p(nxt[1]), _p(nxt[2]), osc, o1n.data_ptr(), nslot.ptr]
+            F16_STATS["c64_fused_next"] = F16_STATS.get("c64_fused_next", 0) + 1
+    F16_STATS["c64_fused"] = F16_STATS.get("c64_fused", 0) + 1
+    _check(lib().mmt_c64_conv3_fused(x.data_ptr(), N, Hh, W, w2.data_ptr(), wp2.data_ptr(), wp2.stride(0), sw2.data_ptr(), _p(scale2),
+                                     _p(shift2), am[0].ptr, w3.data_ptr(), wp3.data_ptr(), wp3.stride(0), sw3.data_ptr(), _p(scale3),
+                                     _p(shift3), res.data_ptr(), out.data_ptr(), slot.ptr, sc, 0 if o2_amax is None else 1, pend,
+                                     *nx, _stream()), "mmt_c64_conv3_fused")
+    out._mmt_amax = (slot, out._version)
+    if nxt is None:
+        return out
+    if o1n is not None:
+        o1n._mmt_amax = (nslot, o1n._version)
+    return out, o1n
 
 
 def conv_pg_plan(N, Cin, H, W, Cout, KH, KW, stride, pad):

@@ -298,8 +298,8 @@ def _strides(stride, in_3x3):
     return (1, stride) if in_3x3 else (stride, 1)
 
 
-def bottleneck_forward(x, w1, w2, w3, wd, bn, stride, in_3x3=False):
-    """the 3-4 launches of a bottleneck -> (o1, o2, out)"""
+def bottleneck_forward(x, w1, w2, w3, wd, bn, stride, in_3x3=False, frozen=False):
+    """the 3-4 launches of a bottleneck -> (o1, o2, out); frozen: no backward pass will ever read o1 / o2 (o2 may come back None)"""
     s1, b1, s2, b2, s3, b3, sd, bd = bn
     if _grouped(w2):
         # ResNeXt: conv2 on the grouped kernels (csrc/conv_group.hip), exact fp32.  o1 feeds no dense plane-fed 3x3: no planes asked
@@ -320,12 +320,59 @@ def bottleneck_forward(x, w1, w2, w3, wd, bn, stride, in_3x3=False):
     od = torch.bfloat16 if H.bf16_storage() else None   # bf16 activation storage (mode 1): every tensor of the block
     # (round 6, fp16 split: row-blocked fp16 planes with the site's lagged scale instead -- conv2 runs on the tap-strip / plane-fed
     # kernel from layer2 on, and its weight gradient takes o1's planes too)
+    # a frozen layer1 block (nothing is saved for a backward pass; 64 bottleneck channels, stride 1, fp32 storage): conv2 and conv3 --
+    # and, `nxt` given, the NEXT block's conv1 -- in one launch; o2 never reaches memory (_frozen_c64)
+    if frozen and mid == 64 and stride == 1 and od is None and w3.shape[0] == 256 and H.c64_fuse_enabled():
+        return _frozen_c64(x, w1, w2, w3, wd, bn, None, None)[:3]
     o1 = H.conv_forward(x, w1, s1, b1, stride, 0, relu=True, want_planes=wp, out_dtype=od,
                         rb_site=("o1", w2.data_ptr()) if mid >= 128 else None)
     o2 = H.conv_forward(o1, w2, s2, b2, 1, 1, relu=True, out_dtype=od)
     r = x if wd is None else H.conv_forward(x, wd, sd, bd, stride, 0, out_dtype=od)
     out = H.conv_forward(o2, w3, s3, b3, 1, 0, relu=True, res=r, res_mode=1, out_dtype=od)
     return o1, o2, out
+
+
+def _frozen_c64(x, w1, w2, w3, wd, bn, o1_pre, nxt):
+    """a frozen stride-1 bottleneck with 64 bottleneck channels -> (o1, o2 or None, out, o1_next or None).  o1_pre: this block's o1 as
+    the previous block's launch already computed it; nxt = (w1, scale1, shift1) of the next block when that is one of these too: its
+    conv1 rides behind conv3 (_hip.c64_conv3_fused).  A site without a scale yet (its first step) takes the old launches, which record
+    the maxima the scales are folded from."""
+    s1, b1, s2, b2, s3, b3, sd, bd = bn
+    o1 = o1_pre if o1_pre is not None else H.conv_forward(x, w1, s1, b1, 1, 0, relu=True)
+    r = x if wd is None else H.conv_forward(x, wd, sd, bd, 1, 0)
+    got = H.c64_conv3_fused(o1, w2, s2, b2, w3, s3, b3, r, nxt=nxt)
+    if got is not None:
+        out, o1n = got if nxt is not None else (got, None)
+        return o1, None, out, o1n
+    o2 = H.conv_forward(o1, w2, s2, b2, 1, 1, relu=True, rb_site=H.o2_site(w3))
+    out = H.conv_forward(o2, w3, s3, b3, 1, 0, relu=True, res=r, res_mode=1, rb_site=H.out_site(nxt[0]) if nxt is not None else None)
+    return o1, o2, out, None
+
+
+def _c64_block(blk):
+    """is (w1, w2, w3, wd, bn, stride, in_3x3) a block _frozen_c64 takes?"""
+    w1, w2, w3, wd, bn, stride, in_3x3 = blk
+    return (stride == 1 and not _grouped(w2) and w1.shape[0] == 64 and w3.shape[0] == 256 and not H.bf16_storage()
+            and H.c64_fuse_enabled())
+
+
+def frozen_stage(x, blocks):
+    """a frozen stage (no gradient flows through it): its bottlenecks in turn -> the stage's output.  blocks: (w1, w2, w3, wd, bn, stride,
+    in_3x3) per block.  Inside layer1 the launch of a block also runs the next block's conv1 (256 -> 64) on the `out` panels it holds,
+    and hands that block its o1: `out` is not read again for it."""
+    x = H.nhwc(x)
+    o1n = None
+    for k, blk in enumerate(blocks):
+        w1, w2, w3, wd, bn, stride, in_3x3 = blk
+        if not _c64_block(blk):
+            x, o1n = bottleneck_forward(x, w1, w2, w3, wd, bn, stride, in_3x3, frozen=True)[2], None
+            continue
+        nxt = None
+        if k + 1 < len(blocks) and _c64_block(blocks[k + 1]) and blocks[k + 1][0].shape[1] == 256:
+            nb = blocks[k + 1]
+            nxt = (nb[0], nb[4][0], nb[4][1])
+        _, _, x, o1n = _frozen_c64(x, w1, w2, w3, wd, bn, o1n, nxt)
+    return x
 
 
 class BottleneckFn(torch.autograd.Function):
@@ -338,9 +385,11 @@ class BottleneckFn(torch.autograd.Function):
     def forward(ctx, x, w1, w2, w3, wd, bn, stride, pre=None, in_3x3=False):
         s1, b1, s2, b2, s3, b3, sd, bd = bn
         x = H.nhwc(x)
-        o1, o2, out = pre if pre is not None else bottleneck_forward(x, w1, w2, w3, wd, bn, stride, in_3x3)
+        # (no input asks for a gradient -- a frozen stage, called under no_grad: this node never runs backward)
+        frozen = pre is None and not any(ctx.needs_input_grad)
+        o1, o2, out = pre if pre is not None else bottleneck_forward(x, w1, w2, w3, wd, bn, stride, in_3x3, frozen)
         ctx.in_3x3 = in_3x3
-        ctx.save_for_backward(x, o1, o2, w1, w2, w3, wd if wd is not None else _none_like(x))
+        ctx.save_for_backward(x, o1, o2 if o2 is not None else _none_like(x), w1, w2, w3, wd if wd is not None else _none_like(x))
         ctx.bn = (s1, s2, s3, sd)
         ctx.stride = stride
         ctx.has_ds = wd is not None

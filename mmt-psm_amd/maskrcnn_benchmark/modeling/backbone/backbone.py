@@ -218,7 +218,7 @@ class ResNet(nn.Module):
         for i, name in enumerate(self.stages, 1):
             if i < self.freeze_at:
                 with torch.no_grad():
-                    x = getattr(self, name)(x)
+                    x = _frozen_stage(getattr(self, name), x)
             else:
                 x = getattr(self, name)(x)
                 _stage_hook(self, name, x)
@@ -228,6 +228,12 @@ class ResNet(nn.Module):
             else:
                 outs.append(x)
         return outs
+
+
+def _frozen_stage(stage, x):
+    """a frozen stage's blocks as one chain (the caller runs this under no_grad): inside layer1 a block's launch also computes the next
+    block's conv1 and hands it over (layers/fused.py::frozen_stage) -- the same values as calling the blocks in turn"""
+    return fused.frozen_stage(x, [blk._args() + (blk.in_3x3,) for blk in stage])
 
 
 def _stage_hook(body, name, x):
@@ -261,10 +267,10 @@ def forward_pair(backbone, xa, xb):
         raw = {}     # block -> (o1, o2, out) on the concatenated batch
         frozen = []
         for i, name in enumerate(body.stages, 1):
-            for bi, blk in enumerate(getattr(body, name)):
-                if i < body.freeze_at:
-                    x = blk(x)
-                else:
+            if i < body.freeze_at:
+                x = _frozen_stage(getattr(body, name), x)
+            else:
+                for bi, blk in enumerate(getattr(body, name)):
                     raw[(name, bi)] = blk.forward_raw(x)
                     x = raw[(name, bi)][2]
             if i < body.freeze_at:
