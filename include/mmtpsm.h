@@ -797,6 +797,29 @@ int mmt_mask_transition_positions(const uint64_t* words, int n, int H, int W, co
 int mmt_mask_pair_intersections(const uint64_t* dwords, const int32_t* drec, int m, const uint64_t* gwords,
                                 const int32_t* grec, int n, int H, int W, int32_t* inter, void* stream);
 
+/* ---------------------------------------------------------------- polygons at image size (csrc/polyfill.hip)
+ * polygon_mask_words (structures/segmentation_mask.py:127-137 Polygons.convert("mask"): frPyObjects -> pycoco/maskApi.c:166-206
+ * rleFrPoly, :53-74 union, :47-51 decode): instance g is the union of the fills of polygons inst_poly[g][0] .. inst_poly[g][1]-1
+ * rasterised into an H x W image -> words [G][ceil(H*W/64)] and rec [G][MMT_MASK_REC_INTS], exactly what mmt_mask_pack gives for
+ * the masks pycocotools decodes, bit for bit.  poly_xy / poly_off [NP+1] as mmt_polygon_targets takes them; inst_poly int32
+ * [G][2]; an empty range is an empty mask.  Every word and record is written (the caller clears nothing).
+ *   ws        toggle workspace of at least the uint64 count that mmt_polygon_mask_words_workspace(NP, H, W, &n) reports: one
+ *             H*W-bit plane per polygon of poly_off plus one int per 64 words of a plane.  Cleared by the call; the library
+ *             allocates nothing.  A smaller ws_words returns MMT_EINVAL: the caller splits the instances over several calls.
+ * Crossings are integer XOR atomics: the same bits run to run, in deterministic mode as well.  The call copies inst_poly and the
+ * two ends of poly_off to the host to check the ranges and to size its launches, so it waits for the stream once.
+ * MMT_EINVAL as for the mask words above, and for NP < 0 or an inst_poly entry outside [0, NP]. */
+int mmt_polygon_mask_words_workspace(int NP, int H, int W, int64_t* words_needed);
+int mmt_polygon_mask_words(const float* poly_xy, const int32_t* poly_off, int NP, const int32_t* inst_poly /*[G][2]*/, int G,
+                           int H, int W, uint64_t* ws, int64_t ws_words, uint64_t* words /*[G][ceil(H*W/64)]*/,
+                           int32_t* rec /*[G][MMT_MASK_REC_INTS]*/, void* stream);
+/* the sum over instances as a row-major map (structures/segmentation_mask.py:174-181 SegmentationMask.decode; what mmt_mask_pool
+ * reads): seg int32 [N][H][W], seg[n][y][x] = number of instances img_off[n] .. img_off[n+1]-1 of `words` whose pixel (y, x) is
+ * set.  img_off [N+1] is a HOST array, non-decreasing from a non-negative start, at most 65535 instances.  Every element of seg is
+ * written; an image without instances is zeros. */
+int mmt_mask_words_integral(const uint64_t* words, const int32_t* img_off /*[host]*/, int N, int H, int W, int32_t* seg,
+                            void* stream);
+
 /* ---------------------------------------------------------------- deterministic mode (csrc/ordered.hip, csrc/ordered.h)
  * Same inputs, same build -> the same bits, run to run: every sum whose order the float atomics of the default kernels leave to
  * timing has a form here that adds in an order fixed by the shapes alone -- block partials stored to a caller's workspace, then a

@@ -202,6 +202,10 @@ _SIGS = {
     "mmt_mask_transition_counts": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_mask_transition_positions": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "mmt_mask_pair_intersections": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "mmt_polygon_mask_words_workspace": [c_int, c_int, c_int, c_void_p],
+    "mmt_polygon_mask_words": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p,
+                               c_void_p],
+    "mmt_mask_words_integral": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_set_deterministic": [c_int],
     "mmt_get_deterministic": [],
     "mmt_roi_align_backward_ordered": [ctypes.POINTER(Pyramid), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
@@ -867,7 +871,7 @@ def _lib_raw():
 # pool, which keeps their addresses for the plan's life; its statistics slots from a block of the plan's own) and REPLAYED from then
 # on: ~70 ctypes calls instead of the Python that derives them (a manual graph: hipGraph replays of the two models serialise in
 # this runtime).  Only the input's address is patched.  Queries are not recorded.
-_NO_RECORD = frozenset(("mmt_conv_wants_planes", "mmt_conv_pg_wanted", "mmt_conv_writes_rb", "mmt_conv_wgrad_group_workspace", "mmt_conv_variant", "mmt_conv_ksplit", "mmt_conv_pg_plan",
+_NO_RECORD = frozenset(("mmt_polygon_mask_words_workspace", "mmt_conv_wants_planes", "mmt_conv_pg_wanted", "mmt_conv_writes_rb", "mmt_conv_wgrad_group_workspace", "mmt_conv_variant", "mmt_conv_ksplit", "mmt_conv_pg_plan",
                         "mmt_conv_wgrad_splits", "mmt_get_conv_precision", "mmt_packed_weight_elems", "mmt_set_conv_precision", "mmt_set_deterministic", "mmt_get_deterministic"))
 LAYOUT_EPOCH = [0]    # bumped when a flat model (re)allocates its plane buffers (engine/flat.py)
 LAUNCH_PLANS = os.environ.get("MMT_LAUNCH_PLANS", "1") != "0"
@@ -3074,3 +3078,87 @@ def mask_pair_intersections(dwords, drec, gwords, grec, H, W):
     _check(lib().mmt_mask_pair_intersections(_p(dwords), _p(drec), m, _p(gwords), _p(grec), n, H, W, _p(out), _stream()),
            "mmt_mask_pair_intersections")
     return out
+
+
+# ---- polygons at image size (include/mmtpsm.h: mmt_polygon_mask_words, mmt_mask_words_integral; csrc/polyfill.hip)
+POLYGON_WS_WORDS = 1 << 25   # toggle workspace of one call, in 64-bit words (256 MiB); more polygons than fit go in several calls
+
+
+def polygon_workspace_words(NP, H, W):
+    """64-bit words of toggle workspace that mmt_polygon_mask_words wants for NP polygons in an H x W image (a query: no launch)"""
+    n = ctypes.c_int64(0)
+    if lib().mmt_polygon_mask_words_workspace(int(NP), int(H), int(W), ctypes.byref(n)) != 0:
+        raise RuntimeError("polygon masks of %d x %d, %d polygons: 0 < H * W < 2^31 and NP >= 0 only" % (H, W, NP))
+    return int(n.value)
+
+
+def polygon_mask_words(xy, poly_off, inst_poly, H, W):
+    """xy float32 vertices (x, y interleaved), poly_off int32 (NP + 1,), inst_poly int32 (G, 2): instance g is the union of
+    polygons inst_poly[g, 0] .. inst_poly[g, 1] - 1 -> (words, records) of the G masks in an H x W image: what
+    mask_pack(pycocotools' decode(merge(frPyObjects(...)))) gives, bit for bit (mmt_polygon_mask_words).  The toggle workspace of
+    one call holds POLYGON_WS_WORDS words; instances whose polygons need more are rasterised in several calls"""
+    xy = _dev(xy, "xy").float().contiguous()
+    poly_off = _dev(poly_off, "poly_off").to(torch.int32).contiguous()
+    inst_poly = _dev(inst_poly, "inst_poly").to(torch.int32).contiguous().reshape(-1, 2)
+    H, W = int(H), int(W)
+    G, NP = inst_poly.shape[0], poly_off.numel() - 1
+    if NP < 0:
+        raise RuntimeError("polygon_mask_words: poly_off holds NP + 1 offsets")
+    words, rec = _mask_buffers(G, H, W, xy.device)
+    if G == 0:
+        return words, rec
+    L = lib()
+
+    def run(off, n_poly, rng, w, r, need):
+        ws = torch.empty((max(need, 1),), dtype=torch.int64, device=xy.device)
+        _check(L.mmt_polygon_mask_words(_p(xy), _p(off), n_poly, _p(rng), rng.shape[0], H, W, _p(ws), need, _p(w), _p(r), _stream()),
+               "mmt_polygon_mask_words")
+
+    need = polygon_workspace_words(NP, H, W)
+    if need <= POLYGON_WS_WORDS:
+        run(poly_off, NP, inst_poly, words, rec, need)
+        return words, rec
+    # consecutive instances whose polygons span a range that fits; an instance that does not fit alone gets what it needs
+    host = inst_poly.cpu().tolist()
+    if any(s < 0 or e < 0 or s > NP or e > NP for s, e in host):
+        raise RuntimeError("polygon_mask_words: an inst_poly range outside [0, %d]" % NP)
+    g0 = 0
+    while g0 < G:
+        lo = hi = None
+        g1 = g0
+        while g1 < G:
+            s, e = host[g1]
+            nlo, nhi = (lo, hi) if e <= s else ((s, e) if lo is None else (min(lo, s), max(hi, e)))
+            if g1 > g0 and nlo is not None and polygon_workspace_words(nhi - nlo, H, W) > POLYGON_WS_WORDS:
+                break
+            lo, hi = nlo, nhi
+            g1 += 1
+        if lo is None:
+            lo = hi = 0
+        # (poly_off holds vertex positions in xy, so a slice of it serves as it is; the ranges move with it)
+        part = inst_poly[g0:g1]
+        full = (part[:, 1:2] > part[:, 0:1]).expand(-1, 2)          # an empty range may lie anywhere: it becomes [0, 0)
+        rng = torch.where(full, part - lo, torch.zeros_like(part)).contiguous()
+        run(poly_off[lo:hi + 1], hi - lo, rng, words[g0:g1], rec[g0:g1], polygon_workspace_words(hi - lo, H, W))
+        g0 = g1
+    return words, rec
+
+
+def mask_words_integral(words, img_off, H, W):
+    """words (G, ceil(H * W / 64)) of G masks in an H x W image, img_off: N + 1 host integers, image n owns masks
+    img_off[n] .. img_off[n + 1] - 1 -> seg int32 (N, H, W) on the device, the number of masks that cover each pixel
+    (mmt_mask_words_integral); what mask_pool reads"""
+    words = _dev(words, "words")
+    H, W = int(H), int(W)
+    off = [int(v) for v in (img_off.tolist() if isinstance(img_off, torch.Tensor) else img_off)]
+    if words.dtype != torch.int64 or words.dim() != 2 or words.shape[1] != (H * W + 63) // 64 or not words.is_contiguous():
+        raise RuntimeError("mask_words_integral: contiguous int64 words (G, ceil(H * W / 64))")
+    if len(off) < 1 or off[0] < 0 or any(b < a for a, b in zip(off, off[1:])) or off[-1] > words.shape[0]:
+        raise RuntimeError("mask_words_integral: img_off must rise from a non-negative start and end within the %d masks" % words.shape[0])
+    N = len(off) - 1
+    seg = torch.empty((N, H, W), dtype=torch.int32, device=words.device)
+    if N:
+        arr = (ctypes.c_int32 * (N + 1))(*off)
+        _check(lib().mmt_mask_words_integral(_p(words), ctypes.cast(arr, c_void_p), N, H, W, _p(seg), _stream()),
+               "mmt_mask_words_integral")
+    return seg

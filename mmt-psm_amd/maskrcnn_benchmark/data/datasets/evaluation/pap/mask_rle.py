@@ -1,6 +1,7 @@
 """Run-length masks for the PAP evaluator: the five calls the reference makes into its vendored pycocotools
 (`/root/reference/pycoco/_mask.pyx`: encode :144, decode :160, merge :177, area :190, iouIntUni :293-380; C side
-`maskApi.c`: rleEncode :21-34, rleToString / rleFrString :204-236, rleIouInterUnion :239-260) restated on numpy.
+`maskApi.c`: rleEncode :21-34, rleToString / rleFrString :204-236, rleIouInterUnion :239-260) restated on numpy, and the polygon rasteriser behind a sixth, `frPyObjects` (`maskApi.c`:
+rleFrPoly :166-206), as `frPolygons`.
 
 An RLE is COCO's: {"size": [h, w], "counts": ...} over the mask flattened COLUMN-major, runs alternating 0 / 1 starting with
 zeros; `counts` is the compressed ASCII string (bytes or str) or a plain list of run lengths (COCO's "uncompressed" form).
@@ -180,6 +181,90 @@ def encode_pasted_device(prob, boxes, h, w, thresh=0.5):
         return []
     words, _ = H.paste_mask_words(prob, boxes, h, w, thresh)
     return _strings_of_words(H, words, h, w)
+
+
+def _poly_crossings(xy, h, w):
+    """one polygon, float64 (k, 2) -> the column crossings a = x * h + y of rleFrPoly (maskApi.c:166-206), unsorted: the x5
+    boundary walk edge by edge (every step is closed-form in t, and a crossing at step d needs steps d and d - 1 only; the walk
+    never changes column between the last point of an edge and the first of the next, which are the same point)"""
+    k = xy.shape[0]
+    if k == 0:
+        return np.zeros(0, np.int64)
+    X = np.trunc(5.0 * xy[:, 0] + .5).astype(np.int64)
+    Y = np.trunc(5.0 * xy[:, 1] + .5).astype(np.int64)
+    found = [np.zeros(0, np.int64)]
+    for j in range(k):
+        xs, ys, xe, ye = int(X[j]), int(Y[j]), int(X[(j + 1) % k]), int(Y[(j + 1) % k])
+        dx, dy = abs(xe - xs), abs(ys - ye)
+        if dx == 0:
+            continue                                   # the column never changes
+        flip = (dx >= dy and xs > xe) or (dx < dy and ys > ye)
+        if flip:
+            xs, xe, ys, ye = xe, xs, ye, ys
+        t = np.arange(max(dx, dy) + 1, dtype=np.float64)
+        if flip:
+            t = t[::-1]
+        if dx >= dy:
+            u, v = t + xs, np.trunc(ys + (float(ye - ys) / dx) * t + .5)
+        else:
+            u, v = np.trunc(xs + (float(xe - xs) / dy) * t + .5), t + ys
+        ch = u[1:] != u[:-1]
+        xd = np.where(u[1:] < u[:-1], u[1:], u[1:] - 1)[ch]
+        xd = (xd + .5) / 5.0 - .5
+        ok = (np.floor(xd) == xd) & (xd >= 0) & (xd <= w - 1)
+        yd = np.ceil(np.clip((np.minimum(v[1:], v[:-1])[ch][ok] + .5) / 5.0 - .5, 0, h))
+        found.append((xd[ok] * h + yd).astype(np.int64))
+    return np.concatenate(found)
+
+
+def _poly_fill(xy, h, w):
+    """one polygon -> bool (h * w,) over the column-major flattening: rleFrPoly's sorted run lengths say that pixel q is the
+    parity of the crossings at or below q; a crossing at h * w lies behind the last pixel"""
+    a = _poly_crossings(xy, h, w)
+    return (np.cumsum(np.bincount(a, minlength=h * w + 1)[:h * w]) & 1).astype(bool)
+
+
+def _instances_of(segm):
+    """a SegmentationMask, or a list of instances, each a Polygons or a list of flat [x0, y0, x1, y1, ...] polygons
+    -> [[float64 (k, 2), ...], ...]"""
+    out = []
+    for inst in (segm.polygons if hasattr(segm, "polygons") else segm):
+        polys = inst.polygons if hasattr(inst, "polygons") else inst
+        out.append([np.asarray(p.detach().cpu().numpy() if hasattr(p, "detach") else p, dtype=np.float64).reshape(-1, 2) for p in polys])
+    return out
+
+
+def frPolygons(segm, h, w, on_device=False):
+    """polygon ground truth -> one RLE per instance: `encode(decode(merge(frPyObjects(polys, h, w))))` of the reference's
+    pycocotools (`_mask.pyx` frPyObjects -> maskApi.c:166-206 rleFrPoly; merge = union of the instance's polygons).  `segm`: a
+    SegmentationMask or a list of instances, each a list of flat polygons.  Host: the boundary walk restated on numpy.
+    on_device=True: `mmt_polygon_mask_words` (csrc/polyfill.hip, vertices in float32 as SegmentationMask keeps them), then the
+    run boundaries as for every other device string; RuntimeError without a GPU or the library"""
+    h, w = int(h), int(w)
+    inst = _instances_of(segm)
+    if on_device:
+        H = _backend()
+        import torch
+        if not inst:
+            return []
+        if h * w == 0:
+            return [{"size": [h, w], "counts": _to_string([0]).encode("ascii")} for _ in inst]
+        device = torch.device("cuda", torch.cuda.current_device())
+        polys = [p for i in inst for p in i]
+        off = np.concatenate([[0], np.cumsum([len(p) for p in polys])]).astype(np.int32)
+        ends = np.cumsum([len(i) for i in inst])
+        rng = np.stack([ends - [len(i) for i in inst], ends], 1).astype(np.int32)
+        xy = np.concatenate(polys + [np.zeros((0, 2))], 0).astype(np.float32)
+        words, _ = H.polygon_mask_words(torch.from_numpy(xy).to(device), torch.from_numpy(off).to(device),
+                                        torch.from_numpy(rng).to(device), h, w)
+        return _strings_of_words(H, words, h, w)
+    out = []
+    for polys in inst:
+        acc = np.zeros(h * w, bool)
+        for p in polys:
+            acc |= _poly_fill(p, h, w)
+        out.append({"size": [h, w], "counts": _to_string(_runs(acc.astype(np.uint8))).encode("ascii")})
+    return out
 
 
 def _expand_device(H, rles, device):

@@ -372,7 +372,13 @@ def prepare_for_pap_segmentation(predictions, dataset, on_device=False):
         target = dataset.get_ground_truth(original_id)
         labels = [dataset.contiguous_category_id_to_json_id[i] for i in target.get_field("labels").tolist()]
         boxes = target.bbox.tolist()
-        for k, rle in enumerate(target.get_field("masks")):
+        gt_masks = target.get_field("masks")
+        if hasattr(gt_masks, "polygons"):
+            # polygon ground truth (a SegmentationMask): rasterised at its own size into RLEs, on the device with on_device
+            gt_masks = maskUtils.frPolygons(gt_masks, gt_masks.size[1], gt_masks.size[0], on_device=on_device)
+            for rle in gt_masks:
+                rle["counts"] = rle["counts"].decode("utf-8")
+        for k, rle in enumerate(gt_masks):
             gts.append({"image_id": original_id, "category_id": labels[k], "segmentation": rle, "bbox": boxes[k]})
         prediction = prediction.resize((dataset.maxWS, dataset.maxWS))
         masks = prediction.get_field("mask")

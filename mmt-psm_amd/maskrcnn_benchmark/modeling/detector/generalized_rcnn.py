@@ -2,6 +2,7 @@
 
 forward(images, targets)            supervised student step -> loss dict / eval detections
 forward_teacher(images)             coarse inference -> pseudo labels + masks; K-aug x flip pyramids; per-view logits
+forward_teacher(images, targets)    the same dict from ground truth: annotated boxes, decoded polygon masks
 forward_student(images, result_t)   MGD (mt_fg_loss) + PSM (mt_classifier)
 
 Same attribute tree (backbone, rpn, box_heads, mask_heads, relation_nms, hint_adaptor), same dict keys.  The IR-Net
@@ -213,10 +214,7 @@ class GeneralizedRCNN(nn.Module):
 
     def forward_teacher(self, images, targets=None):
         if targets is not None:
-            # reference generalized_rcnn.py:133-139: ground truth in place of the coarse inference, its masks decoded at a hard-coded
-            # 800 x 800 (`get_field('masks').decode(800, 800)`); engine/MTtrainer.py:247-275 never passes targets
-            raise NotImplementedError("forward_teacher(images, targets): the ground-truth branch of the reference "
-                                      "(generalized_rcnn.py:133-139) is not built; MTtrainer never takes it")
+            return self._forward_teacher_targets(images, targets)
         integral = []
         images = [to_image_list(im) for im in images]
         # all AUG_K x {plain, mirrored} views go through the backbone as ONE batch; the coarse inference of the
@@ -262,6 +260,42 @@ class GeneralizedRCNN(nn.Module):
             self.box_heads.box.batched_pyramid = batched
             _, result, _, class_logits, _ = self.box_heads.forward_teacher(aug_features, proposals, teacher_infer)
             self.box_heads.box.batched_pyramid = None
+        return {"result_t": result, "class_logit_t": class_logits, "embedding": embeddings, "seg_mask": integral,
+                "ffi_boxes": ffi_boxes}
+
+    def _forward_teacher_targets(self, images, targets):
+        """reference generalized_rcnn.py:133-139: the ground truth, moved to the device, stands in for the coarse inference -- no
+        `self.forward` pass, module mode `train` throughout --, and the integral foreground mask is the sum of the annotated
+        instances' polygon masks (`SegmentationMask.decode`: csrc/polyfill.hip).  Departure: the reference decodes at a hard-coded
+        800 x 800 (`get_field('masks').decode(800, 800)`), which only adds up for targets of exactly that size; here every target is
+        decoded at its own size.  engine/MTtrainer.py never passes targets."""
+        images = [to_image_list(im) for im in images]
+        dev = images[0].tensors.device
+        targets = [t.to(dev) for t in targets]
+        integral = []
+        if self.mt_fg_hint > 0:
+            for i, t in enumerate(targets):
+                if not t.has_field("masks"):
+                    raise RuntimeError("forward_teacher(images, targets) with MT.FG_HINT > 0: target %d carries no 'masks' field" % i)
+                w, h = t.size
+                integral.append(t.get_field("masks").decode(h, w, dev))
+            if len({tuple(m.shape) for m in integral}) > 1:
+                raise RuntimeError("forward_teacher(images, targets): targets of differing sizes in one batch (%s)"
+                                   % sorted({tuple(m.shape) for m in integral}))
+        self.set_module_mode("train")
+        aug_features = self.extract_aug_feat(images)
+        batched = getattr(self, "_batched_pyr", None)
+        self.rpn.shared = None
+        _, _, _, _, proposals, _, ffi_boxes = self.rpn.forward_teacher(images[0], aug_features[0], targets)
+        proposals = self._tap("teacher_proposals", proposals)
+        embeddings = self.get_emb_feature(aug_features) if self.cfg.MT.FG_HINT else None
+        result, class_logits = None, None
+        if self.cfg.MT.CLS_LOSS:
+            self.box_heads.box.batched_pyramid = batched
+            try:
+                _, result, _, class_logits, _ = self.box_heads.forward_teacher(aug_features, proposals, targets)
+            finally:
+                self.box_heads.box.batched_pyramid = None
         return {"result_t": result, "class_logit_t": class_logits, "embedding": embeddings, "seg_mask": integral,
                 "ffi_boxes": ffi_boxes}
 

@@ -51,6 +51,16 @@ class Polygons(object):
             out.append(q)
         return Polygons(out, size, self.mode)
 
+    def convert(self, mode, device=None):
+        """convert("mask") -> uint8 [h, w] on the device: the union of this instance's polygons as pycocotools rasterises them
+        (reference structures/segmentation_mask.py:127-137, frPyObjects + merge + decode), through the image-size rasteriser
+        `_hip.polygon_mask_words`.  The reference returns the same values as a CPU tensor; for any other mode it falls through
+        and returns None, here that raises"""
+        if mode != "mask":
+            raise NotImplementedError("Polygons.convert(%r): only 'mask' is built" % (mode,))
+        w, h = int(self.size[0]), int(self.size[1])
+        return SegmentationMask([self], self.size, self.mode).decode(h, w, device).to(torch.uint8)
+
     def __repr__(self):
         return "Polygons(num_polygons={}, image_width={}, image_height={}, mode={})".format(
             len(self.polygons), self.size[0], self.size[1], self.mode)
@@ -63,6 +73,7 @@ class SegmentationMask(object):
         self.size = size
         self.mode = mode
         self._packed = None
+        self._words = None
 
     def packed(self, device):
         """-> (xy float32 [V,2] flattened, poly_off int32 [NP+1], inst_range int32 [G,2]) on `device`"""
@@ -78,6 +89,41 @@ class SegmentationMask(object):
             self._packed = (xy.to(device), torch.tensor(off, dtype=torch.int32, device=device),
                             torch.tensor(rng, dtype=torch.int32, device=device).reshape(-1, 2))
         return self._packed
+
+    @staticmethod
+    def _device(device):
+        if device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("polygon masks are rasterised on the GPU (csrc/polyfill.hip); no MI355X visible")
+            device = torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:   # "cuda": the index a tensor there reports, so that the cache is found again
+            device = torch.device("cuda", torch.cuda.current_device())
+        return device
+
+    def mask_words(self, device=None):
+        """-> (words int64 [G, ceil(h * w / 64)], records int32 [G, 8]) on the device: every instance rasterised at the mask's own
+        size into the run-length codec's words (`_hip.polygon_mask_words`; layout: include/mmtpsm.h, mmt_mask_pack).  Cached
+        beside the packed vertices"""
+        device = self._device(device)
+        if self._words is None or self._words[0].device != device:
+            from maskrcnn_benchmark import _hip
+            xy, off, rng = self.packed(device)
+            self._words = _hip.polygon_mask_words(xy, off, rng, int(self.size[1]), int(self.size[0]))
+        return self._words
+
+    def decode(self, h, w, device=None):
+        """-> int32 [h, w] on the device: the number of instances that cover each pixel (reference
+        structures/segmentation_mask.py:174-181, which returns the same values as a float64 numpy array).  (h, w) must be the
+        mask's own (size[1], size[0]) -- in the reference any other size breaks the addition --; an empty list gives zeros"""
+        if (int(h), int(w)) != (int(self.size[1]), int(self.size[0])):
+            raise ValueError("decode(%d, %d) of a %d x %d mask" % (h, w, self.size[1], self.size[0]))
+        device = self._device(device)
+        if len(self.polygons) == 0:
+            return torch.zeros((int(h), int(w)), dtype=torch.int32, device=device)
+        from maskrcnn_benchmark import _hip
+        words, _ = self.mask_words(device)
+        return _hip.mask_words_integral(words, [0, len(self.polygons)], int(h), int(w))[0]
 
     def transpose(self, method):
         return SegmentationMask([p.transpose(method) for p in self.polygons], self.size, self.mode)
