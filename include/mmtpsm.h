@@ -820,6 +820,33 @@ int mmt_polygon_mask_words(const float* poly_xy, const int32_t* poly_off, int NP
 int mmt_mask_words_integral(const uint64_t* words, const int32_t* img_off /*[host]*/, int N, int H, int W, int32_t* seg,
                             void* stream);
 
+/* ---------------------------------------------------------------- bitmap ground truth: geometry on mask words (csrc/bitmasks.hip)
+ * Crop, resize and flip of instance masks that are not polygons (BinaryMaskList, structures/segmentation_mask.py), all in
+ * integers (the definitions: INTEGRATION.md, "Bitmap ground truth").  A window (x0, y0, w, h) of the H x W source is resampled to
+ * OH x OW: for output row i, ny = max((2i+1) h - OH, 0), dy = 2 OH, ia = ny / dy, ry = ny % dy, ib = min(ia+1, h-1); columns
+ * alike (j, w, OW -> ja, jb, rx, dx); with p(a, b) the source bit at (y0+a, x0+b)
+ *   S = (dy-ry) ((dx-rx) p(ia,ja) + rx p(ia,jb)) + ry ((dx-rx) p(ib,ja) + rx p(ib,jb)),   bit = (2 S >= dx dy)
+ * -- bilinear with align_corners=False, thresholded at 1/2, ties set; h = OH and w = OW is a copy.
+ * Ranges: H, W, OH, OW <= 16384 and H*W, OH*OW <= 2^26 (everything then fits in int32), at most 65535 masks; anything else, a
+ * negative count or a null pointer where an array is needed returns MMT_EINVAL and writes nothing; a count of 0 is a no-op.
+ * No atomics: the same bits run to run, in deterministic mode as well.
+ *
+ * mmt_mask_words_resample: ONE window for all G masks of an image -> out [G][ceil(OH*OW/64)], rec [G][MMT_MASK_REC_INTS], exactly
+ * what mmt_mask_pack gives for the same bits.  flip acts on the destination index: bit 0 stores column j at OW-1-j, bit 1 row i at
+ * OH-1-i.  Every output word (tail bits zero) and every record is written; the caller clears nothing.  MMT_EINVAL also for a window
+ * outside the image, w or h < 1, a flip outside 0..3, and an `out` that overlaps `words`. */
+int mmt_mask_words_resample(const uint64_t* words, int G, int H, int W, int x0, int y0, int w, int h, int flip /*bit0 x, bit1 y*/,
+                            int OH, int OW, uint64_t* out /*[G][ceil(OH*OW/64)]*/, int32_t* rec /*[G][MMT_MASK_REC_INTS]*/,
+                            void* stream);
+/* mmt_mask_words_targets: the M x M mask targets of P ROIs (what mmt_polygon_targets is for polygons; same layout: out [P][M][M]
+ * float {0, 1}), 1 <= M <= 32.  ROI p takes instance roi_inst[p] and the window of its box (x1, y1, x2, y2), float32 xyxy:
+ * xa, ya, xb, yb = rintf of the coordinates (half to even), clamped in float to +-2^30; x0 = min(max(xa, 0), W-1), xe =
+ * max(min(max(xb, 0), W), x0+1), w = xe - x0 (rows alike): the end is exclusive, a box wholly outside becomes a 1-pixel window on
+ * the border.  A roi_inst outside [0, G) (-1 is how the host marks a non-positive) or a box with a non-finite coordinate gives a
+ * zero plane and reads no mask word.  P == 0 or G == 0 is a no-op. */
+int mmt_mask_words_targets(const uint64_t* words, int G, int H, int W, const int32_t* roi_inst /*[P]*/, const float* boxes /*[P][4]*/,
+                           int P, int M, float* out /*[P][M][M], {0,1}*/, void* stream);
+
 /* ---------------------------------------------------------------- deterministic mode (csrc/ordered.hip, csrc/ordered.h)
  * Same inputs, same build -> the same bits, run to run: every sum whose order the float atomics of the default kernels leave to
  * timing has a form here that adds in an order fixed by the shapes alone -- block partials stored to a caller's workspace, then a

@@ -206,6 +206,9 @@ _SIGS = {
     "mmt_polygon_mask_words": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p,
                                c_void_p],
     "mmt_mask_words_integral": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "mmt_mask_words_resample": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p],
+    "mmt_mask_words_targets": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "mmt_set_deterministic": [c_int],
     "mmt_get_deterministic": [],
     "mmt_roi_align_backward_ordered": [ctypes.POINTER(Pyramid), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
@@ -3162,3 +3165,52 @@ def mask_words_integral(words, img_off, H, W):
         _check(lib().mmt_mask_words_integral(_p(words), ctypes.cast(arr, c_void_p), N, H, W, _p(seg), _stream()),
                "mmt_mask_words_integral")
     return seg
+
+
+# ---- bitmap ground truth: geometry on mask words (include/mmtpsm.h: mmt_mask_words_resample / _targets; csrc/bitmasks.hip)
+MASK_WORDS_MAX_SIDE, MASK_WORDS_MAX_AREA = 16384, 1 << 26
+
+
+def _mask_words_of(words, H, W, what):
+    words = _dev(words, "words")
+    if words.dtype != torch.int64 or words.dim() != 2 or words.shape[1] != (H * W + 63) // 64 or not words.is_contiguous():
+        raise RuntimeError("%s: contiguous int64 words (G, ceil(H * W / 64))" % what)
+    return words
+
+
+def mask_words_resample(words, H, W, window, flip, OH, OW):
+    """words (G, ceil(H * W / 64)) of G masks in an H x W image, window (x0, y0, w, h) inside it, flip bit 0 left-right, bit 1
+    top-bottom -> (words, records) of the window resampled to OH x OW by the integer bilinear rule of include/mmtpsm.h
+    (mmt_mask_words_resample).  Sides up to 16384, areas up to 2^26; a refused call raises"""
+    H, W, OH, OW, flip = int(H), int(W), int(OH), int(OW), int(flip)
+    x0, y0, w, h = (int(v) for v in window)
+    words = _mask_words_of(words, H, W, "mask_words_resample")
+    G = words.shape[0]
+    for a, b in ((H, W), (OH, OW)):
+        if not (0 < a <= MASK_WORDS_MAX_SIDE and 0 < b <= MASK_WORDS_MAX_SIDE and a * b <= MASK_WORDS_MAX_AREA):
+            raise RuntimeError("mask_words_resample: masks of %d x %d; sides up to %d and areas up to 2^26 only" % (a, b, MASK_WORDS_MAX_SIDE))
+    out, rec = _mask_buffers(G, OH, OW, words.device)
+    _check(lib().mmt_mask_words_resample(_p(words), G, H, W, x0, y0, w, h, flip, OH, OW, _p(out), _p(rec), _stream()),
+           "mmt_mask_words_resample")
+    return out, rec
+
+
+def mask_words_targets(words, roi_inst, boxes, H, W, M):
+    """words (G, ceil(H * W / 64)), roi_inst int32 (P,): the instance of each ROI, anything outside [0, G) -- -1 by convention -- for
+    a ROI without one, boxes float32 (P, 4) xyxy -> float32 (P, M, M) in {0, 1}: the instance cropped to the box's window and
+    resampled to M x M (mmt_mask_words_targets); zeros for a ROI without an instance or with a non-finite box.  Nothing is read
+    back"""
+    H, W, M = int(H), int(W), int(M)
+    words = _mask_words_of(words, H, W, "mask_words_targets")
+    roi_inst = _dev(roi_inst, "roi_inst")
+    boxes = _dev(boxes, "boxes")
+    if roi_inst.dtype != torch.int32 or roi_inst.dim() != 1:
+        raise RuntimeError("mask_words_targets: roi_inst is int32 (P,)")
+    if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.shape[0] != roi_inst.shape[0]:
+        raise RuntimeError("mask_words_targets: boxes are float32 (P, 4), one per roi_inst")
+    roi_inst, boxes = roi_inst.contiguous(), boxes.contiguous()
+    G, P = words.shape[0], boxes.shape[0]
+    out = (torch.empty if G and P else torch.zeros)((P, M, M), dtype=torch.float32, device=boxes.device)
+    _check(lib().mmt_mask_words_targets(_p(words), G, H, W, _p(roi_inst), _p(boxes), P, M, _p(out), _stream()),
+           "mmt_mask_words_targets")
+    return out

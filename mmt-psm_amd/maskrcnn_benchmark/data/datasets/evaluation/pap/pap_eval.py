@@ -373,7 +373,15 @@ def prepare_for_pap_segmentation(predictions, dataset, on_device=False):
         labels = [dataset.contiguous_category_id_to_json_id[i] for i in target.get_field("labels").tolist()]
         boxes = target.bbox.tolist()
         gt_masks = target.get_field("masks")
-        if hasattr(gt_masks, "polygons"):
+        if hasattr(gt_masks, "source_rles"):
+            # bitmap ground truth (a BinaryMaskList): its words become strings on the device; on the host path without a GPU a list
+            # that was built from RLE dicts hands those dicts through as they are
+            src = gt_masks.source_rles()
+            if src is not None and not on_device and not torch.cuda.is_available():
+                gt_masks = src
+            else:
+                gt_masks = [dict(rle, counts=rle["counts"].decode("utf-8")) for rle in gt_masks.rles()]
+        elif hasattr(gt_masks, "polygons"):
             # polygon ground truth (a SegmentationMask): rasterised at its own size into RLEs, on the device with on_device
             gt_masks = maskUtils.frPolygons(gt_masks, gt_masks.size[1], gt_masks.size[0], on_device=on_device)
             for rle in gt_masks:

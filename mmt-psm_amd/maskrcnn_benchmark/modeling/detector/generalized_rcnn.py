@@ -266,7 +266,7 @@ class GeneralizedRCNN(nn.Module):
     def _forward_teacher_targets(self, images, targets):
         """reference generalized_rcnn.py:133-139: the ground truth, moved to the device, stands in for the coarse inference -- no
         `self.forward` pass, module mode `train` throughout --, and the integral foreground mask is the sum of the annotated
-        instances' polygon masks (`SegmentationMask.decode`: csrc/polyfill.hip).  Departure: the reference decodes at a hard-coded
+        instances' masks (`SegmentationMask.decode`: csrc/polyfill.hip; a `BinaryMaskList` field sums its words the same way).  Departure: the reference decodes at a hard-coded
         800 x 800 (`get_field('masks').decode(800, 800)`), which only adds up for targets of exactly that size; here every target is
         decoded at its own size.  engine/MTtrainer.py never passes targets."""
         images = [to_image_list(im) for im in images]

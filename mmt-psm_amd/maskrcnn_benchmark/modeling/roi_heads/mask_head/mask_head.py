@@ -16,6 +16,7 @@ from maskrcnn_benchmark.modeling.matcher import Matcher
 from maskrcnn_benchmark.modeling.poolers import Pooler
 from maskrcnn_benchmark.structures.bounding_box import BoxList
 from maskrcnn_benchmark.structures.boxlist_ops import boxlist_iou
+from maskrcnn_benchmark.structures.segmentation_mask import BinaryMaskList
 from maskrcnn_benchmark.utils.miscellaneous import dev_ints
 from maskrcnn_benchmark.modeling.relation.mask_relation_module import MaskRelationRefineNet
 
@@ -210,7 +211,16 @@ class MaskRCNNLossComputation(object):
             labels.append(lab)
             # every box handed to the mask head is already a positive of the same matcher (mask_head.py:74-78),
             # so `positive_inds` is all of them; non-positives (never produced) would get an all-zero range
-            xy, poly_off, inst_rng = t.get_field("masks").packed(p.bbox.device)
+            gt_masks = t.get_field("masks")
+            if isinstance(gt_masks, BinaryMaskList):
+                # bitmap ground truth: the matched instance's words cropped to the ROI's window and resampled to M x M in one
+                # launch (`mmt_mask_words_targets`); -1 marks a non-positive, built on the device from what is already there
+                pos = pos_all[coff[i]:coff[i + 1], 0] if fused_match else (lab > 0).to(torch.int32)
+                roi_inst = (mi.to(torch.int32) + 1) * pos - 1
+                words, _ = gt_masks.mask_words(p.bbox.device)
+                mts.append(H.mask_words_targets(words, roi_inst, p.bbox, gt_masks.size[1], gt_masks.size[0], self.discretization_size))
+                continue
+            xy, poly_off, inst_rng = gt_masks.packed(p.bbox.device)
             rng = inst_rng[mi] * (pos_all[coff[i]:coff[i + 1]] if fused_match else (lab > 0).to(torch.int32)[:, None])
             mt, ovf = H.polygon_targets(xy, poly_off, rng, p.bbox, self.discretization_size)
             mts.append(mt)
