@@ -643,7 +643,7 @@ int mmt_gconv3x3_wgrad(const float* x, const float* dy, const float* rowscale, f
  *   dw[co][kh][kw][ci] += rowscale[co] * sum_{n,ho,wo} dy[n,ho,wo,co] * x[n, ci, 2 ho - 3 + kh, 2 wo - 3 + kw]
  * x [N][3][H][W] fp32 NCHW (any H, W >= 1), dy [N][Ho][Wo][64] NHWC with Ho = (H - 1) / 2 + 1, dw [64][7][7][3] (the parameter's
  * channels-last memory), rowscale [64] or NULL.  Exact fp32 products on the fp32-input MFMA; pixel ranges across blocks, summed
- * into dw with fp32 atomics like mmt_conv_wgrad's split form. */
+ * into dw with fp32 atomics like mmt_conv_wgrad's split form (in a fixed order instead: mmt_stem_wgrad_ordered, below). */
 int mmt_maxpool3x3s2_backward(const float* y, const float* g, float* dy, int N, int H, int W, int C, void* stream);
 int mmt_stem_wgrad(const float* x, const float* dy, const float* rowscale, float* dw, int N, int H, int W, void* stream);
 
@@ -875,6 +875,15 @@ int mmt_roi_align_backward_ordered(const mmt_pyramid* pyr /*[host]*/, const floa
  * functions of M alone, blocks <= MMT_COLSUM_MAX_BLOCKS), stage two adds a column's partials in block order and accumulates into
  * out.  Any C >= 1, M >= 0. */
 int mmt_colsum_ordered(const float* dy, int M, int C, float* out, float* ws, void* stream);
+/* mmt_stem_wgrad in a fixed order: arguments, shape checks and result of mmt_stem_wgrad, plus a workspace of at least
+ * mmt_stem_wgrad_ws_floats(N, H, W) floats, alive until the stream has run the call.  Stage one is the same kernel on the same grid
+ * -- min(tiles, 512) blocks, a function of the shape alone -- storing each block's rowscale-scaled sums to the workspace instead of
+ * adding them to dw; stage two adds the partials of every dw element in ascending block order and accumulates the sum into dw: the
+ * result is bitwise dw + (the result into zeros).  MMT_EINVAL, with nothing written, for a shape mmt_stem_wgrad refuses, a NULL ws
+ * or ws_floats below the need.  The query returns the need in floats (MMT_EINVAL for a refused shape) and launches nothing. */
+int mmt_stem_wgrad_ordered(const float* x, const float* dy, const float* rowscale, float* dw, int N, int H, int W, float* ws,
+                           long ws_floats, void* stream);
+long mmt_stem_wgrad_ws_floats(int N, int H, int W);
 /* the loss entry points with their scalar sums in block order: arguments and results of the entry point of the same name, plus
  * the workspace (sizes above; never NULL).  Gradients are those of the default entry points bit for bit.  mmt_box_loss_ordered
  * stands for both mmt_box_loss (n_rows NULL) and mmt_box_loss_rows; mmt_ciam_bwd_ordered: ws = n floats. */

@@ -11,8 +11,11 @@
 // wave), N = the 147 (kh, kw, ci) filter elements in the parameter's own memory order, padded to ten 16-column tiles, K = output
 // pixels, four per MFMA.  A block keeps its 64 x 160 sums in accumulators over a strided range of 4 x 16 pixel tiles -- image
 // tile with halo and gradient tile in LDS, the next tile's operands on their way into registers while this tile's MFMAs run -- and
-// adds them to dw with fp32 atomics (the form of mmt_conv_wgrad).
+// adds them to dw with fp32 atomics (the form of mmt_conv_wgrad).  Deterministic mode (mmt_stem_wgrad_ordered): the same kernel is
+// handed a workspace, stores its sums there with plain 16-byte stores instead, and a second launch (csrc/ordered.h) adds a dw
+// element's partials in ascending block order.
 #include "common.h"
+#include "ordered.h"
 
 namespace {
 
@@ -108,8 +111,20 @@ struct SwArgs {
   const float* dy;        // [N][Ho][Wo][64]
   const float* rowscale;  // [64] or null
   float* dw;              // [64][7][7][3], accumulated into
+  float* ws;              // null: atomics into dw.  Else the ordered form's partials, [block][wave][column tile][lane][e]
   int N, H, W, Ho, Wo;
   int tiles_w, tiles_img, tiles;
+};
+
+// The ordered form's workspace: a block's accumulators as they sit in registers, one 16-byte store per lane and column tile (1 KB in
+// a row per wave), the 13 padding columns included.  workspace quad -> dw index of its element e (csrc/ordered.h: ordered_finish_wide)
+constexpr int SW_BLOCK_FLOATS = 4 * SW_NT * 64 * 4;
+struct SwFinishMap {
+  __device__ long operator()(long q, int e) const {
+    const int lane = (int)(q & 63), t = (int)((q >> 6) % SW_NT), wv = (int)((q >> 6) / SW_NT);
+    const int el = t * 16 + (lane & 15);
+    return el < 147 ? (long)(wv * 16 + 4 * (lane >> 4) + e) * 147 + el : -1;
+  }
 };
 
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(SwArgs p) {
@@ -194,11 +209,21 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(SwArgs p) {
   for (int e = 0; e < 4; ++e) {
     const int co = wv * 16 + 4 * kq + e;
     const float rs = p.rowscale ? p.rowscale[co] : 1.f;
+    if (p.ws) {                                       // (wave-uniform) ordered form: scaled in place, stored below
+#pragma unroll
+      for (int t = 0; t < SW_NT; ++t) acc[t][e] *= rs;
+      continue;
+    }
 #pragma unroll
     for (int t = 0; t < SW_NT; ++t) {
       const int el = t * 16 + i;
       if (el < 147) atomicAdd(p.dw + co * 147 + el, rs * acc[t][e]);
     }
+  }
+  if (p.ws) {
+    float* wp = p.ws + (long)blockIdx.x * SW_BLOCK_FLOATS + (wv * SW_NT * 64 + lane) * 4;
+#pragma unroll
+    for (int t = 0; t < SW_NT; ++t) *reinterpret_cast<f32x4*>(wp + t * 256) = acc[t];
   }
 }
 
@@ -215,19 +240,46 @@ extern "C" int mmt_maxpool3x3s2_backward(const float* y, const float* g, float* 
   return 0;
 }
 
-extern "C" int mmt_stem_wgrad(const float* x, const float* dy, const float* rowscale, float* dw, int N, int H, int W, void* stream) {
-  if (!x || !dy || !dw || N <= 0 || H <= 0 || W <= 0) return MMT_EINVAL;
-  SwArgs a{};
-  a.x = x; a.dy = dy; a.rowscale = rowscale; a.dw = dw;
+namespace {
+
+// the shape half of the arguments -> the block count (a function of the shape alone), 0 for a shape that is not taken
+int stem_wgrad_blocks(SwArgs& a, int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
   a.N = N; a.H = H; a.W = W; a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1;
   a.tiles_w = mmt_cdiv(a.Wo, 16);
   a.tiles_img = a.tiles_w * mmt_cdiv(a.Ho, SW_TH);
   const long tiles = (long)a.tiles_img * N;
-  if (tiles > 0x7fffffffL) return MMT_EINVAL;
+  if (tiles > 0x7fffffffL) return 0;
   a.tiles = (int)tiles;
-  // two blocks per CU: pixel ranges across blocks, summed by the atomics (9408 per block)
-  const int blocks = a.tiles < 512 ? a.tiles : 512;
+  // two blocks per CU: pixel ranges across blocks, summed by the atomics (9408 per block) or in block order by the finish
+  return a.tiles < 512 ? a.tiles : 512;
+}
+
+}  // namespace
+
+extern "C" int mmt_stem_wgrad(const float* x, const float* dy, const float* rowscale, float* dw, int N, int H, int W, void* stream) {
+  SwArgs a{};
+  const int blocks = stem_wgrad_blocks(a, N, H, W);
+  if (!x || !dy || !dw || blocks == 0) return MMT_EINVAL;
+  a.x = x; a.dy = dy; a.rowscale = rowscale; a.dw = dw;
   hipLaunchKernelGGL(stem_wgrad_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
   MMT_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" long mmt_stem_wgrad_ws_floats(int N, int H, int W) {
+  SwArgs a{};
+  const int blocks = stem_wgrad_blocks(a, N, H, W);
+  return blocks == 0 ? MMT_EINVAL : (long)blocks * SW_BLOCK_FLOATS;
+}
+
+extern "C" int mmt_stem_wgrad_ordered(const float* x, const float* dy, const float* rowscale, float* dw, int N, int H, int W, float* ws,
+                                      long ws_floats, void* stream) {
+  SwArgs a{};
+  const int blocks = stem_wgrad_blocks(a, N, H, W);
+  if (!x || !dy || !dw || blocks == 0 || !ws || ws_floats < (long)blocks * SW_BLOCK_FLOATS) return MMT_EINVAL;
+  a.x = x; a.dy = dy; a.rowscale = rowscale; a.dw = dw; a.ws = ws;
+  hipLaunchKernelGGL(stem_wgrad_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+  MMT_LAUNCH_CHECK();
+  return ordered_finish_wide(ws, blocks, SW_BLOCK_FLOATS, dw, SwFinishMap{}, (hipStream_t)stream);
 }

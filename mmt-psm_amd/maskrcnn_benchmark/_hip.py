@@ -213,6 +213,7 @@ _SIGS = {
     "mmt_get_deterministic": [],
     "mmt_roi_align_backward_ordered": [ctypes.POINTER(Pyramid), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
     "mmt_colsum_ordered": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "mmt_stem_wgrad_ordered": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_long, c_void_p],
     "mmt_mask_bce_ordered": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "mmt_mgd_level_forward_ordered": [c_void_p, ctypes.POINTER(MgdTeachers), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "mmt_mgd_views_forward_ordered": [ctypes.POINTER(MgdStudents), ctypes.POINTER(MgdTeachers), c_void_p, c_int, c_int, c_int, c_int, c_void_p,
@@ -220,6 +221,10 @@ _SIGS = {
     "mmt_box_loss_ordered": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "mmt_ciam_bwd_ordered": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p],
+}
+# the entry points that return `long` (sizes in floats; include/mmtpsm.h), bound like _SIGS with that result type
+_SIGS_LONG = {
+    "mmt_stem_wgrad_ws_floats": [c_int, c_int, c_int],
 }
 
 _lib = None
@@ -777,9 +782,10 @@ def bf16_storage():
 
 # ---- deterministic mode (include/mmtpsm.h: mmt_set_deterministic).  Process-wide and opt-in: with it, the same seed,
 # build, weights and batches give bit-identical training state run to run on one device.  Every sum whose order the default kernels
-# leave to timing goes through a fixed-order form (ROIAlign backward, bias gradients, loss scalars, CIAM's gamma), the lagged
-# host-side site test is frozen, torch's own deterministic algorithms are switched on, and the configurations whose unordered sums
-# have no ordered form yet refuse.  Off: nothing here is consulted beyond one boolean per call.
+# leave to timing goes through a fixed-order form (ROIAlign backward, bias gradients, loss scalars, CIAM's gamma, the stem's weight
+# gradient), the lagged host-side site test is frozen, torch's own deterministic algorithms are switched on, and what has no ordered
+# form yet refuses (the grouped 3x3 weight gradient of ResNeXt, the CSPN mask head's multi-map ROIAlign backward; bf16 activation
+# storage).  Off: nothing here is consulted beyond one boolean per call.
 _DET = os.environ.get("MMT_DETERMINISTIC", "0") != "0"
 _DET_TORCH = None   # torch's switches as set_deterministic(True) found them: (deterministic algorithms, warn only, fill uninitialised memory)
 COLSUM_MAX_BLOCKS, MASK_BCE_WS, MGD_MAX_BLOCKS, RPN_LOSS_MAX_BLOCKS, BOX_LOSS_MAX_BLOCKS = 256, 2048, 4096, 1024, 256   # include/mmtpsm.h
@@ -856,6 +862,10 @@ def lib():
             f = getattr(L, name)
             f.restype = c_int
             f.argtypes = args
+        for name, args in _SIGS_LONG.items():
+            f = getattr(L, name)
+            f.restype = ctypes.c_long
+            f.argtypes = args
         if _DET:
             L.mmt_set_deterministic(1)
         _lib = _LibProxy(L)
@@ -875,7 +885,8 @@ def _lib_raw():
 # on: ~70 ctypes calls instead of the Python that derives them (a manual graph: hipGraph replays of the two models serialise in
 # this runtime).  Only the input's address is patched.  Queries are not recorded.
 _NO_RECORD = frozenset(("mmt_polygon_mask_words_workspace", "mmt_conv_wants_planes", "mmt_conv_pg_wanted", "mmt_conv_writes_rb", "mmt_conv_wgrad_group_workspace", "mmt_conv_variant", "mmt_conv_ksplit", "mmt_conv_pg_plan",
-                        "mmt_conv_wgrad_splits", "mmt_get_conv_precision", "mmt_packed_weight_elems", "mmt_set_conv_precision", "mmt_set_deterministic", "mmt_get_deterministic"))
+                        "mmt_conv_wgrad_splits", "mmt_get_conv_precision", "mmt_packed_weight_elems", "mmt_set_conv_precision", "mmt_set_deterministic", "mmt_get_deterministic",
+                        "mmt_stem_wgrad_ws_floats"))
 LAYOUT_EPOCH = [0]    # bumped when a flat model (re)allocates its plane buffers (engine/flat.py)
 LAUNCH_PLANS = os.environ.get("MMT_LAUNCH_PLANS", "1") != "0"
 _LP_SLOTS = 512
@@ -2436,7 +2447,14 @@ def _bias_ordered(dy, out):
     M = dy.numel() // C
     ws = torch.empty((COLSUM_MAX_BLOCKS * C,), dtype=torch.float32, device=dy.device)
     _check(lib().mmt_colsum_ordered(_p(dy), M, C, _p(out), _p(ws), _stream()), "mmt_colsum_ordered")
-    if getattr(_TLS, "stream", None) is not None:   # a side stream: the workspace lives until its caller has dealt with it
+    _keep_det_ws(ws)
+
+
+def _keep_det_ws(ws):
+    """a deterministic-mode workspace just handed to a launch.  On the current stream the caching allocator orders its reuse behind
+    the launch (inside a recorded launch plan it comes from the plan's pool and lives with the plan); on a side stream it lives until
+    the caller that set the stream has dealt with it (_drain_det_ws)"""
+    if getattr(_TLS, "stream", None) is not None:
         kept = getattr(_TLS, "det_ws", None)
         if kept is None:
             kept = _TLS.det_ws = []
@@ -2603,10 +2621,8 @@ def maxpool3x3s2_backward(y, g, out=None):
     return out
 
 
-def stem_wgrad(x, dy, dw, rowscale=None):
-    """include/mmtpsm.h: mmt_stem_wgrad.  x (N, 3, H, W) fp32 NCHW-contiguous (the image), dy (N, 64, Ho, Wo) the gradient of the
-    7x7 / stride 2 / pad 3 convolution's output; dw (64, 3, 7, 7 in the weight's channels-last layout) += rowscale[co] * the
-    weight gradient"""
+def _stem_wgrad_args(x, dy, dw, rowscale):
+    """checked (dy NHWC-dense, N, H, W) of a stem weight-gradient call"""
     _dev(x, "x")
     dy = nhwc(_dev(dy, "dy"))
     N, C, H, W = x.shape
@@ -2620,9 +2636,39 @@ def stem_wgrad(x, dy, dw, rowscale=None):
         raise RuntimeError("stem weight gradient: dw is a dense fp32 tensor in the weight's layout (64, 3, 7, 7 channels-last)")
     if rowscale is not None and not (rowscale.is_cuda and rowscale.dtype == torch.float32 and rowscale.numel() == 64 and rowscale.is_contiguous()):
         raise RuntimeError("stem weight gradient: rowscale is a dense fp32 GPU vector of 64 elements")
-    _refuse_unordered("stem_wgrad_kernel", "a trainable stem (MODEL.BACKBONE.FREEZE_CONV_BODY_AT 0)")
+    return dy, N, H, W
+
+
+def stem_wgrad(x, dy, dw, rowscale=None):
+    """include/mmtpsm.h: mmt_stem_wgrad.  x (N, 3, H, W) fp32 NCHW-contiguous (the image), dy (N, 64, Ho, Wo) the gradient of the
+    7x7 / stride 2 / pad 3 convolution's output; dw (64, 3, 7, 7 in the weight's channels-last layout) += rowscale[co] * the
+    weight gradient, the blocks' sums added with float atomics.  This form stays refused in deterministic mode
+    (tests/test_deterministic_kernels_gpu.py); the mode's callers take stem_wgrad_ordered (layers/fused.py::StemFn.backward)"""
+    dy, N, H, W = _stem_wgrad_args(x, dy, dw, rowscale)
+    if _DET:
+        raise NotImplementedError("stem_wgrad is not offered in deterministic mode: stem_wgrad_kernel adds into its destination with "
+                                  "float atomics here; call stem_wgrad_ordered, or set_deterministic(False)")
     _check(lib().mmt_stem_wgrad(_p(x), _p(dy), _p(rowscale), _p(dw), N, H, W, _stream()), "mmt_stem_wgrad")
     return dw
+
+
+def stem_wgrad_ordered(x, dy, dw, rowscale=None):
+    """include/mmtpsm.h: mmt_stem_wgrad_ordered.  stem_wgrad's arguments and result with the blocks' sums stored to a workspace and
+    added in block order: the same bits run to run, in either mode"""
+    dy, N, H, W = _stem_wgrad_args(x, dy, dw, rowscale)
+    ws = _wgrad_ordered_ws(lib().mmt_stem_wgrad_ws_floats(N, H, W), x.device, "mmt_stem_wgrad_ws_floats")
+    _check(lib().mmt_stem_wgrad_ordered(_p(x), _p(dy), _p(rowscale), _p(dw), N, H, W, _p(ws), ws.numel(), _stream()),
+           "mmt_stem_wgrad_ordered")
+    _keep_det_ws(ws)
+    return dw
+
+
+def _wgrad_ordered_ws(floats, device, what):
+    """the workspace of an ordered weight gradient, sized by the library's query (nothing in it needs clearing: every partial the
+    finish reads is written by stage one)"""
+    if floats <= 0:
+        raise RuntimeError("%s refused the shape (%d)" % (what, floats))
+    return torch.empty((floats,), dtype=torch.float32, device=device)
 
 
 # ------------------------------------------------------------------------------------------ grouped 3x3 convolution (ResNeXt conv2)

@@ -462,7 +462,8 @@ class StemFn(torch.autograd.Function):
     `pre` = (y, pooled) of the un-fused forward launches for this image batch (backbone.py: StemWithFixedBatchNorm.forward_raw, or
     batch slices of it: forward_pair); the node records the image and y.  Backward: the pool's gradient with y's ReLU mask
     (mmt_maxpool3x3s2_backward; `g` arrives masked by (pooled > 0), which changes nothing: a window whose maximum is 0 has no
-    positive element), then the weight gradient straight from the image (mmt_stem_wgrad).  The input is the image: no dx."""
+    positive element), then the weight gradient straight from the image (mmt_stem_wgrad; mmt_stem_wgrad_ordered in deterministic mode).  The input is the
+    image: no dx."""
 
     @staticmethod
     def forward(ctx, x, w, scale, pre):
@@ -478,7 +479,8 @@ class StemFn(torch.autograd.Function):
         d = ctx.dst
         dy = H.maxpool3x3s2_backward(y, H.nhwc(g))
         dw = d if d is not None else torch.zeros((64, 7, 7, 3), dtype=torch.float32, device=x.device).permute(0, 3, 1, 2)
-        H.stem_wgrad(x, dy, dw, ctx.scale)
+        # deterministic mode: block partials added in block order instead of float atomics (both launch on the current stream)
+        (H.stem_wgrad_ordered if H.get_deterministic() else H.stem_wgrad)(x, dy, dw, ctx.scale)
         _touch(d)
         return None, (None if d is not None else dw), None, None
 
