@@ -434,7 +434,8 @@ __global__ __launch_bounds__(NT) void rpn_post_kernel(const RpnPostArgs a) {
 // ------------------------------------------------------------------------------------------------ fg / bg sampler
 // labels: >= 1 positive, 0 negative, < 0 ignored; per image the num_pos = min(#pos, P) positives and
 // num_neg = min(#neg, B - num_pos) negatives with the SMALLEST keys (uniform random keys -> a uniform sample without
-// replacement, balanced_positive_negative_sampler.py:40-60); equal keys: lower index first.
+// replacement, balanced_positive_negative_sampler.py:40-60); equal keys: lower index first.  With B < num_pos (a caller
+// whose P exceeds B) num_neg is 0 in the counts as in the mask, never negative.
 // Uniform keys make this cheap: the num smallest of m keys all lie below tau = 8 num / m (expected 8 num members there),
 // so ONE pass over the labels collects the members below tau into LDS (<= 4096) and the exact select runs on that list.
 // Any key distribution stays correct: if fewer than num or more than 4096 land below tau the select runs over the whole
@@ -469,7 +470,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const LT* __restrict__ label
   if (cn) atomicAdd(&nneg_s, cn);
   __syncthreads();
   const int npos = npos_s, nneg = nneg_s;
-  const int num_pos = min(npos, max_pos), num_neg = min(nneg, batch - num_pos);
+  const int num_pos = min(npos, max_pos), num_neg = max(0, min(nneg, batch - num_pos));
   // smallest key first = largest inverted key; the index in the low word makes keys unique (equal keys: lower index first)
   auto k64 = [&](int i) -> unsigned long long {
     return ((unsigned long long)(~f2ord(ky[i])) << 32) | (unsigned)(0xffffffffu - (unsigned)i);
@@ -597,7 +598,7 @@ __global__ __launch_bounds__(NT) void sample_collect_kernel(const LT* __restrict
   const float* ky = keys + o0;
   SampleWs& w = ws[img];
   const int npos = w.npos, nneg = w.nneg;
-  const int num_pos = min(npos, max_pos), num_neg = min(nneg, batch - num_pos);
+  const int num_pos = min(npos, max_pos), num_neg = max(0, min(nneg, batch - num_pos));
   // a class needs a list only when it is actually cut (threshold(): 0 < num < members)
   const bool need_p = num_pos > 0 && npos > num_pos, need_n = num_neg > 0 && nneg > num_neg;
   if (!need_p && !need_n) return;
@@ -637,7 +638,7 @@ __global__ __launch_bounds__(NT) void sample_threshold_kernel(const LT* __restri
   const float* ky = keys + o0;
   SampleWs& w = ws[img];
   const int npos = w.npos, nneg = w.nneg;
-  const int num_pos = min(npos, max_pos), num_neg = min(nneg, batch - num_pos);
+  const int num_pos = min(npos, max_pos), num_neg = max(0, min(nneg, batch - num_pos));
   auto k64 = [&](int i) -> unsigned long long {
     return ((unsigned long long)(~f2ord(ky[i])) << 32) | (unsigned)(0xffffffffu - (unsigned)i);
   };
