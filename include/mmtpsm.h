@@ -372,16 +372,54 @@ typedef struct {
 } mmt_conv_args;
 
 int mmt_conv_forward(const mmt_conv_args* a /*[host]*/, void* stream);
-/* which tile configuration mmt_conv_forward picks for these shapes: 0 = 128x32, 1 = 128x128 (the dominant
- * kernel of the step, conv_fwd_kernel<128,128,2,2>), 2 = 64x64.  Used by bench.py for the roofline line. */
-int mmt_conv_variant(const mmt_conv_args* a /*[host]*/);
-/* number of K ranges mmt_conv_forward would use for this call on the DMA-fed kernel (1 = un-split; > 1: partial tiles go
- * through the library's per-stream workspace and a finish launch).  Tuning / measurement aid like mmt_conv_variant. */
-int mmt_conv_ksplit(const mmt_conv_args* a /*[host]*/);
-/* 1 when mmt_conv_forward would run this call on the all-planes 3x3 kernel if x_planes were given (mode 3; 3x3, stride 1,
- * pad 1, Cin % 32 == 0, Cin >= 128, W % 64 == 0, enough 256-pixel tiles to fill the chip): the caller then splits x once
- * with mmt_split_planes (or has the producing convolution write the planes) and passes them. */
-int mmt_conv_wants_planes(const mmt_conv_args* a /*[host]*/);
+/* THE ROUTE of a convolution call: which kernel the library runs it on, and with what plan.  One host function decides it
+ * (csrc/conv_route.hip) -- the launching entry points switch on its answer, and this query returns the same answer without launching.
+ *   entry   MMT_ENTRY_LIB: the dispatch of mmt_conv_forward in the current arithmetic mode; MMT_ENTRY_F16: the two-term fp16 split
+ *           of mode 3 (mmt_conv3x3_strip_f16x2, mmt_conv_forward_pg, mmt_conv_forward_f16x2 -- `family` names the one to call;
+ *           MMT_ROUTE_NONE: none of them takes the call, or the mode is not 3)
+ *   assume  operands absent from the block that the caller promises to supply before the launch (MMT_ASSUME_*: x, the fp32 weight,
+ *           the packed weight planes, planes of x -- suitably aligned --, the device scalars of the fp16 split).  A producer asks
+ *           "would a 3x3 over my output run on the tap-strip kernel if I wrote its planes?" with the bare shape and
+ *           MMT_ASSUME_X | MMT_ASSUME_W_PLANES | MMT_ASSUME_X_PLANES.
+ * The answer holds for the environment switches as they stand at the call (mmt_conv_switches).  Returns 0, or the code the launch
+ * would return for a malformed block. */
+enum { MMT_ENTRY_LIB = 0, MMT_ENTRY_F16 = 1 };
+enum { MMT_ASSUME_X = 1, MMT_ASSUME_W = 2, MMT_ASSUME_W_PLANES = 4, MMT_ASSUME_X_PLANES = 8, MMT_ASSUME_F16_SCALARS = 16 };
+enum {
+  MMT_ROUTE_NONE = 0,
+  MMT_ROUTE_FP32 = 1,      /* conv_fwd_kernel: fp32-input MFMA, operands through registers */
+  MMT_ROUTE_SPLIT = 2,     /* conv_fwd_split_kernel: bf16 terms split in registers (no packed weight) */
+  MMT_ROUTE_DMA = 3,       /* conv_fwd_glds_kernel: packed weight planes DMA-copied, x split in registers (bf16 terms or fp16 pair) */
+  MMT_ROUTE_DMA_BF16X = 4, /* conv_fwd_pp_kernel: x stored as bf16 is its own plane */
+  MMT_ROUTE_ROWS = 5,      /* conv1x1_rows_kernel: 128 rows resident in registers, panels of 32 columns */
+  MMT_ROUTE_STRIP = 6,     /* conv3x3_strip_kernel: 256 x 128 tiles over strips of `strip_tw` pixels */
+  MMT_ROUTE_PG = 7,        /* conv_pg_kernel: plane-fed implicit GEMM */
+  MMT_ROUTE_C64 = 8        /* conv3x3_c64_kernel: layer1's 3x3 patch kernel */
+};
+enum { MMT_X_AS_IS = 0, MMT_X_BF16_PLANES = 1, MMT_X_F16_PLANES = 2 };
+typedef struct {
+  int family;              /* MMT_ROUTE_*: the kernel the dispatch picks */
+  int tag;                 /* profile tag 0..5 (the host side prints fwd%d): the tile variant 0 = 128x32, 1 = 128x128, 2 = 64x64,
+                            * 3 = 128x64 of the tiled, row-resident and patch kernels; 4 = tap-strip; 5 = plane-fed */
+  int bm, bn;              /* block tile of `family` (plane-fed: bm = tile rows; patch kernel: 0) */
+  int kgroups;             /* plane-fed: K groups inside a block (256 / bm); else 1 */
+  int panels;              /* row-resident: panels per block (grid.y = column groups of that many); else 0 */
+  int ksplit;              /* K ranges of `family` (> 1: partial tiles meet in the per-stream workspace) */
+  int strip_tw, strip_ksplit, strip_korder;   /* the tap-strip kernel's plan for this call (strip_tw 0: not one of its shapes):
+                            * strip width 64 | 128, K ranges, K order (slabs per group << 24) -- what mmt_conv3x3_strip_f16x2 runs */
+  int pg_rows, pg_ksplit;  /* MMT_ENTRY_F16: the plane-fed kernel's own choice of tile rows and K ranges (0, 0: not one of its
+                            * shapes) -- what mmt_conv_forward_pg runs with tile_rows = ksplit = 0, wanted or not */
+  int wanted;              /* bit f set: kernel family f asks for this call (`family` is the first of them in the dispatch order:
+                            * tap-strip, plane-fed, patch, row-resident, tiled) */
+  int x_form;              /* MMT_X_*: what `family` reads x as (planes: mmt_conv_args.x_planes) */
+  int writes_rb;           /* MMT_ENTRY_F16: the launch this call takes can write mmt_conv_args.y_rb from its epilogue (asked by the
+                            * host before it allocates the planes; the patch kernel cannot) */
+  int switches;            /* mmt_conv_switches() as read for this answer */
+} mmt_conv_route_t;   /* (the function below carries the plain name) */
+int mmt_conv_route(const mmt_conv_args* a /*[host]*/, int entry, int assume, mmt_conv_route_t* out /*[host]*/);
+/* the six forward switches of the environment, read per call (A/B timing, parity tests): bit set = on (anything but "0") */
+enum { MMT_SW_SPLITK = 1, MMT_SW_STRIP = 2, MMT_SW_ROWS = 4, MMT_SW_PG = 8, MMT_SW_C64 = 16, MMT_SW_DIRECT_EPI = 32 };
+int mmt_conv_switches(void);
 /* arithmetic of the convolution GEMMs -- forward, data gradient and weight gradient (process-wide; initial value from
  * the environment variable MMT_CONV_PRECISION, default 3):
  *   3  fp32 operands split on the fly into three bf16 terms x = x0 + x1 + x2 (round-to-nearest at each level, exact to
@@ -401,7 +439,7 @@ int mmt_set_conv_precision(int mode);
  * caller scales each operand tensor by a power of two (largest magnitude near 2^14), passes the two fp16 planes of the input
  * (mmt_split_planes_f16 / _rb, or a producer's y_rb) and of the packed weight (mmt_pack_weight_f16 / _flipped_f16) in x_planes /
  * w_planes; the scales are device scalars derived on the device from mmt_amax (no host round trip), the epilogue divides the sum
- * by s_x s_w.  Strip shapes only (mmt_conv_wants_planes). */
+ * by s_x s_w.  Strip shapes only (mmt_conv_route: strip_tw != 0). */
 int mmt_amax(const float* x, long n, const float* rowscale, long inner, int rows, float* amax /*device, zeroed*/, void* stream);
 /* the same reduction into a 33-float statistics slot (device, zeroed): slot[0] = max |x|, slot[1..16] += sums of |x| over a
  * sample of the tensor, slot[17..32] += the sample's element counts
@@ -506,8 +544,7 @@ int mmt_replay(const mmt_call* calls /*[host]*/, int n, int* failed_index /*[hos
 int mmt_split_planes_f16_rb(const float* x, void* planes, long plane_stride, int rows, int W, int C, const float* amax,
                             float* scale_out, void* stream);
 /* Round 6 (planes out of the producers, see mmt_conv_args.y_rb).
- * mmt_conv_writes_rb: 1 when the launch mmt_conv_forward_f16x2 / mmt_conv3x3_strip_f16x2 / mmt_conv_forward_pg would take for
- *   these shapes writes y_rb from its epilogue (asked by the host before it allocates the planes); 0: the consumer splits itself.
+ * (Whether the launch a call takes writes y_rb from its epilogue: mmt_conv_route, writes_rb; 0: the consumer splits itself.)
  * mmt_sum_stats_rb: mmt_sum_stats (y = a + b (+ c) (+ d), statistics into `slot`) over an NHWC tensor of `rows` = N * H image rows
  *   of W pixels x C channels that also writes y's row-blocked fp16 planes with *scale (planes NULL: the sum and its statistics
  *   alone -- a site's first step), and max |y| into *amax_next (or NULL) --
@@ -516,7 +553,6 @@ int mmt_split_planes_f16_rb(const float* x, void* planes, long plane_stride, int
  * mmt_rb_scales_update: once per training step over the host side's table of producing sites, state[2 i] = scale, state[2 i + 1] =
  *   pending maximum (what y_amax_next / amax_next accumulated): scale <- the power of two that puts 2 x pending into [2^13, 2^14),
  *   pending <- 0; sites without a pending maximum keep their scale. */
-int mmt_conv_writes_rb(const mmt_conv_args* a /*[host]*/);
 /* Round 6: the weight gradients of a BATCH of layers (what a backward pass hands over at a time) as grouped launches -- replaces the
  * per-layer conv2d weight gradients autograd issues behind layers/misc.py:30-43 for backbone/resnet.py:202-274, backbone/fpn.py:43-69,
  * rpn/rpn.py:39-46 and the heads.  Every job is what mmt_conv_wgrad takes (a, dy, rowscale, dw, dbias; a.f16_x_amax / f16_dy_amax and
@@ -548,13 +584,10 @@ int mmt_rb_scales_update(float* state, int n, void* stream);
  * data gradient.  tile_rows: 64 | 128 | 256 (4 / 2 / 1 K groups inside a block) | 0 = the library's choice; ksplit: K ranges (> 1: partial tiles meet in the per-stream
  * workspace inside the SAME launch -- the last block of a tile to arrive adds them in the order 0 .. ksplit - 1 and runs the
  * epilogue), 0 = the library's choice.  Results are bit-identical to mmt_conv_forward_f16x2 on the tiled kernel for an equal number
- * of K ranges.  mmt_conv_pg_plan: the tile height and K ranges the library would pick (both 0: not a shape for this kernel). */
+ * of K ranges.  The tile height and K ranges the library would pick, and whether it wants the call here with a plane-split pass of x in
+ * front (3x3 and larger kernels that are not tap-strip shapes; MMT_PG=0 in the environment: never): mmt_conv_route. */
 int mmt_conv_forward_pg(const mmt_conv_args* a /*[host]*/, const float* s_x /*device*/, const float* s_w /*device*/, int tile_rows,
                         int ksplit, void* stream);
-int mmt_conv_pg_plan(const mmt_conv_args* a /*[host]*/, int* tile_rows, int* ksplit);
-/* 1 when the library wants this call on mmt_conv_forward_pg with a plane-split pass of x in front (3x3 and larger kernels that
- * are not tap-strip shapes: mmt_conv_wants_planes is asked first); 0 otherwise.  MMT_PG=0 in the environment answers 0. */
-int mmt_conv_pg_wanted(const mmt_conv_args* a /*[host]*/);
 /* Packed bf16 planes of a weight matrix w[Cout][K] (K = KH*KW*Cin in the weight's own memory order, K % 16 == 0) for
  * the split-bf16 modes.  Plane q (q = 0..2, at planes + q*plane_stride bf16 elements) holds the q-th term of the
  * round-to-nearest bf16 expansion w = w0 + w1 + w2 (exact to 2^-27 |w|), tiled as

@@ -25,8 +25,9 @@
 // ridge of HBM, so the algorithmic HBM traffic is input + weights + output once.
 //
 // Round 6: this translation unit holds the FORWARD / data-gradient kernels that read fp32 tensors (fp32 MFMA, bf16 x 3 and two-term
-// fp16 tiled kernels, the tap-strip 3x3 kernel, the row-resident 1x1 kernel, split-K finish) and the dispatch behind mmt_conv_forward /
-// mmt_conv_forward_f16x2.  The weight gradients are conv_wgrad.hip (+ conv_wgpl.hip), operand preparation (weight packing, plane
+// fp16 tiled kernels, the tap-strip 3x3 kernel, the row-resident 1x1 kernel, split-K finish), one launcher per kernel family and the
+// entry points mmt_conv_forward / mmt_conv_forward_f16x2 / mmt_conv3x3_strip_f16x2, which switch on the route of conv_route.hip (the
+// one place that decides which kernel a call runs on).  The weight gradients are conv_wgrad.hip (+ conv_wgpl.hip), operand preparation (weight packing, plane
 // splits, statistics, sums, max-pool) is conv_prep.hip, the plane-fed GEMM conv_pgemm.hip, the stem and frozen-stage kernels
 // conv_stem.hip; what they share is conv_shared.h.  One experiment rebuilds one object.
 #include <stdlib.h>
@@ -1768,8 +1769,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_rows_kernel(const ConvP p, con
 }  // namespace
 
 namespace mmtconv {
-int fill(ConvP& p, const mmt_conv_args* a) {
-  if (!a || !a->x) return MMT_EINVAL;
+int fill(ConvP& p, const mmt_conv_args* a, bool x_promised) {
+  if (!a || (!a->x && !x_promised)) return MMT_EINVAL;
   p.x = a->x; p.w = a->w; p.scale = a->scale; p.shift = a->shift; p.res = a->res; p.mask = a->mask;
   p.mul = a->mul; p.y = a->y;
   p.N = a->N; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.KH = a->KH; p.KW = a->KW;
@@ -1786,7 +1787,7 @@ int fill(ConvP& p, const mmt_conv_args* a) {
   p.f16_ax = 0;
   p.guard_x = (const float*)a->f16_guard_x; p.guard_dy = (const float*)a->f16_guard_dy;
   p.w_src = (const float*)a->w_src; p.w_src_scale = (const float*)a->w_src_scale;
-  { const char* e = getenv("MMT_DIRECT_EPI"); p.staged_epilogue = e && atoi(e) == 0; }   // read per call (A/B timing)
+  p.staged_epilogue = 0;   // (the entry points that reach a kernel with two epilogues set it from the route's switches)
   p.amax_out = (unsigned*)a->y_amax;
   p.amax_stats = a->y_amax_stats;
   p.io = a->io_bf16;
@@ -1814,6 +1815,36 @@ int fill(ConvP& p, const mmt_conv_args* a) {
 
 namespace {
 
+// ---- launchers: one per kernel family, used by the library dispatch and by the fp16-split entry points alike.  Each holds the
+// LDS size of its kernel; launch_ranges is what they share.
+
+// the attribute for a dynamic LDS size above 64 KiB once per instantiation (`done`: the instantiation's flag), the split-K workspace,
+// the launch (go(ws) issues it) and its check, the finish launch (FM x FN: its tile; 0: an instantiation that never runs split) and
+// its check.  tiles: output tiles, each in `ksplit` K ranges
+template <int FM, int FN, class Go>
+int launch_ranges(const void* kern, bool& done, size_t lds, const ConvP& p, hipStream_t s, int tiles, int ksplit, Go&& go) {
+  SplitWs w{nullptr, nullptr};
+  if (ksplit > 1) {
+    if (FM == 0) return MMT_EINVAL;
+    w = split_workspace(s);
+    if (!w.ws || (size_t)tiles * ksplit * FM * FN * sizeof(float) > SPLITK_WS_BYTES) return MMT_EINVAL;
+  }
+  if (lds > 65536 && !done) {
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    done = true;
+  }
+  go(w.ws);
+  MMT_LAUNCH_CHECK();
+  if constexpr (FM != 0) {
+    if (ksplit > 1) {
+      launch_finish<FM, FN>(p, tiles, ksplit, w.ws, s);
+      MMT_LAUNCH_CHECK();
+    }
+  }
+  return 0;
+}
+
 template <int BM, int BN, int WM, int WN>
 int launch_fwd(const ConvP& p, hipStream_t s) {
   const int tiles = mmt_cdiv(p.M, BM) * mmt_cdiv(p.Cout, BN);
@@ -1823,13 +1854,93 @@ int launch_fwd(const ConvP& p, hipStream_t s) {
   return 0;
 }
 
-template <int BM, int BN, int WM, int WN, int NS>
+template <int BM, int BN, int NS>
 int launch_split(const ConvP& p, hipStream_t s) {
   const int tiles = mmt_cdiv(p.M, BM) * mmt_cdiv(p.Cout, BN);
   size_t ring = (size_t)2 * NS * (BM + BN) * 32, epi = (size_t)BM * BN * sizeof(float);
-  hipLaunchKernelGGL((conv_fwd_split_kernel<BM, BN, WM, WN, NS>), dim3(tiles), dim3(256), ring > epi ? ring : epi, s, p);
+  hipLaunchKernelGGL((conv_fwd_split_kernel<BM, BN, 2, 2, NS>), dim3(tiles), dim3(256), ring > epi ? ring : epi, s, p);
   MMT_LAUNCH_CHECK();
   return 0;
+}
+
+constexpr int DMA_STAGES = 3;   // LDS stages of the operand ring (4 / 5 measured no faster: 36.4 / 34.8 / 35.0 us, profiles/r03_history.md)
+
+// the tiled DMA-fed kernel: activations split in registers into NS bf16 terms, or (F16) into the fp16 pair; 128-row tiles on 4 x 1 waves
+template <int BM, int BN, int NS, bool F16>
+int launch_glds(const ConvP& p, hipStream_t s, int ksplit) {
+  constexpr int S = DMA_STAGES, WM = BM == 128 ? 4 : 2, WN = BM == 128 ? 1 : 2;
+  constexpr size_t ring = (size_t)S * (BM * 64 + NS * BN * 32), epi = (size_t)BM * BN * sizeof(float), lds = ring > epi ? ring : epi;
+  auto kern = conv_fwd_glds_kernel<BM, BN, WM, WN, NS, S, F16>;
+  static bool done = false;  // per instantiation
+  const int tiles = mmt_cdiv(p.M, BM) * mmt_cdiv(p.Cout, BN);
+  return launch_ranges<BM == 128 && BN == 128 ? 128 : 0, 128>((const void*)kern, done, lds, p, s, tiles, ksplit, [&](float* ws) {
+    hipLaunchKernelGGL(kern, dim3(tiles * ksplit), dim3(256), lds, s, p, p.wpl, p.wpl_stride, ksplit, ws);
+  });
+}
+
+// x stored as bf16 (mode 1): both operands are DMA-copied as they are
+template <int BM, int BN>
+int launch_pp(const ConvP& p, hipStream_t s, int ksplit) {
+  constexpr int S = DMA_STAGES, NS = 1;
+  constexpr size_t ring = (size_t)S * NS * (BM + BN) * 32, epi = (size_t)BM * BN * sizeof(float), lds = ring > epi ? ring : epi;
+  void (*kern)(const ConvP, const int, float*) = conv_fwd_pp_kernel<BM, BN, 2, 2, NS, S>;
+  static bool done = false;  // per instantiation
+  const int tiles = mmt_cdiv(p.M, BM) * mmt_cdiv(p.Cout, BN);
+  return launch_ranges<BM == 128 && BN == 128 ? 128 : 0, 128>((const void*)kern, done, lds, p, s, tiles, ksplit, [&](float* ws) {
+    hipLaunchKernelGGL(kern, dim3(tiles * ksplit), dim3(256), lds, s, p, ksplit, ws);
+  });
+}
+
+// the tap-strip kernel with the route's plan; split: Wo == TW, tile t covers the 256 consecutive pixels [256 t', 256 t' + 256) of its
+// channel block (the finish kernel's row mapping)
+template <int TW, int NS, bool F16>
+int launch_strip(const ConvP& p, hipStream_t s, const Route& r) {
+  constexpr int R = 256 / TW, SW = TW + 32;
+  constexpr size_t ring = (size_t)2 * (NS * R * SW * 32 + 3 * NS * 128 * 32), epi = (size_t)256 * 128 * sizeof(float), lds = ring > epi ? ring : epi;
+  void (*kern)(const ConvP, const int, float*) = conv3x3_strip_kernel<TW, NS, F16>;
+  static bool done = false;  // per instantiation
+  const int tiles = p.N * (p.Ho * p.Wo / 256) * mmt_cdiv(p.Cout, 128);
+  return launch_ranges<256, 128>((const void*)kern, done, lds, p, s, tiles, r.strip_ksplit, [&](float* ws) {
+    hipLaunchKernelGGL(kern, dim3(tiles * r.strip_ksplit), dim3(512), lds, s, p, r.strip_ksplit | r.strip_korder, ws);
+  });
+}
+template <int NS, bool F16>
+int launch_strip_tw(const ConvP& p, hipStream_t s, const Route& r) {
+  return r.strip_tw == 128 ? launch_strip<128, NS, F16>(p, s, r) : launch_strip<64, NS, F16>(p, s, r);
+}
+
+// the row-resident 1x1 kernel: KT = Cin / 16 (K = 256 on the fp16 split only), `panels` per block
+template <int KT, int NS, bool F16, bool MASK>
+int launch_rows(const ConvP& p, hipStream_t s, int panels) {
+  constexpr size_t lds = 2 * (size_t)KT * NS * 1024;
+  auto kern = conv1x1_rows_kernel<KT, NS, F16, MASK>;
+  static bool done = false;  // per instantiation
+  return launch_ranges<0, 0>((const void*)kern, done, lds, p, s, 0, 1, [&](float*) {
+    hipLaunchKernelGGL(kern, dim3(mmt_cdiv(p.M, 128), mmt_cdiv(mmt_cdiv(p.Cout, 32), panels)), dim3(256), lds, s, p, p.wpl, p.wpl_stride, panels);
+  });
+}
+template <int NS, bool F16, bool MASK>
+int launch_rows_k(const ConvP& p, hipStream_t s, int panels) {
+  if (p.Cin == 64) return launch_rows<4, NS, F16, MASK>(p, s, panels);
+  if (p.Cin == 128) return launch_rows<8, NS, F16, MASK>(p, s, panels);
+  if constexpr (F16) return launch_rows<16, NS, F16, MASK>(p, s, panels);
+  return MMT_EINVAL;
+}
+
+// run-time values of the route as compile-time constants: the number of bf16 terms of a split mode, the tile of a tiled kernel
+template <class F>
+int with_terms(int mode, F&& f) {
+  if (mode == 1) return f(std::integral_constant<int, 1>{});
+  if (mode == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 3>{});
+}
+template <class F>
+int with_tile(const Route& r, F&& f) {
+  typedef std::integral_constant<int, 128> c128;
+  typedef std::integral_constant<int, 64> c64;
+  if (r.bm == 128 && r.bn == 128) return f(c128{}, c128{});
+  if (r.bm == 128 && r.bn == 64) return f(c128{}, c64{});
+  return f(c64{}, c64{});
 }
 
 }  // namespace
@@ -1853,243 +1964,6 @@ SplitWs split_workspace(hipStream_t s) {
 }
 }  // namespace mmtconv
 
-namespace {
-
-// number of K ranges for the 128 x 128 kernel: fill the 512 resident block slots when the tiles alone do not, keeping
-// at least 32 steps per range
-static int pick_ksplit(const ConvP& p) {
-  const char* on_env = getenv("MMT_SPLITK");  // read per call: the schedule-equivalence test switches it
-  if ((on_env && atoi(on_env) == 0) || p.Cout < 128) return 1;
-  const long t128 = (long)mmt_cdiv(p.M, 128) * mmt_cdiv(p.Cout, 128);
-  const int nkt = p.K >> 4;
-  constexpr int tmax = 512;   // (tuned: profiles/r04_dispatch_sweep.txt)
-  constexpr int kmin = 128;   // (tuned: profiles/r04_dispatch_sweep.txt)
-  if (t128 >= tmax || nkt < kmin) return 1;  // K >= 2048: shorter sums lose more in the second launch than they gain
-  int ks = (int)(512 / t128);
-  if (ks > nkt / 32) ks = nkt / 32;
-  if (ks > 16) ks = 16;
-  return ks < 2 ? 1 : ks;
-}
-
-template <int BM, int BN, int WM, int WN, int NS, int S>
-int launch_glds(const ConvP& p, hipStream_t s, int ksplit = 1) {
-  const int tiles = mmt_cdiv(p.M, BM) * mmt_cdiv(p.Cout, BN) * ksplit;
-  SplitWs w{nullptr, nullptr};
-  if (ksplit > 1) {
-    w = split_workspace(s);
-    if (!w.ws || tiles > 1024) return MMT_EINVAL;
-  }
-  const size_t ring = (size_t)S * (BM * 64 + NS * BN * 32), epi = (size_t)BM * BN * sizeof(float);
-  const size_t lds = ring > epi ? ring : epi;
-  auto kern = conv_fwd_glds_kernel<BM, BN, WM, WN, NS, S>;
-  if (lds > 65536) {
-    static bool done = false;  // per instantiation
-    if (!done) {
-      const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      done = true;
-    }
-  }
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), lds, s, p, p.wpl, p.wpl_stride, ksplit, w.ws);
-  MMT_LAUNCH_CHECK();
-  if (ksplit > 1) {
-    if constexpr (BM == 128 && BN == 128)
-      launch_finish<BM, BN>(p, tiles / ksplit, ksplit, w.ws, s);
-    else
-      return MMT_EINVAL;
-    MMT_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-template <int BM, int BN, int WM, int WN, int NS, int S>
-int launch_pp(const ConvP& p, hipStream_t s, int ksplit = 1) {
-  const int tiles = mmt_cdiv(p.M, BM) * mmt_cdiv(p.Cout, BN) * ksplit;
-  SplitWs w{nullptr, nullptr};
-  if (ksplit > 1) {
-    w = split_workspace(s);
-    if (!w.ws || tiles > 1024) return MMT_EINVAL;
-  }
-  const size_t ring = (size_t)S * NS * (BM + BN) * 32, epi = (size_t)BM * BN * sizeof(float);
-  const size_t lds = ring > epi ? ring : epi;
-  void (*kern)(const ConvP, const int, float*) = conv_fwd_pp_kernel<BM, BN, WM, WN, NS, S>;
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), lds, s, p, ksplit, w.ws);
-  MMT_LAUNCH_CHECK();
-  if (ksplit > 1) {
-    if constexpr (BM == 128 && BN == 128)
-      launch_finish<BM, BN>(p, tiles / ksplit, ksplit, w.ws, s);
-    else
-      return MMT_EINVAL;
-    MMT_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-// K ranges for the tap-strip kernel: 1 when its 256 x 128 tiles fill the chip (one 512-thread block per CU), else enough
-// ranges to do so -- possible when a tile's pixels are consecutive in memory (Wo == TW: the finish kernel's row mapping),
-// Cout is a multiple of 128 and every range keeps >= 6 super-steps; 0 = not a shape for this kernel
-static int strip_ksplit(const ConvP& p, int tw) {
-  const long tiles = (long)p.N * (p.Ho * p.Wo / 256) * mmt_cdiv(p.Cout, 128);
-  if (tiles >= 256) return 1;
-  // fp32 tensors (the split arithmetics): a few-tile shape is NOT taken -- this kernel needs its input as pre-split planes, a pass
-  // of its own over the tensor (~9 us on the student's N = 2 maps) that the tiled kernel, which splits in registers, does not; with
-  // equal kernel times (profiles/r04_dispatch_sweep.txt: 35.07 vs 35.12-35.23 ms) the pass is what counts: 32 fewer launches per
-  // step, 35.55 -> 35.34 ms in three same-box alternations (round 4).  bf16-stored tensors ARE their plane: split form kept.
-  if (!(p.io & IO_X)) return 0;
-  const char* e = getenv("MMT_SPLITK");
-  if ((e && atoi(e) == 0) || p.Wo != tw || (p.Cout & 127) || tiles < 32) return 0;
-  int ks = (int)((256 + tiles - 1) / tiles);
-  const int pairs = 3 * (p.Cin >> 4) / 2;
-  if (ks > pairs / 3) ks = pairs / 3;
-  if (ks > 8) ks = 8;
-  if (tiles * ks > 512) ks = (int)(512 / tiles);
-  return ks >= 2 ? ks : 0;
-}
-
-// K order of the tap-strip kernel (bits 24-30 of its ksplit argument = slabs per group, 0 = kh outermost as in rounds 2-5): groups
-// of 4 slabs, fewer where Cin / 16 is not a multiple of 4 (profiles/r06_strip_korder.txt): the fabric reads of 1 (141 MB per launch
-// instead of 278) at the cycle count of 0 -- every change of kh recomputes the copy slots' row offsets, which costs 7 % of the
-// kernel's cycles when it happens every super-step and 1 % every fourth
-static int strip_korder(const ConvP& p) {
-  int g = 4;
-  while (g > 1 && ((p.Cin >> 4) % g) != 0) g >>= 1;
-  return g << 24;
-}
-
-// 3x3 / stride 1 / pad 1 with both operands as planes: which strip width (0 = not taken)
-static int strip_tw(const ConvP& p, bool need_planes = true) {
-  if ((need_planes && !p.xpl) || !p.wpl || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.out_stride != 1 || p.Ho != p.H ||
-      p.Wo != p.W || (p.Cin & 31) || p.Cout <= 32 || ((size_t)p.xpl & 15) || (p.xpl_stride & 7))
-    return 0;
-  const char* e = getenv("MMT_STRIP");  // read per call (A/B timing)
-  if (e && atoi(e) == 0) return 0;
-  int tw = 0;
-  if (p.Wo % 128 == 0 && p.Ho % 2 == 0) tw = 128;   // 2 image rows x 128 pixels per tile; 4 x 64 where Wo % 128 != 0
-  else if (p.Wo % 64 == 0 && p.Ho % 4 == 0) tw = 64;
-  constexpr int minc = 128;   // (tuned: profiles/r04_dispatch_sweep.txt)
-  if (!tw || p.Cin < minc) return 0;  // K = 576 (the 64-channel layer1 convs): 12 super-steps do not amortise the fill
-  return strip_ksplit(p, tw) ? tw : 0;
-}
-
-template <int TW, int NS = 3>
-int launch_strip(const ConvP& p, hipStream_t s) {
-  constexpr int R = 256 / TW, SW = TW + 32;
-  const size_t ring = (size_t)2 * (NS * R * SW * 32 + 3 * NS * 128 * 32), epi = (size_t)256 * 128 * sizeof(float);
-  const size_t lds = ring > epi ? ring : epi;
-  const int ksplit = strip_ksplit(p, TW);
-  SplitWs w{nullptr, nullptr};
-  if (ksplit > 1) {
-    w = split_workspace(s);
-    if (!w.ws) return MMT_EINVAL;
-  }
-  void (*kern)(const ConvP, const int, float*) = conv3x3_strip_kernel<TW, NS>;
-  {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  const int tiles = p.N * (p.Ho * p.Wo / 256) * mmt_cdiv(p.Cout, 128);
-  hipLaunchKernelGGL(kern, dim3(tiles * ksplit), dim3(512), lds, s, p, ksplit | strip_korder(p), w.ws);
-  MMT_LAUNCH_CHECK();
-  if (ksplit > 1) {  // Wo == TW: tile t covers the 256 consecutive pixels [256 t', 256 t' + 256) of its channel block
-    launch_finish<256, 128>(p, tiles, ksplit, w.ws, s);
-    MMT_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-// panels per block of the row-resident 1x1 kernel: all of them when the row blocks alone fill the chip (>= 512 resident
-// slots), else column groups so that about 512 blocks exist (256 / 1024 / 2048 measured slower: profiles/r04_rows_epilogue.txt)
-static int rows_ppb(const ConvP& p) {
-  const int tiles_m = mmt_cdiv(p.M, 128), npanel = mmt_cdiv(p.Cout, 32);
-  if (tiles_m >= 512) return npanel;
-  int groups = mmt_cdiv(512, tiles_m);
-  if (groups > npanel) groups = npanel;
-  return mmt_cdiv(npanel, groups);
-}
-
-template <int KT, int NS, bool F16 = false, bool MASK = false>
-int launch_rows(const ConvP& p, hipStream_t s) {
-  const size_t lds = 2 * (size_t)KT * NS * 1024;
-  auto kern = conv1x1_rows_kernel<KT, NS, F16, MASK>;
-  if (lds > 65536) {
-    static bool done = false;  // per instantiation
-    if (!done) {
-      const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      done = true;
-    }
-  }
-  const int ppb = rows_ppb(p);
-  hipLaunchKernelGGL(kern, dim3(mmt_cdiv(p.M, 128), mmt_cdiv(mmt_cdiv(p.Cout, 32), ppb)), dim3(256), lds, s, p, p.wpl, p.wpl_stride, ppb);
-  MMT_LAUNCH_CHECK();
-  return 0;
-}
-
-// is this call one for the row-resident 1x1 kernel?  (K = 64 / 128 in every split mode; K = 256 on the fp16 split only)
-static bool rows_shape(const ConvP& p, bool f16) {
-  const char* rows_env = getenv("MMT_ROWS");  // read per call: the parity tests switch it
-  const int rows = rows_env ? atoi(rows_env) : 1;
-  constexpr int rows_min = 256;   // (tuned: profiles/r04_dispatch_sweep.txt)  // blocks of 128 rows (bf16 split)
-  constexpr int rows_min16 = 16;   // (tuned: profiles/r04_dispatch_sweep.txt)
-  if (!rows || p.io || p.KH != 1 || p.KW != 1 || p.stride != 1 || p.pad != 0 || p.Cout < 64 || (p.Cout & 3) || p.res_mode > 2 || p.mul ||
-      p.out_stride != 1 || (long)p.M * p.Cin * 4 >= (1L << 31) || (long)p.M * p.Cout * 4 >= (1L << 31) ||
-      (p.res_mode == 2 && (p.Wo & 7)))
-    return false;
-  if (f16) return (p.Cin == 64 || p.Cin == 128 || p.Cin == 256) && p.M >= 128 * rows_min16;
-  return !p.mask && p.res_mode <= 1 && (p.Cin == 64 || p.Cin == 128) && p.M >= 128 * rows_min;
-}
-
-template <int NS>
-int launch_glds_variant(int variant, const ConvP& p, hipStream_t s) {
-  // 1x1 / stride 1 layers with K = 64 or 128 and many rows: one block per 128 rows, all Cout panels (see the kernel)
-  if (rows_shape(p, false)) {
-    if (p.Cin == 64) return launch_rows<4, NS>(p, s);
-    if (p.Cin == 128) return launch_rows<8, NS>(p, s);
-  }
-  if (NS == 3) {
-    const int tw = strip_tw(p);
-    if (tw == 128) return launch_strip<128>(p, s);
-    if (tw == 64) return launch_strip<64>(p, s);
-  }
-  const int ksplit = pick_ksplit(p);
-  if (p.io & IO_X) {  // x stored as bf16 (mode 1 only, checked by the caller): both operands are DMA-copied as they are
-    if constexpr (NS == 1) {
-      const int tw = strip_tw(p);
-      if (tw == 128) return launch_strip<128, 1>(p, s);
-      if (tw == 64) return launch_strip<64, 1>(p, s);
-      if (ksplit > 1) return launch_pp<128, 128, 2, 2, 1, 3>(p, s, ksplit);
-      switch (variant) {
-        case 1: return launch_pp<128, 128, 2, 2, 1, 3>(p, s);
-        case 3: return launch_pp<128, 64, 2, 2, 1, 3>(p, s);
-        default: return launch_pp<64, 64, 2, 2, 1, 3>(p, s);
-      }
-    }
-    return MMT_EINVAL;
-  }
-  // activations pre-split into planes by the caller: the all-planes kernel (128 x 128 tiles, 2 x 2 waves)
-  if (ksplit > 1) return launch_glds<128, 128, 4, 1, NS, 3>(p, s, ksplit);
-  switch (variant) {
-    case 1: return launch_glds<128, 128, 4, 1, NS, 3>(p, s);
-    case 3: return launch_glds<128, 64, 4, 1, NS, 3>(p, s);
-    default: return launch_glds<64, 64, 2, 2, NS, 3>(p, s);
-  }
-}
-
-template <int NS>
-int launch_split_variant(int variant, const ConvP& p, hipStream_t s) {
-  switch (variant) {
-    case 1: return launch_split<128, 128, 2, 2, NS>(p, s);
-    case 3: return launch_split<128, 64, 2, 2, NS>(p, s);
-    default: return launch_split<64, 64, 2, 2, NS>(p, s);
-  }
-}
-
-}  // namespace
-
 namespace mmtconv {
 static int g_precision = -1;
 int precision() {
@@ -2109,7 +1983,7 @@ extern "C" int mmt_set_conv_precision(int mode) {
 
 extern "C" int mmt_get_conv_precision(void) { return precision(); }
 
-// ---- experiment: 3x3 convolution on the tap-strip kernel with a two-term fp16 split (3 products instead of 6)
+// ---- the tap-strip 3x3 kernel on the two-term fp16 split (3 products instead of 6)
 // x_planes / w_planes: the two fp16 planes of x * s_x and of the packed weight * s_w; s_x, s_w: device scalars
 extern "C" int mmt_conv3x3_strip_f16x2(const mmt_conv_args* a, const float* s_x, const float* s_w, void* stream) {
   ConvP p;
@@ -2117,52 +1991,12 @@ extern "C" int mmt_conv3x3_strip_f16x2(const mmt_conv_args* a, const float* s_x,
   if (e) return e;
   if (!p.y || !p.xpl || !p.wpl || !s_x || !s_w || p.io || p.ypl) return MMT_EINVAL;
   p.f16_sx = s_x; p.f16_sw = s_w;
-  const int tw = strip_tw(p);
-  if (!tw) return MMT_EINVAL;
-  const int ksplit = strip_ksplit(p, tw);
-  constexpr int NS = 2;
-  hipStream_t s = (hipStream_t)stream;
-  SplitWs w{nullptr, nullptr};
-  if (ksplit > 1) {
-    w = split_workspace(s);
-    if (!w.ws) return MMT_EINVAL;
-  }
-  const int tiles = p.N * (p.Ho * p.Wo / 256) * mmt_cdiv(p.Cout, 128);
-  auto go = [&](auto kern, int TW) {
-    const int R = 256 / TW, SW = TW + 32;
-    const size_t ring = (size_t)2 * (NS * R * SW * 32 + 3 * NS * 128 * 32), epi = (size_t)256 * 128 * sizeof(float);
-    const size_t lds = ring > epi ? ring : epi;
-    const hipError_t er = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (er != hipSuccess) return (int)er;
-    hipLaunchKernelGGL(kern, dim3(tiles * ksplit), dim3(512), lds, s, p, ksplit | strip_korder(p), w.ws);
-    return 0;
-  };
-  if (tw == 128) e = go(conv3x3_strip_kernel<128, NS, true>, 128);
-  else e = go(conv3x3_strip_kernel<64, NS, true>, 64);
-  if (e) return e;
-  MMT_LAUNCH_CHECK();
-  if (ksplit > 1) {
-    launch_finish<256, 128>(p, tiles, ksplit, w.ws, s);
-    MMT_LAUNCH_CHECK();
-  }
-  return 0;
+  const Route r = route(p, 3, MMT_ENTRY_F16, 0);
+  if (!r.strip_tw) return MMT_EINVAL;
+  p.staged_epilogue = !(r.switches & MMT_SW_DIRECT_EPI);
+  return launch_strip_tw<2, true>(p, (hipStream_t)stream, r);
 }
 
-static int pick_variant(const ConvP& p);
-// round 6: would the launch this call takes on the fp16 split write row-blocked planes of y from its epilogue (mmt_conv_args.y_rb)?
-// The register-direct, LDS-staged and split-K-finish epilogues do; the patch kernels (layer1's 3x3, the stem) do not
-static bool rb_epilogue_ok(const ConvP& p) {
-  if ((p.Cout & 15) || p.out_stride > 1 || (p.io & IO_Y) || p.mul || (long)p.M * p.Cout >= (1L << 30)) return false;
-  if (c64_shape(p)) return false;
-  return true;   // (the row-resident 1x1 kernel writes them from its register epilogue)
-}
-extern "C" int mmt_conv_writes_rb(const mmt_conv_args* a) {
-  ConvP p;
-  if (fill(p, a) || precision() != 3 || p.io) return 0;
-  p.f16_ax = 1;
-  p.f16_sx = p.f16_sw = (const float*)16;   // (shape question: placeholders for the shape tests that look at them)
-  return rb_epilogue_ok(p) ? 1 : 0;
-}
 // any convolution the DMA-fed kernel takes (Cin % 16 == 0, Cout > 32), raw fp32 x: x_amax = device max |x|, w_planes = the two
 // fp16 planes of the packed weight, s_w their device scale
 extern "C" int mmt_conv_forward_f16x2(const mmt_conv_args* a, const float* x_amax, const float* s_w, void* stream) {
@@ -2171,101 +2005,18 @@ extern "C" int mmt_conv_forward_f16x2(const mmt_conv_args* a, const float* x_ama
   if (e) return e;
   if (!p.y || !p.wpl || !x_amax || !s_w || p.io || p.ypl || p.xpl_rb || (p.Cin & 15) || ((size_t)p.wpl & 15) || (p.wpl_stride & 7)) return MMT_EINVAL;
   if (p.M == 0 || p.Cout == 0) return 0;
-  const int variant = pick_variant(p);
-  if (variant == 0) return MMT_EINVAL;
   p.f16_sx = x_amax; p.f16_sw = s_w; p.f16_ax = 1;
+  p.xpl = nullptr; p.xpl_stride = 0;   // x is split in registers here: its planes, if any, belong to the other two entry points
+  const Route r = route(p, 3, MMT_ENTRY_F16, 0);
+  if (r.family == MMT_ROUTE_NONE) return MMT_EINVAL;
+  if (p.yrb && !r.writes_rb) return MMT_EINVAL;   // (the caller asks mmt_conv_route first)
+  p.staged_epilogue = !(r.switches & MMT_SW_DIRECT_EPI);
   hipStream_t s = (hipStream_t)stream;
-  if (p.yrb && !rb_epilogue_ok(p)) return MMT_EINVAL;   // (the caller asks mmt_conv_writes_rb first)
-  if (c64_shape(p)) return launch_c64(p, s);   // layer1's 3x3, 64 -> 64 channels: the patch kernel (conv_stem.hip, round 5)
-  if (rows_shape(p, true)) {   // 1x1 layers with K = 64 / 128 / 256: rows resident in registers as fp16 fragments
-    if (p.mask) {
-      if (p.Cin == 64) return launch_rows<4, 2, true, true>(p, s);
-      if (p.Cin == 128) return launch_rows<8, 2, true, true>(p, s);
-      return launch_rows<16, 2, true, true>(p, s);
-    }
-    if (p.Cin == 64) return launch_rows<4, 2, true>(p, s);
-    if (p.Cin == 128) return launch_rows<8, 2, true>(p, s);
-    return launch_rows<16, 2, true>(p, s);
+  switch (r.family) {
+    case MMT_ROUTE_C64: return launch_c64(p, s);   // layer1's 3x3, 64 -> 64 channels: the patch kernel (conv_stem.hip, round 5)
+    case MMT_ROUTE_ROWS: return p.mask ? launch_rows_k<2, true, true>(p, s, r.panels) : launch_rows_k<2, true, false>(p, s, r.panels);
+    default: return with_tile(r, [&](auto BM, auto BN) { return launch_glds<decltype(BM)::value, decltype(BN)::value, 2, true>(p, s, r.ksplit); });
   }
-  const int ksplit = pick_ksplit(p);
-  constexpr int S = 3;   // LDS stages of the operand ring (4 / 5 measured no faster: 36.4 / 34.8 / 35.0 us, profiles/r03_history.md)
-  auto go = [&](auto kern, int BM, int BN, int ks) -> int {
-    const int tiles = mmt_cdiv(p.M, BM) * mmt_cdiv(p.Cout, BN) * ks;
-    SplitWs w{nullptr, nullptr};
-    if (ks > 1) {
-      w = split_workspace(s);
-      if (!w.ws || tiles > 1024) return MMT_EINVAL;
-    }
-    const size_t ring = (size_t)S * (BM * 64 + 2 * BN * 32), epi = (size_t)BM * BN * sizeof(float);
-    const size_t lds = ring > epi ? ring : epi;
-    if (lds > 65536) {
-      const hipError_t er = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (er != hipSuccess) return (int)er;
-    }
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), lds, s, p, p.wpl, p.wpl_stride, ks, w.ws);
-    if (ks > 1)
-      launch_finish<128, 128>(p, tiles / ks, ks, w.ws, s);
-    return 0;
-  };
-#define MMT_GLDS_GO(SS)                                                                                      \
-  do {                                                                                                       \
-    if (ksplit > 1) e = go(conv_fwd_glds_kernel<128, 128, 4, 1, 2, SS, true>, 128, 128, ksplit);            \
-    else if (variant == 1) e = go(conv_fwd_glds_kernel<128, 128, 4, 1, 2, SS, true>, 128, 128, 1);          \
-    else if (variant == 3) e = go(conv_fwd_glds_kernel<128, 64, 4, 1, 2, SS, true>, 128, 64, 1);            \
-    else e = go(conv_fwd_glds_kernel<64, 64, 2, 2, 2, SS, true>, 64, 64, 1);                                \
-  } while (0)
-  MMT_GLDS_GO(3);
-#undef MMT_GLDS_GO
-  if (e) return e;
-  MMT_LAUNCH_CHECK();
-  return 0;
-}
-
-static int pick_variant(const ConvP& p) {
-  if (p.Cout <= 32) return 0;
-  // K <= 256 (the 1x1 layers of layer1/layer2/FPN laterals): 2-8 k-tiles per output tile, so prologue and epilogue
-  // dominate; the 64x64 configuration keeps ~4x more blocks resident to overlap them (measured +10..25 %)
-  constexpr int lowk = 256;   // (tuned: profiles/r04_dispatch_sweep.txt)
-  constexpr int lowv = 3;   // (tuned: profiles/r04_dispatch_sweep.txt)
-  if (p.K <= lowk) return (p.Cout >= 64 && (long)mmt_cdiv(p.M, 128) * mmt_cdiv(p.Cout, 64) >= 768) ? lowv : 2;
-  // enough 128x128 tiles to fill 256 CUs (2 resident blocks each) -> 128x128; else 128x64 (twice the blocks, A tile
-  // still reused across 64 output channels); else 64x64 (4x the blocks)
-  const long t128 = (long)mmt_cdiv(p.M, 128) * mmt_cdiv(p.Cout, 128);
-  constexpr int t128min = 256;   // (tuned: profiles/r04_dispatch_sweep.txt)
-  if (t128 >= t128min && p.Cout > 64) return 1;
-  constexpr int mid = 1;   // (tuned: profiles/r04_dispatch_sweep.txt)
-  const long t12864 = (long)mmt_cdiv(p.M, 128) * mmt_cdiv(p.Cout, 64);
-  if (mid && t12864 >= 256 && p.Cout >= 64) return 3;
-  return 2;
-}
-
-extern "C" int mmt_conv_variant(const mmt_conv_args* a) {
-  ConvP p;
-  int e = fill(p, a);
-  if (e) return e;
-  const int v = pick_variant(p);
-  // conv3x3_strip_kernel: mode 3 with x_planes given, mode 1 with x stored as bf16
-  if (v != 0 && (precision() == 3 || (precision() == 1 && (p.io & IO_X))) && strip_tw(p)) return 4;
-  // the split-K form runs on the 128 x 128 kernel whatever the tile variant would have been
-  if (v != 0 && precision() > 0 && (p.Cin & 15) == 0 && p.wpl && pick_ksplit(p) > 1) return 1;
-  return v;
-}
-
-extern "C" int mmt_conv_wants_planes(const mmt_conv_args* a) {
-  ConvP p;
-  int e = fill(p, a);
-  if (e) return 0;
-  if (precision() != 3 || pick_variant(p) == 0) return 0;
-  return strip_tw(p, false) ? 1 : 0;
-}
-
-extern "C" int mmt_conv_ksplit(const mmt_conv_args* a) {
-  ConvP p;
-  int e = fill(p, a);
-  if (e) return e;
-  if (pick_variant(p) != 0 && (precision() == 3 || (precision() == 1 && (p.io & IO_X))) && strip_tw(p)) return 1;
-  if (pick_variant(p) != 0 && precision() > 0 && (p.Cin & 15) == 0 && p.wpl) return pick_ksplit(p);
-  return 1;
 }
 
 extern "C" int mmt_conv_forward(const mmt_conv_args* a, void* stream) {
@@ -2275,25 +2026,30 @@ extern "C" int mmt_conv_forward(const mmt_conv_args* a, void* stream) {
   if (!p.y || p.xpl_rb || p.yrb) return MMT_EINVAL;   // (row-blocked planes: the fp16-split entry points only)
   if (p.M == 0 || p.Cout == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const int variant = pick_variant(p);
   const int prec = precision();
-  if ((p.io & IO_X) && !(prec == 1 && variant != 0 && (p.Cin & 15) == 0 && p.wpl)) return MMT_EINVAL;  // bf16 x: DMA kernels only
-  if (!p.w && !(prec > 0 && variant != 0 && (p.Cin & 15) == 0 && p.wpl)) return MMT_EINVAL;  // planes-only call
-  if (prec > 0 && variant != 0 && (p.Cin & 15) == 0 && p.wpl) {
-    if (((size_t)p.wpl & 15) || (p.wpl_stride & 7)) return MMT_EINVAL;
-    if (prec == 1) return launch_glds_variant<1>(variant, p, s);
-    if (prec == 2) return launch_glds_variant<2>(variant, p, s);
-    return launch_glds_variant<3>(variant, p, s);
-  }
-  if (prec > 0 && variant != 0 && (p.Cin & 15) == 0) {
-    if (prec == 1) return launch_split_variant<1>(variant, p, s);
-    if (prec == 2) return launch_split_variant<2>(variant, p, s);
-    return launch_split_variant<3>(variant, p, s);
-  }
-  switch (variant) {
-    case 0: return launch_fwd<128, 32, 4, 1>(p, s);
-    case 1: return launch_fwd<128, 128, 2, 2>(p, s);
-    case 3: return launch_fwd<128, 64, 2, 2>(p, s);
-    default: return launch_fwd<64, 64, 2, 2>(p, s);
+  const Route r = route(p, prec, MMT_ENTRY_LIB, 0);
+  const bool dma = r.family != MMT_ROUTE_FP32 && r.family != MMT_ROUTE_SPLIT;   // a DMA-fed kernel: it reads the packed weight planes
+  if ((p.io & IO_X) && !(prec == 1 && dma)) return MMT_EINVAL;  // bf16 x: DMA kernels only
+  if (!p.w && !dma) return MMT_EINVAL;  // planes-only call
+  if (dma && (((size_t)p.wpl & 15) || (p.wpl_stride & 7))) return MMT_EINVAL;
+  p.staged_epilogue = !(r.switches & MMT_SW_DIRECT_EPI);
+  switch (r.family) {
+    case MMT_ROUTE_ROWS:
+      return with_terms(prec, [&](auto NS) { return launch_rows_k<decltype(NS)::value, false, false>(p, s, r.panels); });
+    case MMT_ROUTE_STRIP:   // mode 3: three bf16 planes of x; mode 1: x stored as bf16 is the one plane
+      return prec == 3 ? launch_strip_tw<3, false>(p, s, r) : launch_strip_tw<1, false>(p, s, r);
+    case MMT_ROUTE_DMA_BF16X:
+      return with_tile(r, [&](auto BM, auto BN) { return launch_pp<decltype(BM)::value, decltype(BN)::value>(p, s, r.ksplit); });
+    case MMT_ROUTE_DMA:
+      return with_terms(prec, [&](auto NS) {
+        return with_tile(r, [&](auto BM, auto BN) { return launch_glds<decltype(BM)::value, decltype(BN)::value, decltype(NS)::value, false>(p, s, r.ksplit); });
+      });
+    case MMT_ROUTE_SPLIT:
+      return with_terms(prec, [&](auto NS) {
+        return with_tile(r, [&](auto BM, auto BN) { return launch_split<decltype(BM)::value, decltype(BN)::value, decltype(NS)::value>(p, s); });
+      });
+    default:
+      if (r.bn == 32) return launch_fwd<128, 32, 4, 1>(p, s);
+      return with_tile(r, [&](auto BM, auto BN) { return launch_fwd<decltype(BM)::value, decltype(BN)::value, 2, 2>(p, s); });
   }
 }

@@ -557,32 +557,6 @@ __global__ void rb_scales_update_kernel(float* __restrict__ state, const int n) 
   state[2 * i + 1] = 0.f;
 }
 
-// is this call one the plane-fed kernel takes?  (shape / epilogue form only; the caller checked planes and arithmetic)
-bool pg_shape(const ConvP& p) {
-  return p.xpl && p.wpl && !p.io && !p.ypl && !p.mul && p.out_stride == 1 && p.res_mode <= 1 && (p.Cin & 15) == 0 && p.Cout > 32 &&
-         (long)p.N * p.H * p.W * p.Cin < (1L << 29) && (long)p.M * p.Cout * 4 < (1L << 31) && ((size_t)p.xpl & 15) == 0 &&
-         (p.xpl_stride & 7) == 0 && ((size_t)p.wpl & 15) == 0 && (p.wpl_stride & 7) == 0;
-}
-
-// tile height (64 / 128 / 256 rows: 4 / 2 / 1 K groups inside the block) and K ranges across blocks.  Every block is 8 waves and
-// takes a CU for itself: the tallest tile that still gives (nearly) every CU a block; K ranges across blocks only when even the
-// 64-row tiles leave half the chip empty and K is long
-void pg_plan(const ConvP& p, int& rows, int& ksplit) {
-  const long tn = mmt_cdiv(p.Cout, 128);
-  const long t256 = (long)mmt_cdiv(p.M, 256) * tn, t128 = (long)mmt_cdiv(p.M, 128) * tn, t64 = (long)mmt_cdiv(p.M, 64) * tn;
-  const int nkt = p.K >> 4;
-  rows = t256 >= 448 ? 256 : (t128 >= 224 ? 128 : 64);
-  ksplit = 1;
-  if (rows == 64 && t64 <= 128) {
-    int ks = (int)(256 / t64);
-    if (ks > nkt / 64) ks = nkt / 64;     // >= 16 steps per group and range
-    if (ks > 8) ks = 8;
-    if (ks >= 2) ksplit = ks;
-  }
-  const char* e = getenv("MMT_SPLITK");   // read per call: the schedule-equivalence test switches it
-  if (e && atoi(e) == 0) ksplit = 1;
-}
-
 template <int WM, int KG, int S>
 int launch_pg(const ConvP& p, hipStream_t s, int ksplit) {
   constexpr int BM = 64 * WM;
@@ -608,35 +582,6 @@ int launch_pg(const ConvP& p, hipStream_t s, int ksplit) {
 }
 
 }  // namespace
-
-extern "C" int mmt_conv_pg_plan(const mmt_conv_args* a, int* tile_rows, int* ksplit) {
-  ConvP p;
-  int e = fill(p, a);
-  if (e) return e;
-  int rows = 0, ks = 0;
-  if (precision() == 3 && p.wpl && p.M > 0 && p.Cout > 0) {
-    const unsigned short* keep = p.xpl;
-    if (!p.xpl) p.xpl = (const unsigned short*)16;   // shape question: the planes need not exist yet
-    if (pg_shape(p)) pg_plan(p, rows, ks);
-    p.xpl = keep;
-  }
-  if (tile_rows) *tile_rows = rows;
-  if (ksplit) *ksplit = ks;
-  return 0;
-}
-
-// does the library want this call on the plane-fed kernel (with a plane-split pass of x in front)?  Measured on the step's shapes
-// (profiles/r05_bench_pg.txt): yes for the 3x3 (and larger) convolutions the tap-strip kernel does not take; no for 1x1 / fc, whose
-// inputs are large against their work -- the split pass costs what the leaner loop returns
-extern "C" int mmt_conv_pg_wanted(const mmt_conv_args* a) {
-  ConvP p;
-  if (fill(p, a)) return 0;
-  if (precision() != 3 || !p.wpl || p.M <= 0 || p.Cout < 96 || p.KH * p.KW < 4) return 0;   // (Cout = 64: half of every 128-column tile would be zeros)
-  const char* e = getenv("MMT_PG");   // read per call (A/B timing, parity tests)
-  if (e && atoi(e) == 0) return 0;
-  if (!p.xpl) p.xpl = (const unsigned short*)16;
-  return pg_shape(p) ? 1 : 0;
-}
 
 extern "C" int mmt_split_planes_f16_rb(const float* x, void* planes, long plane_stride, int rows, int W, int C, const float* amax,
                                        float* scale_out, void* stream) {
@@ -684,11 +629,12 @@ extern "C" int mmt_conv_forward_pg(const mmt_conv_args* a, const float* s_x, con
   ConvP p;
   int e = fill(p, a);
   if (e) return e;
-  if (!p.xpl || !p.y || !s_x || !s_w || precision() != 3 || !pg_shape(p)) return MMT_EINVAL;
-  if (p.M == 0 || p.Cout == 0) return 0;
+  if (!p.xpl || !p.y || !s_x || !s_w || precision() != 3) return MMT_EINVAL;
   p.f16_sx = s_x; p.f16_sw = s_w;
-  int rows, ks;
-  pg_plan(p, rows, ks);
+  const Route r = route(p, 3, MMT_ENTRY_F16, 0);
+  if (!r.pg_rows) return MMT_EINVAL;   // not a shape of this kernel
+  if (p.M == 0 || p.Cout == 0) return 0;
+  int rows = r.pg_rows, ks = r.pg_ksplit;
   if (tile_rows == 64 || tile_rows == 128 || tile_rows == 256) rows = tile_rows; else if (tile_rows != 0) return MMT_EINVAL;
   if (ksplit > 0) ks = ksplit;
   if (ks < 1 || ks * (256 / rows) > (p.K >> 4)) return MMT_EINVAL;

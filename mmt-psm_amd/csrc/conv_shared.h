@@ -1,4 +1,4 @@
-// Shared by the convolution translation units (conv_igemm.hip, conv_wgrad.hip, conv_prep.hip, conv_pgemm.hip, conv_stem.hip, conv_wgpl.hip): the parameter block of every convolution kernel,
+// Shared by the convolution translation units (conv_igemm.hip, conv_route.hip, conv_wgrad.hip, conv_prep.hip, conv_pgemm.hip, conv_stem.hip, conv_wgpl.hip): the parameter block of every convolution kernel,
 // the fp16 split's range guard and its slow exact path, small vector types.  Device helpers live in an anonymous namespace (one
 // copy per translation unit); the host-side pieces with one definition (conv_igemm.hip) are declared in namespace mmtconv.
 #pragma once
@@ -29,7 +29,7 @@ struct ConvP {
   // w_src / w_src_scale: where the fp32 weights of a planes-only (data-gradient) call come from (see conv_slow_tile)
   const float* guard_x; const float* guard_dy;
   const float* w_src; const float* w_src_scale;
-  int staged_epilogue;   // (A/B timing: MMT_DIRECT_EPI=0) the tiled and tap-strip kernels leave through the LDS-staged epilogue
+  int staged_epilogue;   // (A/B timing: the route's switch MMT_SW_DIRECT_EPI off) the tiled and tap-strip kernels leave through the LDS-staged epilogue
   int xpl_rb;            // xpl is row-blocked: [N * H][Cin / 16][W][16] per plane (conv_pg_kernel only; mmt_conv_args.x_planes_layout)
   // round 6: y also as two row-blocked fp16 planes of y * *yrb_s ([N Ho][Cout / 16][Wo][16]), written by the epilogue for a plane-fed
   // consumer; amax_next: the producing site's pending maximum (-> next step's scale); xpl_lag: the scale of xpl was chosen before the
@@ -40,8 +40,13 @@ struct ConvP {
 constexpr float F16_CREST_HI = 131072.f;   // 2^17: max / mean |x| above which fp16's five exponent bits lose the bulk of the tensor
 constexpr int IO_X = 1, IO_Y = 2, IO_RES = 4, IO_MASK = 8, IO_DY = 16;
 
-// mmt_conv_args -> ConvP (conv_igemm.hip); 0 or an MMT_E* code
-int fill(ConvP& p, const mmt_conv_args* a);
+// mmt_conv_args -> ConvP (conv_igemm.hip); 0 or an MMT_E* code.  x_promised: a shape question whose caller supplies x later
+int fill(ConvP& p, const mmt_conv_args* a, bool x_promised = false);
+// THE decision which kernel a convolution call runs on (conv_route.hip; include/mmtpsm.h: mmt_conv_route).  `mode`: the arithmetic
+// (precision(); the fp16-split entry points ARE mode 3); entry: MMT_ENTRY_*; assume: MMT_ASSUME_* -- operands the block lacks and
+// the caller promises.  The launching entry points switch on the answer; nothing else tests a shape or reads a forward switch.
+typedef mmt_conv_route_t Route;
+Route route(const ConvP& p, int mode, int entry, int assume);
 // 0: fp32-input MFMA (exact fp32 products)   1: bf16   2: 2-term split (3 products)   3: 3-term split (6 products)
 int precision();
 // split-K workspace (partial tiles) + arrival counters (zeroed; whoever uses one leaves it zero), one pair per stream: kernels of a
@@ -58,8 +63,7 @@ struct WgPlJob { const mmt_conv_args* a; const float* dy; const void* xpl; long 
 int wgpl_eligible_splits(const mmt_conv_args* a);   // > 0: the plane-fed weight gradient takes the layer
 long wgpl_super_steps(const mmt_conv_args* a);      // 32-pixel super-steps of the layer's reduction
 int launch_wgpl_group(const WgPlJob* jobs, int n, hipStream_t s);
-// layer1's 3x3 (64 -> 64 channels) on the patch kernel of conv_stem.hip: is this call one, and its launch
-bool c64_shape(const ConvP& p);
+// layer1's 3x3 (64 -> 64 channels) on the patch kernel of conv_stem.hip (MMT_ROUTE_C64)
 int launch_c64(const ConvP& p, hipStream_t s);
 }  // namespace mmtconv
 

@@ -871,15 +871,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvP p, cons
 }  // namespace
 
 namespace mmtconv {
-// 3x3 / stride 1 / pad 1 with 64 input and 64 output channels on fp32 tensors, plain affine (+ ReLU) epilogue: layer1's conv2
-bool c64_shape(const ConvP& p) {
-  const char* e = getenv("MMT_C64");   // read per call (A/B timing, parity tests)
-  if (e && atoi(e) == 0) return false;
-  return p.Cin == 64 && p.Cout == 64 && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.Ho == p.H && p.Wo == p.W && !p.io &&
-         !p.ypl && !p.mul && !p.mask && p.res_mode == 0 && p.out_stride == 1 && p.wpl && p.w && p.f16_sx && p.f16_ax && p.f16_sw &&
-         (long)p.M * 64 * 4 < (1L << 31);
-}
-
 // one launch of a form of the kernel (0: the 3x3 alone, 1: + conv3, 2: + the next block's conv1)
 template <int FUSE>
 static int launch_c64_form(const ConvP& p, const C64Tail& t, hipStream_t s) {

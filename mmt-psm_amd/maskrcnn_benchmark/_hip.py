@@ -46,6 +46,16 @@ class ConvArgs(ctypes.Structure):
 IO_X, IO_Y, IO_RES, IO_MASK, IO_DY = 1, 2, 4, 8, 16  # include/mmtpsm.h: mmt_conv_args.io_bf16
 
 
+class ConvRoute(ctypes.Structure):   # include/mmtpsm.h: mmt_conv_route_t
+    _fields_ = [(n, c_int) for n in ("family", "tag", "bm", "bn", "kgroups", "panels", "ksplit", "strip_tw", "strip_ksplit", "strip_korder",
+                                     "pg_rows", "pg_ksplit", "wanted", "x_form", "writes_rb", "switches")]
+
+
+ENTRY_LIB, ENTRY_F16 = 0, 1                                                        # mmt_conv_route: entry
+ASSUME_X, ASSUME_W, ASSUME_W_PLANES, ASSUME_X_PLANES, ASSUME_F16_SCALARS = 1, 2, 4, 8, 16   # ... assume
+ROUTE_NONE, ROUTE_STRIP, ROUTE_PG = 0, 6, 7                                        # ... family (the ones the host side tells apart)
+
+
 class WgradJob(ctypes.Structure):   # include/mmtpsm.h: mmt_wgrad_job
     _fields_ = [("a", ConvArgs), ("dy", c_void_p), ("rowscale", c_void_p), ("dw", c_void_p), ("dbias", c_void_p),
                 ("x_planes", c_void_p), ("x_plane_stride", ctypes.c_long), ("dy_planes", c_void_p), ("dy_plane_stride", ctypes.c_long),
@@ -105,8 +115,8 @@ _SIGS = {
                           c_float, c_int, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                           c_void_p],
     "mmt_conv_forward": [ctypes.POINTER(ConvArgs), c_void_p],
-    "mmt_conv_variant": [ctypes.POINTER(ConvArgs)],
-    "mmt_conv_ksplit": [ctypes.POINTER(ConvArgs)],
+    "mmt_conv_route": [ctypes.POINTER(ConvArgs), c_int, c_int, c_void_p],
+    "mmt_conv_switches": [],
     "mmt_set_conv_precision": [ctypes.c_int],
     "mmt_get_conv_precision": [],
     "mmt_pack_weight": [c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_void_p],
@@ -117,7 +127,6 @@ _SIGS = {
     "mmt_box_decode": [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int,
                        c_void_p, c_void_p],
     "mmt_split_planes": [c_void_p, c_void_p, ctypes.c_long, ctypes.c_long, c_void_p],
-    "mmt_conv_wants_planes": [ctypes.POINTER(ConvArgs)],
     "mmt_pack_weights": [c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_int, c_void_p],
     "mmt_pack_weights_flipped": [c_void_p, c_void_p, c_int, c_void_p],
     "mmt_pack_weights_f16": [c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
@@ -151,7 +160,6 @@ _SIGS = {
     "mmt_split_planes_f16": [c_void_p, c_void_p, ctypes.c_long, ctypes.c_long, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "mmt_split_planes_f16_rb": [c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "mmt_replay": [c_void_p, c_int, c_void_p],
-    "mmt_conv_writes_rb": [ctypes.POINTER(ConvArgs)],
     "mmt_conv_wgrad_group_workspace": [c_void_p, c_int, ctypes.POINTER(ctypes.c_long)],
     "mmt_conv_wgrad_group": [c_void_p, c_int, c_void_p, ctypes.c_long, c_void_p],
     "mmt_sum_stats_rb": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_void_p,
@@ -165,8 +173,6 @@ _SIGS = {
     "mmt_conv3x3_strip_f16x2": [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_void_p],
     "mmt_conv_forward_f16x2": [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_void_p],
     "mmt_conv_forward_pg": [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_int, c_int, c_void_p],
-    "mmt_conv_pg_plan": [ctypes.POINTER(ConvArgs), c_void_p, c_void_p],
-    "mmt_conv_pg_wanted": [ctypes.POINTER(ConvArgs)],
     "mmt_stem_fused": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_void_p, c_void_p],
     "mmt_c64_conv3_fused": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -664,7 +670,7 @@ def _rb_produce(a, y, key):
     okk = (i, a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.stride, a.res_mode, a.mask is not None)
     ok = t.ok.get(okk)
     if ok is None:
-        ok = t.ok[okk] = (lib().mmt_conv_writes_rb(ctypes.byref(a)) == 1)
+        ok = t.ok[okk] = conv_route(a, ENTRY_F16, ASSUME_F16_SCALARS).writes_rb == 1
     if not ok:
         return None
     n = y.numel() if images is None else (y.numel() // y.shape[0]) * images
@@ -884,7 +890,7 @@ def _lib_raw():
 # pool, which keeps their addresses for the plan's life; its statistics slots from a block of the plan's own) and REPLAYED from then
 # on: ~70 ctypes calls instead of the Python that derives them (a manual graph: hipGraph replays of the two models serialise in
 # this runtime).  Only the input's address is patched.  Queries are not recorded.
-_NO_RECORD = frozenset(("mmt_polygon_mask_words_workspace", "mmt_conv_wants_planes", "mmt_conv_pg_wanted", "mmt_conv_writes_rb", "mmt_conv_wgrad_group_workspace", "mmt_conv_variant", "mmt_conv_ksplit", "mmt_conv_pg_plan",
+_NO_RECORD = frozenset(("mmt_polygon_mask_words_workspace", "mmt_conv_route", "mmt_conv_switches", "mmt_conv_wgrad_group_workspace",
                         "mmt_conv_wgrad_splits", "mmt_get_conv_precision", "mmt_packed_weight_elems", "mmt_set_conv_precision", "mmt_set_deterministic", "mmt_get_deterministic",
                         "mmt_stem_wgrad_ws_floats"))
 LAYOUT_EPOCH = [0]    # bumped when a flat model (re)allocates its plane buffers (engine/flat.py)
@@ -1021,9 +1027,9 @@ def planned(tag, fn, x):
     """fn(x) -- a no-grad pass that issues nothing but C-ABI launches and tensor allocations (a backbone pass) -- through a launch
     plan: the first call of a (tag, shape, stream, arithmetic) runs as it is (caches warm up: weight planes, folded BN), the second
     is recorded, later ones are replayed.  -> fn's result (replays return the SAME tensor objects, refilled)."""
-    env = os.environ.get   # (the library's per-call switches -- A/B timing, parity tests -- choose kernels: part of the key)
+    # (the library's per-call switches -- A/B timing, parity tests -- choose kernels: part of the key)
     key = (tag, tuple(x.shape), x.dtype, _stream(), _PLAN_EPOCH[0], PLANES_EPOCH, LAYOUT_EPOCH[0], F16X2, _PREC, _BF16_STORAGE, _RB_EPOCH[0], _DET,
-           env("MMT_STRIP"), env("MMT_SPLITK"), env("MMT_ROWS"), env("MMT_PG"), env("MMT_C64"), env("MMT_DIRECT_EPI"))
+           lib().mmt_conv_switches())
     if getattr(_TLS, "rec", None) is None and _POOL_GRAVE:
         _drain_pools()
     with _LP_LOCK:
@@ -1683,14 +1689,24 @@ def split_planes(x, out=None):
     return out
 
 
+def conv_route(a, entry, assume=0):
+    """which kernel the library runs the call with the argument block `a` on, and its plan (include/mmtpsm.h: mmt_conv_route): entry =
+    ENTRY_LIB (mmt_conv_forward's dispatch in the current mode) or ENTRY_F16 (the two-term fp16 split's three launches); assume: ASSUME_*
+    bits for operands the block lacks and the caller supplies before the launch.  A query: not counted, not recorded."""
+    r = ConvRoute()
+    code = lib().mmt_conv_route(ctypes.byref(a), entry, assume, ctypes.byref(r))
+    if code != 0:
+        raise RuntimeError("mmt_conv_route failed with code %d" % code)
+    return r
+
+
 def planes_wanted_3x3(N, C, H, W, Cout):
     """would a 3x3 / stride 1 / pad 1 convolution (C -> Cout) over an (N, C, H, W) tensor run on the all-planes kernel?
     (asked by the PRODUCER of that tensor, which then writes the planes from its epilogue: conv_forward(want_planes=True))"""
     if get_conv_precision() != 3 or F16X2:   # (on the fp16 split no epilogue writes bf16 planes: consumers scale
         return False                                              # the tensor themselves, conv_forward ignores the request)
     a = _conv_shape(ConvArgs(), N, H, W, C, Cout, 3, 3, 1, 1, H, W)
-    a.x, a.w_planes = 16, 16  # placeholders: only the shape is looked at
-    return lib().mmt_conv_wants_planes(ctypes.byref(a)) == 1
+    return conv_route(a, ENTRY_LIB, ASSUME_X | ASSUME_W_PLANES | ASSUME_X_PLANES).family == ROUTE_STRIP
 
 
 def planes_of(x):
@@ -1715,30 +1731,27 @@ FAST_PLANS = True
 # tiled / row-resident kernels (x split in registers), on the tap-strip kernel, on the plane-fed implicit GEMM (x as fp16 planes)
 K_LIB, K_TILED, K_STRIP, K_PG = -1, 0, 1, 2
 _F16_STAT = {K_TILED: "tiled", K_STRIP: "conv", K_PG: "pg"}
+_KIND_OF = {ROUTE_STRIP: K_STRIP, ROUTE_PG: K_PG}   # the route's family -> the kind (every other family: K_TILED)
 
 
-def _conv_kind(a, x, w, f16_src, io, y_out, mul, out_stride, res_mode, prec):
-    """which path the call with the argument block `a` (x, the weight or its planes, the shape and the output stride filled in) takes
-    -> (kind, is the shape one of the tap-strip kernel's, the fp16 split's weight source (tensor, flipped?, row scale) or None).
-    The strip kernel wins over the plane-fed GEMM, that over the tiled kernels; a site whose input defeats fp16 (lagged crest-factor
+def _conv_kind(a, x, w, f16_src, io, y_out, prec):
+    """which path the call with the argument block `a` (x, the weight or its planes, the shape, the output stride and `mul` filled in)
+    takes -> (kind, is the shape one of the tap-strip kernel's, the fp16 split's weight source (tensor, flipped?, row scale) or None).
+    ONE question to the library's route (planes of x and the fp16 scalars promised: they are made once the kind is known) answers
+    everything about shapes, strides and epilogue forms; what only this side knows is the arithmetic (F16X2, bf16 storage, the mode),
+    an explicit output tensor, a missing weight source and the site's verdict: a site whose input defeats fp16 (lagged crest-factor
     test, counted in F16_STATS["fallback"]) stays on the library's 3-term bf16 split."""
-    # would this shape run on the tap-strip kernel?  (asked once: the answer depends on the shape only)
-    strip = bool(a.KH == 3 and a.w_planes and not io and lib().mmt_conv_wants_planes(ctypes.byref(a)) == 1)
-    if not (F16X2 and not io and prec == 3) or (w is None and f16_src is None):
+    if F16X2 and not io and prec == 3 and y_out is None and (w is not None or f16_src is not None):
+        r = conv_route(a, ENTRY_F16, ASSUME_X_PLANES | ASSUME_F16_SCALARS)
+        strip = r.strip_tw != 0
+        if r.family != ROUTE_NONE:
+            src = (w, False, None) if w is not None else (nhwc(f16_src[0]), True, f16_src[1])
+            if _site_ok((src[0].data_ptr(), src[1]), x):
+                return _KIND_OF.get(r.family, K_TILED), strip, src
         return K_LIB, strip, None
-    if strip and out_stride == 1 and y_out is None and mul is None:
-        kind = K_STRIP
-    elif a.w_planes and a.Cout > 32 and a.Cin % 16 == 0 and y_out is None:
-        kind = K_TILED   # 1x1 layers, 3x3 on small maps, fc
-    else:
-        return K_LIB, strip, None
-    src = (w, False, None) if w is not None else (nhwc(f16_src[0]), True, f16_src[1])
-    if not _site_ok((src[0].data_ptr(), src[1]), x):
-        return K_LIB, strip, None
-    if (kind == K_TILED and mul is None and out_stride == 1 and res_mode <= 1 and a.KH * a.KW >= 4
-            and lib().mmt_conv_pg_wanted(ctypes.byref(a)) == 1):
-        kind = K_PG
-    return kind, strip, src
+    # would the library's own dispatch run this call on the tap-strip kernel, given planes of x?  (mode 3, fp32 tensors)
+    strip = prec == 3 and not io and conv_route(a, ENTRY_LIB, ASSUME_X_PLANES).family == ROUTE_STRIP
+    return K_LIB, strip, None
 
 
 def _ev():
@@ -1781,9 +1794,9 @@ def _conv_f16(a, kind, x, src, y, slot, rb_site, tile_rows=0, ksplit=0, xp=None,
     if kind == K_TILED:   # x is split in registers, its recorded maximum gives the scale
         pre = None
         if prof is not None:
-            var = lib().mmt_conv_variant(ctypes.byref(a))
-            if PROFILE_ALL or var == 1:
-                tag, ks, e0 = "fwd%d" % var, lib().mmt_conv_ksplit(ctypes.byref(a)), _ev()
+            r = conv_route(a, ENTRY_F16, ASSUME_F16_SCALARS)
+            if PROFILE_ALL or r.tag == 1:
+                tag, ks, e0 = "fwd%d" % r.tag, r.ksplit, _ev()
         _check(lib().mmt_conv_forward_f16x2(ctypes.byref(a), am[0].data_ptr(), sw.data_ptr(), _stream()), "mmt_conv_forward_f16x2")
     else:                 # x's planes (its producer's, or one split pass), then the launch
         xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x) if xp is None else (tuple(xp) + (0, 0))[:4]
@@ -1836,11 +1849,10 @@ def _conv_fast(x, w, scale, shift, stride, pad, relu, res, res_mode, mask, mask_
     if mask is not None:
         a.mask, a.mask_scale = nhwc(mask).data_ptr(), float(mask_scale)
     if a.KH == 3:
-        # the library's choice between the strip, plane-fed and tiled kernels can be switched per call (MMT_STRIP, MMT_PG): the two
-        # questions _conv_kind asked, about the shape and about weight planes being there at all (a placeholder until the launch)
-        a.w_planes = 16
-        if (lib().mmt_conv_wants_planes(ctypes.byref(a)) == 1) != (kind == K_STRIP) or (
-                kind != K_STRIP and (lib().mmt_conv_pg_wanted(ctypes.byref(a)) == 1) != (kind == K_PG)):
+        # the library's choice between the strip, plane-fed and tiled kernels can be switched per call (MMT_STRIP, MMT_PG): the
+        # question _conv_kind asked (the weight planes are made for the launch below)
+        r = conv_route(a, ENTRY_F16, ASSUME_W_PLANES | ASSUME_X_PLANES | ASSUME_F16_SCALARS)
+        if _KIND_OF.get(r.family, K_TILED) != kind:
             return None   # re-plan
     slot = _amax_slot(x.device)
     a.y_amax = slot.ptr
@@ -1929,23 +1941,8 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
         y = y_out if y_out is not None else empty_nhwc(N, Cout, Ho, Wo, x.device, dtype=out_dtype)
     a.y = y.data_ptr() + esz * int(y_offset)
     prec = get_conv_precision()
-    kind, strip, src = _conv_kind(a, x, w, f16_src, io, y_out, mul, out_stride, res_mode, prec)
-    want_amax = bool(F16X2 and not io and prec == 3)
-    if want_amax:
-        want_planes = False   # consumers on the fp16 split scale y themselves: no bf16 planes from this epilogue, max |y| recorded on the way
-    if kind != K_LIB:
-        x_planes = None       # (the fp16 kinds split x in registers or read fp16 planes of their own)
-    y_planes = None
-    if want_planes and out_stride == 1 and y_out is None and Cout % 4 == 0 and not io:
-        y_planes = torch.empty((3, y.numel()), dtype=torch.bfloat16, device=x.device)
-        a.y_planes, a.y_plane_stride = y_planes.data_ptr(), y_planes.stride(0)
-    auto_split = x_planes is None and strip and kind == K_LIB
-    if auto_split:
-        # one pass over x; the 3x3 kernel then reads bf16 planes (9 taps x Cout/128 re-reads).  Allocated here, filled
-        # below INSIDE the profiling bracket: the pass is part of this convolution's cost
-        x_planes = torch.empty((3, x.numel()), dtype=torch.bfloat16, device=x.device)
-    if x_planes is not None:
-        a.x_planes, a.x_plane_stride = x_planes.data_ptr(), x_planes.stride(0)
+    io_xy = io   # (bf16 storage of x / y: what the arithmetic goes by)
+    want_amax = bool(F16X2 and not io_xy and prec == 3)
     a.scale, a.shift = _p(scale), _p(shift)
     a.relu = 1 if relu else 0
     if res is not None:
@@ -1959,13 +1956,29 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
         if mask.dtype == torch.bfloat16:
             io |= IO_MASK
     a.io_bf16 = io
+    if mul is not None:
+        mul = nhwc(mul)
+        a.mul = mul.data_ptr()
+    kind, strip, src = _conv_kind(a, x, w, f16_src, io_xy, y_out, prec)
+    if want_amax:
+        want_planes = False   # consumers on the fp16 split scale y themselves: no bf16 planes from this epilogue, max |y| recorded on the way
+    if kind != K_LIB:
+        x_planes = None       # (the fp16 kinds split x in registers or read fp16 planes of their own)
+    y_planes = None
+    if want_planes and out_stride == 1 and y_out is None and Cout % 4 == 0 and not io_xy:
+        y_planes = torch.empty((3, y.numel()), dtype=torch.bfloat16, device=x.device)
+        a.y_planes, a.y_plane_stride = y_planes.data_ptr(), y_planes.stride(0)
+    auto_split = x_planes is None and strip and kind == K_LIB
+    if auto_split:
+        # one pass over x; the 3x3 kernel then reads bf16 planes (9 taps x Cout/128 re-reads).  Allocated here, filled
+        # below INSIDE the profiling bracket: the pass is part of this convolution's cost
+        x_planes = torch.empty((3, x.numel()), dtype=torch.bfloat16, device=x.device)
+    if x_planes is not None:
+        a.x_planes, a.x_plane_stride = x_planes.data_ptr(), x_planes.stride(0)
     amax_slot = None
     if want_amax and not io and y_out is None and out_stride == 1:
         amax_slot = _amax_slot(x.device)
         a.y_amax, a.y_amax_stats = amax_slot.ptr, 1
-    if mul is not None:
-        mul = nhwc(mul)
-        a.mul = mul.data_ptr()
     ebytes = _epilogue_bytes(y, res, res_mode, mask, mul) if PROFILE is not None else None
     if kind != K_LIB:
         if fast_ok and not io:
@@ -1974,8 +1987,8 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
             rb_site = None   # (y's row-blocked planes come out of an epilogue that also records max |y|, see f16_split_pg)
         # (a, kind, x, src, y, slot, rb_site, tile_rows, ksplit, xp, prof = the epilogue's bytes when PROFILE is on)
         return _conv_f16(a, kind, x, src, y, amax_slot, rb_site, 0, 0, None, ebytes)
-    var = lib().mmt_conv_variant(ctypes.byref(a)) if ebytes is not None else 0
-    rec = ebytes is not None and (var in (1, 4) or PROFILE_ALL)
+    r = conv_route(a, ENTRY_LIB) if ebytes is not None else None
+    rec = r is not None and (r.tag in (1, 4) or PROFILE_ALL)
     pre = None
     if auto_split:   # the plane-split pass of the input (when no producer wrote the planes): its own bracket
         p0 = _ev() if rec else None
@@ -1987,7 +2000,7 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
         planes_owner.ensure_bf16()
     _check(lib().mmt_conv_forward(ctypes.byref(a), _stream()), "mmt_conv_forward")
     if rec:
-        _profiled(a, e0, "fwd%d" % var, lib().mmt_conv_ksplit(ctypes.byref(a)), pre, ebytes)
+        _profiled(a, e0, "fwd%d" % r.tag, 1 if r.tag == 4 else r.ksplit, pre, ebytes)   # (K ranges of the tiled kernels, as ever)
     if y_planes is not None:
         y._mmt_planes = (y_planes, y._version)
     if amax_slot is not None:
@@ -2140,10 +2153,8 @@ def conv_pg_plan(N, Cin, H, W, Cout, KH, KW, stride, pad):
     """(tile rows, K ranges) the library would run this shape with on the plane-fed kernel; (0, 0): not one of its shapes"""
     Ho, Wo = _conv_out_hw(H, W, KH, KW, stride, pad)
     a = _conv_shape(ConvArgs(), N, H, W, Cin, Cout, KH, KW, stride, pad, Ho, Wo)
-    a.x = a.w_planes = 16   # placeholders: only the shape is looked at
-    rows, ks = c_int(0), c_int(0)
-    _check(lib().mmt_conv_pg_plan(ctypes.byref(a), ctypes.byref(rows), ctypes.byref(ks)), "mmt_conv_pg_plan")
-    return rows.value, ks.value
+    r = conv_route(a, ENTRY_F16, ASSUME_X | ASSUME_W_PLANES | ASSUME_X_PLANES | ASSUME_F16_SCALARS)
+    return (r.pg_rows, r.pg_ksplit) if N * Ho * Wo > 0 else (0, 0)
 
 
 # ---- who owns the derived forms of a weight (what a convolution reads instead of the weight: packed bf16 / fp16 planes of the

@@ -47,18 +47,27 @@ def _cl(t):
 
 
 def _shape_args(H, N, Cin, Hh, W, Cout, k, pad):
+    """the bare shape; what the caller promises to supply goes into the route question (_route)"""
     a = H.ConvArgs()
-    a.x = a.w_planes = 16   # placeholders: the queries look at the shape only
     a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = N, Hh, W, Cin, Cout, k, k
     a.stride, a.pad, a.Ho, a.Wo, a.out_stride = 1, pad, Hh + 2 * pad - k + 1, W + 2 * pad - k + 1, 1
     return a
+
+
+def _route(H, entry, a, planes=False):
+    """the library's route for a shape-only block: x and the weight planes promised, planes of x and the fp16 scalars on request"""
+    return H.conv_route(a, entry, H.ASSUME_X | H.ASSUME_W_PLANES | ((H.ASSUME_X_PLANES | H.ASSUME_F16_SCALARS) if planes else 0))
+
+
+def _wants_planes(H, a):
+    return H.get_conv_precision() == 3 and _route(H, H.ENTRY_LIB, a, True).family == H.ROUTE_STRIP
 
 
 def _strip_shape(H):
     """the smallest 3x3 shape the tap-strip kernel takes (the library's own answer: for fp32 tensors it wants 256 tiles of 256 pixels x
     128 channels before it gives up the tiled kernel's in-register split, so the first two candidates are declined today)"""
     for s in ((1, 128, 4, 64, 64), (1, 128, 8, 128, 64), (2, 128, 64, 128, 512), (2, 128, 128, 128, 256)):
-        if H.lib().mmt_conv_wants_planes(ctypes.byref(_shape_args(H, s[0], s[1], s[2], s[3], s[4], 3, 1))) == 1:
+        if _wants_planes(H, _shape_args(H, s[0], s[1], s[2], s[3], s[4], 3, 1)):
             return s
     raise AssertionError("no strip-shaped candidate")
 
@@ -68,7 +77,7 @@ def _pg_shape(H):
     for s in ((2, 128, 16, 16, 128), (2, 128, 32, 32, 128), (2, 128, 64, 64, 128), (4, 128, 64, 64, 128)):
         rows, ks = H.conv_pg_plan(s[0], s[1], s[2], s[3], s[4], 3, 3, 1, 1)
         a = _shape_args(H, s[0], s[1], s[2], s[3], s[4], 3, 1)
-        if rows != 0 and ks == 1 and H.lib().mmt_conv_wants_planes(ctypes.byref(a)) == 0 and H.lib().mmt_conv_pg_wanted(ctypes.byref(a)) == 1:
+        if rows != 0 and ks == 1 and not _wants_planes(H, a) and _route(H, H.ENTRY_F16, a, True).wanted >> H.ROUTE_PG & 1 == 1:
             return s
     raise AssertionError("no plane-fed candidate with one K range")
 
@@ -83,6 +92,10 @@ def _case(H, name):
     from maskrcnn_benchmark.layers import fused
     if name in ("tiled_1x1", "bf16x3_1x1"):
         x0, w = _rand((2, 64, 16, 16), 1).relu(), _rand((64, 64, 1, 1), 2, 0.1)
+        s, b = torch.rand(64, device="cuda") + 0.5, torch.randn(64, device="cuda") * 0.1
+        return x0, lambda x: H.conv_forward(x, w, s, b, 1, 0, relu=True)
+    if name == "rows_1x1":   # M = 2048 = 128 * 16: the smallest shape that reaches the row-resident kernel on the fp16 split
+        x0, w = _rand((2, 64, 32, 32), 1).relu(), _rand((64, 64, 1, 1), 2, 0.1)
         s, b = torch.rand(64, device="cuda") + 0.5, torch.randn(64, device="cuda") * 0.1
         return x0, lambda x: H.conv_forward(x, w, s, b, 1, 0, relu=True)
     if name == "tiled_3x3_res":
@@ -190,6 +203,7 @@ _SPLIT = ("amax_pass", "rb_split")
 EXPECT = {
     # first call: bf16 weight pack + reduction pass over the fresh x + fp16 weight pack (2) + launch; plan path: pass + launch
     "tiled_1x1": _f16("tiled", 5, 2, 3, [(0, None), (1, "fwd2")]),
+    "rows_1x1": _f16("tiled", 5, 2, 3, [(0, None), (1, "fwd2")]),   # (the row-resident kernel; recorded on the parent of the commit that added the case)
     "tiled_3x3_res": _f16("tiled", 5, 2, 3, [(0, None), (1, "fwd2")]),
     "tiled_3x3_rb": _f16("tiled", 5, 2, 3, [(0, None), (1, "fwd2")]),
     # the plane-fed kinds add the row-blocked split pass of x
@@ -208,7 +222,7 @@ EXPECT = {
                    "profile": [(0, None), (1, "fwd2")], "planes": False, "rb": None},
 }
 
-FORWARD_CASES = ("tiled_1x1", "tiled_3x3_res", "tiled_3x3_rb", "pg_rb", "strip", "pg", "dgrad_tiled_mask", "dgrad_tiled_res", "dgrad_pg_mask", "dgrad_pg_res",
+FORWARD_CASES = ("tiled_1x1", "rows_1x1", "tiled_3x3_res", "tiled_3x3_rb", "pg_rb", "strip", "pg", "dgrad_tiled_mask", "dgrad_tiled_res", "dgrad_pg_mask", "dgrad_pg_res",
                  "bf16x3_strip", "bf16x3_1x1")
 
 
@@ -251,7 +265,8 @@ def test_shapes_are_not_split_over_k(hip):
     """bitwise comparison above is meaningful only for launches that are not split over K with atomics"""
     H = hip
     for s, k, pad in (((2, 64, 16, 16, 64), 1, 0), ((2, 64, 16, 16, 64), 3, 1), (_strip_shape(H), 3, 1)):
-        assert H.lib().mmt_conv_ksplit(ctypes.byref(_shape_args(H, s[0], s[1], s[2], s[3], s[4], k, pad))) == 1, (s, k)
+        r = _route(H, H.ENTRY_LIB, _shape_args(H, s[0], s[1], s[2], s[3], s[4], k, pad))
+        assert (1 if r.family == H.ROUTE_STRIP else r.ksplit) == 1, (s, k)
     s = _pg_shape(H)
     assert H.conv_pg_plan(s[0], s[1], s[2], s[3], s[4], 3, 3, 1, 1)[1] == 1
 

@@ -178,7 +178,6 @@ def test_split_k_in_one_launch(hip, case, splits):
 def test_split_k_equals_the_tiled_kernels_split_k(hip):
     """equal K ranges, equal order of the partial sums: the launch pair of the tiled kernel and the one-launch form agree bit for bit"""
     H = hip
-    import ctypes
     case = (2, 256, 64, 64, 256, 3, 1, 1, "bn relu")
     N, C, Hh, W, Co, k, stride, pad, opts = case
     x, w, sc, sh, kw = _make(case, seed=11)
@@ -189,10 +188,9 @@ def test_split_k_equals_the_tiled_kernels_split_k(hip):
     finally:
         os.environ.pop("MMT_PG", None)
     a = H.ConvArgs()
-    a.x = a.w_planes = 16
     a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW = N, Hh, W, C, Co, k, k
     a.stride, a.pad, a.Ho, a.Wo, a.out_stride = stride, pad, Hh, W, 1
-    ks = H.lib().mmt_conv_ksplit(ctypes.byref(a))
+    ks = H.conv_route(a, H.ENTRY_LIB, H.ASSUME_X | H.ASSUME_W_PLANES).ksplit   # (the tiled kernel's: MMT_STRIP is still off)
     assert ks > 1
     y = H.conv_forward_pg(x, w, sc, sh, stride, pad, tile_rows=256, ksplit=ks, **kw)       # every range in a block of its own
     assert torch.equal(y, y_old)
