@@ -1,5 +1,8 @@
 """Deterministic mode at bench size: is a run repeatable, and what does the mode cost?
-  python det_steps.py [steps] [timed]
+  python det_steps.py [steps] [timed] [--set KEY VALUE]...
+--set merges configuration keys into the defaults of both parts (the children are then tests/det_cfg_worker.py, which takes the same
+pairs): `--set MODEL.BACKBONE.FREEZE_CONV_BODY_AT 0` measures the mode with a trainable stem.  A configuration the mode refuses ends
+part 1 with the refusal's message.
 1. tests/det_worker.py -- the bench's trainer (2 + 2 crops of 1000 x 1000, BASE_LR 0.005, seed 0), `steps` (10) mean-teacher steps with the
    mode on -- twice, as fresh child processes one after the other; the per-step SHA-256 digests of the student's flat buffer, its
    momentum, the teacher's flat buffer and the losses side by side, and the first step that differs, if any.  Acceptance: none.
@@ -15,13 +18,23 @@ import torch
 
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 sys.path.insert(0, os.path.join(ROOT, "mmt-psm_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
-steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-timed = int(sys.argv[2]) if len(sys.argv) > 2 else 12
+argv, keys = sys.argv[1:], []
+while "--set" in argv:
+    i = argv.index("--set")
+    if len(argv) < i + 3:
+        raise SystemExit("--set takes a key and a value")
+    keys += argv[i + 1:i + 3]
+    del argv[i:i + 3]
+steps = int(argv[0]) if len(argv) > 0 else 10
+timed = int(argv[1]) if len(argv) > 1 else 12
 
+worker = [os.path.join(ROOT, "tests", "det_cfg_worker.py")] + [a for k, v in zip(keys[0::2], keys[1::2]) for a in ("--set", k, v)] if keys \
+    else [os.path.join(ROOT, "tests", "det_worker.py")]
 runs = []
 for r in range(2):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "det_worker.py"), "--crop", "0", "--n-inst", "0", "--steps", str(steps)],
+    out = subprocess.run([sys.executable] + worker + ["--crop", "0", "--n-inst", "0", "--steps", str(steps)],
                          capture_output=True, text=True, timeout=900)
     if out.returncode != 0:   # (the second child is not started after a first that failed)
         raise SystemExit("run %d ended with exit status %d:\n%s" % (r, out.returncode, out.stderr[-3000:]))
@@ -39,8 +52,10 @@ print("two fresh processes, %d steps at bench size, mode on: %s" % (steps, "iden
                                                                    else "FIRST DIFFERENCE at step %s" % first), flush=True)
 
 import bench
+from det_cfg_worker import default_cfg_with
 from maskrcnn_benchmark import _hip as H
-cfg, trainer, batch = bench.build(torch.device("cuda", 0), 0, base_lr=bench.BENCH_BASE_LR)
+with default_cfg_with(keys):
+    cfg, trainer, batch = bench.build(torch.device("cuda", 0), 0, base_lr=bench.BENCH_BASE_LR)
 it0 = cfg.MT.START_MT + cfg.MT.RAMPUP_STEP + 100
 ms = {False: [], True: []}
 calls = {}
