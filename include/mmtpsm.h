@@ -254,6 +254,38 @@ int mmt_ciam_fwd(const float* x, const int64_t* group, int n, int C, int HW, int
                  float* out, void* stream);
 int mmt_ciam_bwd(const float* x, const int64_t* group, int n, int C, int HW, int max_group, const float* gamma, const float* A,
                  const int* J, const float* dout, float* T, float* R, float* dx, float* dgamma, void* stream);
+/* mmt_ciam_norm_{fwd,bwd}: the same module with the reference's normalisations in front of the softmax (MODEL.RELATION_MASK.NORM
+ * and PRE_NORM, mask_relation_module.py:214-232).  norm: 1 = "sum channel", 2 = "L2 norm", any other value = none (the
+ * reference's else branch); pre_norm: 0 / 1.  Arguments as above; the bound of a group's size is n itself.  Every sum the
+ * reference takes over its (image, class) slice is taken over the group:
+ *   s[i] = 1 / ||x[i]||_2 over the instance's C HW values with pre_norm, 1 without;  E[c][i][j] = s[i] s[j] <x[i,c,:], x[j,c,:]>
+ *   (only the energies read the normalised features; the mix and the residual read x);
+ *   norm 1: S[c] = sum_{i,j} E[c][i][j] (computed as ||sum_i s[i] x[i,c,:]||^2), w[c] = |S[c]| / max_c' |S[c']|, N = w[c] E;
+ *   norm 2: F[i][j] = sqrt(sum_c E[c][i][j]^2), N = E / (F + 1e-10);   else N = E;
+ *   M[i][j] = mean_c (max_j' N[c][i][j'] - N[c][i][j]); A = softmax_j M over the group; out = gamma A x + x.
+ * Kept for the backward: A [n][n], J [C][n] = the arg-max column of N[c][i][:] (first index on a tie; with norm 2 it may differ
+ * from that of E) and `saved`, mmt_ciam_norm_saved_floats(n, C) = n C n + n + n C floats: E [n][C][n] (entries inside the group),
+ * s [n] (pre_norm only), S [n][C] at the group's first instance (norm 1 only).  s and S come from two small launches in front of
+ * the main one (one owner and one summation order per value: no float atomics), so a forward pass is 1 to 3 launches.
+ * bwd: dout -> dx, dgamma through every term (the instance norm, the channel weights with their quotient by the maximum -- the
+ * gradient of the maximum goes to the first channel that attains it --, the L2 factor).  ws = mmt_ciam_norm_ws_floats(n, C) =
+ * n n + n + n C + n floats (T, R, the rows' shares of the channel weights' gradient, the rows' shares of dgamma).  dgamma: zeroed
+ * here, then one atomic per instance; _bwd_ordered adds the rows' shares in row order instead (mmt_ciam_bwd_ordered).  dx is the
+ * same bits in both forms and from run to run.  2 launches (3 with norm 1) and the memset; the ordered form one more.
+ * Capacity: n <= 512, C <= 16 and mmt_ciam_norm_lds_bytes(n, C, HW) = 4 max(C HW + (C + 1) n, (C + 4) n) <= 65536 -- the default
+ * kernels' limit; beyond it MMT_EINVAL and nothing is launched.  The three queries launch nothing (MMT_EINVAL for sizes < 1).
+ * Degenerate inputs (the reference yields NaN or an undefined sub-gradient in each): an all-zero instance with pre_norm gives
+ * s = inf and NaN in its group; all S[c] zero with norm 1 gives NaN in the group; two channels tying for max |S|: the first
+ * takes the maximum's gradient; F[i][j] = 0 with norm 2: the forward pass gives N = 0 there, the backward NaN.  J stays inside
+ * the group whatever the values. */
+long mmt_ciam_norm_lds_bytes(int n, int C, int HW);
+long mmt_ciam_norm_saved_floats(int n, int C);
+long mmt_ciam_norm_ws_floats(int n, int C);
+int mmt_ciam_norm_fwd(const float* x, const int64_t* group, int n, int C, int HW, int norm, int pre_norm, const float* gamma,
+                      float* saved, float* A, int* J, float* out, void* stream);
+int mmt_ciam_norm_bwd(const float* x, const int64_t* group, int n, int C, int HW, int norm, int pre_norm, const float* gamma,
+                      const float* saved, const float* A, const int* J, const float* dout, float* ws, float* dx, float* dgamma,
+                      void* stream);
 /* mmt_rpn_loss: the RPN's two losses over all anchors of the batch (reference modeling/rpn/loss.py:183-194, with the sampler's
  * masks instead of index gathers): obj [R] logits, reg / regt [R][4] (16-byte aligned), labels [R] float (-1 / 0 / 1), pos / neg
  * [R] bool bytes.  n = max(#(pos | neg), 1); out[0] = sum_{pos | neg} BCEWithLogits(obj, max(label, 0)) / n; out[1] =
@@ -931,6 +963,11 @@ int mmt_box_loss_ordered(const float* logits, const float* breg, const int64_t* 
 int mmt_ciam_bwd_ordered(const float* x, const int64_t* group, int n, int C, int HW, int max_group, const float* gamma,
                          const float* A, const int* J, const float* dout, float* T, float* R, float* dx, float* dgamma, float* ws,
                          void* stream);
+/* mmt_ciam_norm_bwd with dgamma's rows' shares added in row order (arguments, workspace and every other result of
+ * mmt_ciam_norm_bwd) */
+int mmt_ciam_norm_bwd_ordered(const float* x, const int64_t* group, int n, int C, int HW, int norm, int pre_norm,
+                              const float* gamma, const float* saved, const float* A, const int* J, const float* dout, float* ws,
+                              float* dx, float* dgamma, void* stream);
 
 #ifdef __cplusplus
 }

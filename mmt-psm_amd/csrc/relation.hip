@@ -453,6 +453,322 @@ __global__ __launch_bounds__(256) void ciam_bwd_dx_kernel(const float* __restric
   }
 }
 
+// ---------------------------------------------------------------- CIAM with the reference's normalisations, forward
+// MODEL.RELATION_MASK.NORM 1 / 2 and PRE_NORM (reference mask_relation_module.py:214-232) in front of the softmax; every sum
+// "over the slice" of the reference runs over the group.  With s[i] = 1 / ||x[i]||_2 over the instance's C HW values under
+// PRE_NORM and 1 without it:
+//   E[c][i][j] = s[i] s[j] <x[i,c,:], x[j,c,:]>     (only the energies read the normalised features: the mix and the residual
+//                                                    read x)
+//   NORM 1:  S[c] = sum_{i,j} E[c][i][j] = ||sum_i s[i] x[i,c,:]||^2;  w[c] = |S[c]| / max_c' |S[c']|;  N = w[c] E
+//   NORM 2:  F[i][j] = sqrt(sum_c E[c][i][j]^2);  N = E / (F + 1e-10)
+//   else:    N = E
+// and then as above with N in the place of E (J is the arg-max of N).  s and S need values of other workgroups, so they come
+// from two small launches in front (no float atomics: every value has one owner and one summation order); the main kernel is the
+// default one with the scale on the energy, the raw E rows written out for the backward, and N formed in place in LDS.
+constexpr float CI_EPS = 1e-10f;
+
+__device__ __forceinline__ float block_sum(float v, float* s_red) {   // 256 threads; ends with every thread holding the sum
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+// s[i] = 1 / ||x[i]||_2: one workgroup per instance
+__global__ __launch_bounds__(256) void ciam_inorm_kernel(const float* __restrict__ x, int CH, float* __restrict__ s) {
+  __shared__ float s_red[4];
+  const int i = blockIdx.x;
+  float a = 0.f;
+  for (int e = threadIdx.x; e < CH; e += 256) {
+    const float v = x[(long)i * CH + e];
+    a = fmaf(v, v, a);
+  }
+  a = block_sum(a, s_red);
+  if (threadIdx.x == 0) s[i] = 1.f / sqrtf(a);
+}
+
+// S[lo][c] = ||sum_{i in the group that starts at lo} s[i] x[i,c,:]||^2: grid (n, C), only the workgroups of a group's FIRST
+// instance work (a group is a contiguous run); the instances are added in index order, the pixels by the fixed block reduction
+__global__ __launch_bounds__(256) void ciam_chansum_kernel(const float* __restrict__ x, const int64_t* __restrict__ grp, int n, int C,
+                                                           int HW, const float* __restrict__ s, float* __restrict__ S) {
+  const int i = blockIdx.x, c = blockIdx.y;
+  if (i > 0 && grp[i - 1] == grp[i]) return;
+  __shared__ int s_lo, s_hi;
+  __shared__ float s_red[4];
+  group_bounds(grp, n, i, &s_lo, &s_hi);
+  const int nj = s_hi - i;
+  float a = 0.f;
+  for (int h = threadIdx.x; h < HW; h += 256) {
+    float v = 0.f;
+    for (int j = 0; j < nj; ++j) v = fmaf(s ? s[i + j] : 1.f, x[((long)(i + j) * C + c) * HW + h], v);
+    a = fmaf(v, v, a);
+  }
+  a = block_sum(a, s_red);
+  if (threadIdx.x == 0) S[(long)i * C + c] = a;
+}
+
+// the channel weights of NORM 1 from the group's sums (lanes of one wave, lane = channel): w = |S| / max |S|, `cstar` the first
+// channel at the maximum, `mx` the maximum
+__device__ __forceinline__ float ciam_channel_weight(const float* __restrict__ Sg, int C, int lane, int* cstar, float* mx) {
+  const float v = lane < C ? fabsf(Sg[lane]) : -INFINITY;
+  const float m = wave_max(v);
+  int cand = v == m ? lane : 0x7fffffff;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+  *cstar = cand;
+  *mx = m;
+  return v / m;
+}
+
+__global__ __launch_bounds__(256) void ciam_norm_fwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ grp, int n, int C,
+                                                            int HW, int norm, const float* __restrict__ gamma,
+                                                            const float* __restrict__ s, const float* __restrict__ S,
+                                                            float* __restrict__ Es, float* __restrict__ A, int* __restrict__ J,
+                                                            float* __restrict__ out) {
+  extern __shared__ float lds[];
+  const int i = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  __shared__ int s_lo, s_hi;
+  __shared__ float s_w[CI_MAXC];
+  group_bounds(grp, n, i, &s_lo, &s_hi);
+  float* xi = lds;                      // [C][HW]
+  const int CH = C * HW;
+  for (int e = tid; e < CH; e += 256) xi[e] = x[(long)i * CH + e];
+  __syncthreads();
+  const int lo = s_lo, nj = s_hi - s_lo;
+  float* E = xi + CH;                   // [C][nj]   E, then N
+  float* Mr = E + C * nj;               // [nj]
+  if (norm == 1 && wave == 0) {
+    int cstar;
+    float mx;
+    const float w = ciam_channel_weight(S + (long)lo * C, C, lane, &cstar, &mx);
+    if (lane < C) s_w[lane] = w;
+  }
+  const float si = s ? s[i] : 1.f;
+  for (int t = tid; t < C * nj; t += 256) {
+    const int c = t / nj, j = t - c * nj;
+    const float* xj = x + (long)(lo + j) * CH + (long)c * HW;
+    const float* xc = xi + c * HW;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    int h = 0;
+    if ((HW & 3) == 0) {
+      for (; h < HW; h += 4) {
+        const float4 u = *(const float4*)(xj + h);
+        a0 = fmaf(xc[h], u.x, a0);
+        a1 = fmaf(xc[h + 1], u.y, a1);
+        a2 = fmaf(xc[h + 2], u.z, a2);
+        a3 = fmaf(xc[h + 3], u.w, a3);
+      }
+    }
+    for (; h < HW; ++h) a0 = fmaf(xc[h], xj[h], a0);
+    float e = (a0 + a1) + (a2 + a3);
+    if (s) e *= si * s[lo + j];
+    E[t] = e;
+    Es[((long)i * C + c) * n + lo + j] = e;
+  }
+  __syncthreads();
+  if (norm == 1) {
+    for (int t = tid; t < C * nj; t += 256) E[t] *= s_w[t / nj];
+    __syncthreads();
+  } else if (norm == 2) {
+    for (int j = tid; j < nj; j += 256) {
+      float q = 0.f;
+      for (int c = 0; c < C; ++c) q = fmaf(E[c * nj + j], E[c * nj + j], q);
+      const float f = sqrtf(q) + CI_EPS;
+      for (int c = 0; c < C; ++c) E[c * nj + j] /= f;
+    }
+    __syncthreads();
+  }
+  // from here on the default kernel, on N
+  __shared__ float s_mx[CI_MAXC];
+  for (int c = wave; c < C; c += 4) {
+    float best = -INFINITY;
+    int bj = 0x7fffffff;
+    for (int j = lane; j < nj; j += 64) {
+      const float e = E[c * nj + j];
+      if (e > best) { best = e; bj = j; }
+    }
+    const float mx = wave_max(best);
+    int cand = best == mx ? bj : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+    if (lane == 0) {
+      s_mx[c] = mx;
+      J[(long)c * n + i] = lo + min(cand, nj - 1);   // (a row of NaN has no maximum: the index stays inside the group)
+    }
+  }
+  __syncthreads();
+  const float invC = 1.f / (float)C;
+  for (int j = tid; j < nj; j += 256) {
+    float a = 0.f;
+    for (int c = 0; c < C; ++c) a += s_mx[c] - E[c * nj + j];
+    Mr[j] = a * invC;
+  }
+  __syncthreads();
+  __shared__ float s_red[4];
+  float mx = -INFINITY;
+  for (int j = tid; j < nj; j += 256) mx = fmaxf(mx, Mr[j]);
+  mx = wave_max(mx);
+  if (lane == 0) s_red[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+  __syncthreads();
+  float sm = 0.f;
+  for (int j = tid; j < nj; j += 256) {
+    const float e = expf(Mr[j] - mx);
+    Mr[j] = e;
+    sm += e;
+  }
+  sm = wave_sum(sm);
+  if (lane == 0) s_red[wave] = sm;
+  __syncthreads();
+  const float inv = 1.f / (s_red[0] + s_red[1] + s_red[2] + s_red[3]);
+  for (int j = tid; j < n; j += 256) {
+    const int jj = j - lo;
+    const float a = (jj >= 0 && jj < nj) ? Mr[jj] * inv : 0.f;
+    A[(long)i * n + j] = a;
+    if (jj >= 0 && jj < nj) Mr[jj] = a;
+  }
+  __syncthreads();
+  const float gm = gamma[0];
+  for (int e = tid; e < CH; e += 256) {
+    float a = 0.f;
+    for (int j = 0; j < nj; ++j) a = fmaf(Mr[j], x[(long)(lo + j) * CH + e], a);
+    out[(long)i * CH + e] = gm * a + xi[e];
+  }
+}
+
+// ---------------------------------------------------------------- CIAM with the reference's normalisations, backward
+// The softmax row pass does not see the normalisation: ciam_bwd_rows_kernel gives T = dM, R = its row sums and dgamma (in both
+// of its forms) as it stands.  With dN[c][i][j] = (R[i] [j == J[c][i]] - T[i][j]) / C (the default dE, J the arg-max of N):
+//   NORM 1:  dw[c] = sum_{i,j} dN E  (over the group: P below holds the rows' shares, added in instance order);
+//            dS[c] = (dw[c] - [c == c*] sum_c' dw[c'] w[c']) / max |S|   (c* the first channel at the maximum; S >= 0);
+//            dE = w[c] dN + dS[c]
+//   NORM 2:  D[i][j] = sum_c dN E;  dE = dN / (F + eps) - D E / (F (F + eps)^2)
+//   PRE_NORM: E = s[i] s[j] G with G the raw energies: dG = s[i] s[j] dE, and through s[i] = ||x[i]||^-1
+//            dx[i] -= s[i]^2 (sum_{c,j} (dE[c][i][j] + dE[c][j][i]) E[c][i][j]) x[i]
+//   dx[i] = dOut[i] + sum_j gamma A[j][i] dOut[j] + per channel sum_j s[i] s[j] (dE[c][i][j] + dE[c][j][i]) x[j,c,:] + the line above
+// E and F are symmetric in (i, j), so the workgroup of i forms dE[c][i][j] + dE[c][j][i] from its own saved E rows.
+__global__ __launch_bounds__(256) void ciam_norm_bwd_p_kernel(const int64_t* __restrict__ grp, int n, int C, const int* __restrict__ J,
+                                                              const float* __restrict__ Es, const float* __restrict__ T,
+                                                              const float* __restrict__ R, float* __restrict__ P) {
+  const int i = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __shared__ int s_lo, s_hi;
+  group_bounds(grp, n, i, &s_lo, &s_hi);
+  const int lo = s_lo, nj = s_hi - s_lo;
+  const float invC = 1.f / (float)C;
+  for (int c = wave; c < C; c += 4) {
+    const float* er = Es + ((long)i * C + c) * n;
+    float a = 0.f;
+    for (int j = lane; j < nj; j += 64) a = fmaf(T[(long)i * n + lo + j], er[lo + j], a);
+    a = wave_sum(a);
+    if (lane == 0) P[(long)i * C + c] = (R[i] * er[J[(long)c * n + i]] - a) * invC;
+  }
+}
+
+__global__ __launch_bounds__(256) void ciam_norm_bwd_dx_kernel(const float* __restrict__ x, const int64_t* __restrict__ grp, int n, int C,
+                                                               int HW, int norm, const float* __restrict__ gamma,
+                                                               const float* __restrict__ A, const int* __restrict__ J,
+                                                               const float* __restrict__ Es, const float* __restrict__ s,
+                                                               const float* __restrict__ S, const float* __restrict__ T,
+                                                               const float* __restrict__ R, const float* __restrict__ P,
+                                                               const float* __restrict__ dout, float* __restrict__ dx) {
+  extern __shared__ float lds[];
+  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  __shared__ int s_lo, s_hi;
+  __shared__ float s_red[4], s_w[CI_MAXC], s_ds[CI_MAXC], s_part[CI_MAXC * 16];
+  group_bounds(grp, n, i, &s_lo, &s_hi);
+  const int lo = s_lo, nj = s_hi - s_lo;
+  const int CH = C * HW;
+  float* W = lds;                        // [C][nj]  dE[c][i][j] + dE[c][j][i], then the coefficient of x[j, c, :] in dx[i, c, :]
+  float* Am = W + C * nj;                // [nj]     gamma A[j][i]
+  float* Fj = Am + nj;                   // [nj]     F[i][j]        (NORM 2)
+  float* Dj = Fj + nj;                   // [nj]     D[i][j] + D[j][i]
+  float* sj = Dj + nj;                   // [nj]     s[j]           (PRE_NORM)
+  const float invC = 1.f / (float)C, gm = gamma[0];
+  const float* Ei = Es + (long)i * C * n;   // E[c][i][j] at Ei[c * n + j]
+  if (norm == 1) {
+    // dw[c]: the rows' shares of the group in a fixed order (16 strided partial sums per channel, added in order)
+    if (tid < C * 16) {
+      const int c = tid >> 4, k = tid & 15;
+      float a = 0.f;
+      for (int j = k; j < nj; j += 16) a += P[(long)(lo + j) * C + c];
+      s_part[tid] = a;
+    }
+    __syncthreads();
+    if (tid < 64) {
+      float p = 0.f;
+      if (lane < C)
+        for (int k = 0; k < 16; ++k) p += s_part[lane * 16 + k];
+      int cstar;
+      float mx;
+      const float w = ciam_channel_weight(S + (long)lo * C, C, lane, &cstar, &mx);
+      const float pw = wave_sum(lane < C ? p * w : 0.f);
+      if (lane < C) {
+        s_w[lane] = w;
+        s_ds[lane] = (p - (lane == cstar ? pw : 0.f)) / mx;
+      }
+    }
+  }
+  for (int t = tid; t < C * nj; t += 256) {
+    const int c = t / nj, j = lo + (t - c * nj);
+    float w = -(T[(long)i * n + j] + T[(long)j * n + i]);      // dN[c][i][j] + dN[c][j][i]
+    if (J[(long)c * n + i] == j) w += R[i];
+    if (J[(long)c * n + j] == i) w += R[j];
+    W[t] = w * invC;
+  }
+  for (int j = tid; j < nj; j += 256) {
+    Am[j] = gm * A[(long)(lo + j) * n + i];
+    if (s) sj[j] = s[lo + j];
+  }
+  __syncthreads();
+  if (norm == 1) {
+    for (int t = tid; t < C * nj; t += 256) {
+      const int c = t / nj;
+      W[t] = fmaf(s_w[c], W[t], 2.f * s_ds[c]);
+    }
+  } else if (norm == 2) {
+    for (int j = tid; j < nj; j += 256) {
+      float q = 0.f, d = 0.f;
+      for (int c = 0; c < C; ++c) {
+        const float e = Ei[(long)c * n + lo + j];
+        q = fmaf(e, e, q);
+        d = fmaf(W[c * nj + j], e, d);
+      }
+      Fj[j] = sqrtf(q);
+      Dj[j] = d;
+    }
+    __syncthreads();
+    for (int t = tid; t < C * nj; t += 256) {
+      const int c = t / nj, j = t - c * nj;
+      const float f = Fj[j], fe = f + CI_EPS;
+      W[t] = W[t] / fe - Dj[j] * Ei[(long)c * n + lo + j] / (f * fe * fe);
+    }
+  }
+  float selfc = 0.f;
+  if (s) {
+    const float si = s[i];
+    float q = 0.f;
+    for (int t = tid; t < C * nj; t += 256) {   // (each thread its own entries of W: no barrier since they were written)
+      const int c = t / nj, j = t - c * nj;
+      q = fmaf(W[t], Ei[(long)c * n + lo + j], q);
+      W[t] *= si * sj[j];
+    }
+    selfc = -si * si * block_sum(q, s_red);
+  }
+  __syncthreads();
+  for (int e = tid; e < CH; e += 256) {
+    const int c = e / HW;
+    float a = dout[(long)i * CH + e];
+    for (int j = 0; j < nj; ++j) {
+      a = fmaf(Am[j], dout[(long)(lo + j) * CH + e], a);
+      a = fmaf(W[c * nj + j], x[(long)(lo + j) * CH + e], a);
+    }
+    if (s) a = fmaf(selfc, x[(long)i * CH + e], a);
+    dx[(long)i * CH + e] = a;
+  }
+}
+
 }  // namespace
 
 static int ra_set_lds(const void* kern, size_t lds) {
@@ -543,4 +859,89 @@ extern "C" int mmt_ciam_bwd_ordered(const float* x, const int64_t* group, int n,
                                     float* ws, void* stream) {
   if (!ws) return MMT_EINVAL;
   return ciam_bwd_launch(x, group, n, C, HW, max_group, gamma, A, J, dout, T, R, dx, dgamma, ws, stream);
+}
+
+// ---- the normalised variants.  One capacity expression for every launch of the forward and the backward (the default kernels'
+// limit: the variants keep the instance's features and its energy rows in LDS like they do, and stay below 64 KiB).
+extern "C" long mmt_ciam_norm_lds_bytes(int n, int C, int HW) {
+  if (n < 1 || C < 1 || HW < 1) return MMT_EINVAL;
+  const size_t fwd = ciam_lds(C, HW, n), dxk = sizeof(float) * (size_t)(C + 4) * n;
+  return (long)(fwd > dxk ? fwd : dxk);
+}
+
+extern "C" long mmt_ciam_norm_saved_floats(int n, int C) {
+  if (n < 1 || C < 1) return MMT_EINVAL;
+  return (long)n * C * n + n + (long)n * C;      // E [n][C][n], s [n], S [n][C]
+}
+
+extern "C" long mmt_ciam_norm_ws_floats(int n, int C) {
+  if (n < 1 || C < 1) return MMT_EINVAL;
+  return (long)n * n + n + (long)n * C + n;      // T [n][n], R [n], P [n][C], the rows' shares of dgamma [n]
+}
+
+static bool ciam_norm_fits(int n, int C, int HW) {
+  return n >= 1 && n <= CI_MAXG && C >= 1 && C <= CI_MAXC && HW >= 1 && mmt_ciam_norm_lds_bytes(n, C, HW) <= 64 * 1024;
+}
+
+extern "C" int mmt_ciam_norm_fwd(const float* x, const int64_t* group, int n, int C, int HW, int norm, int pre_norm,
+                                 const float* gamma, float* saved, float* A, int* J, float* out, void* stream) {
+  if (!x || !group || !gamma || !saved || !A || !J || !out || !ciam_norm_fits(n, C, HW)) return MMT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  float* Es = saved;
+  float* s = pre_norm ? Es + (size_t)n * C * n : nullptr;
+  float* S = Es + (size_t)n * C * n + n;
+  if (s) {
+    hipLaunchKernelGGL(ciam_inorm_kernel, dim3(n), dim3(256), 0, st, x, C * HW, s);
+    MMT_LAUNCH_CHECK();
+  }
+  if (norm == 1) {
+    hipLaunchKernelGGL(ciam_chansum_kernel, dim3(n, C), dim3(256), 0, st, x, group, n, C, HW, (const float*)s, S);
+    MMT_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(ciam_norm_fwd_kernel, dim3(n), dim3(256), ciam_lds(C, HW, n), st, x, group, n, C, HW, norm, gamma, (const float*)s,
+                     (const float*)S, Es, A, J, out);
+  MMT_LAUNCH_CHECK();
+  return 0;
+}
+
+static int ciam_norm_bwd_launch(const float* x, const int64_t* group, int n, int C, int HW, int norm, int pre_norm, const float* gamma,
+                                const float* saved, const float* A, const int* J, const float* dout, float* ws, float* dx,
+                                float* dgamma, bool ordered, void* stream) {
+  if (!x || !group || !gamma || !saved || !A || !J || !dout || !ws || !dx || !dgamma || !ciam_norm_fits(n, C, HW)) return MMT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const float* Es = saved;
+  const float* s = pre_norm ? Es + (size_t)n * C * n : nullptr;
+  const float* S = Es + (size_t)n * C * n + n;
+  float* T = ws;
+  float* R = T + (size_t)n * n;
+  float* P = R + n;
+  float* part = ordered ? P + (size_t)n * C : nullptr;
+  if (hipMemsetAsync(dgamma, 0, sizeof(float), st) != hipSuccess) return MMT_EINVAL;
+  hipLaunchKernelGGL(ciam_bwd_rows_kernel, dim3(n), dim3(256), sizeof(float) * ((size_t)C * HW + n), st, x, group, n, C, HW, gamma, A,
+                     dout, T, R, dgamma, part);
+  MMT_LAUNCH_CHECK();
+  if (part) {
+    const int e = ordered_finish(part, n, 1, dgamma, st);
+    if (e) return e;
+  }
+  if (norm == 1) {
+    hipLaunchKernelGGL(ciam_norm_bwd_p_kernel, dim3(n), dim3(256), 0, st, group, n, C, J, Es, (const float*)T, (const float*)R, P);
+    MMT_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(ciam_norm_bwd_dx_kernel, dim3(n), dim3(256), sizeof(float) * (size_t)(C + 4) * n, st, x, group, n, C, HW, norm,
+                     gamma, A, J, Es, s, S, (const float*)T, (const float*)R, (const float*)P, dout, dx);
+  MMT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmt_ciam_norm_bwd(const float* x, const int64_t* group, int n, int C, int HW, int norm, int pre_norm, const float* gamma,
+                                 const float* saved, const float* A, const int* J, const float* dout, float* ws, float* dx,
+                                 float* dgamma, void* stream) {
+  return ciam_norm_bwd_launch(x, group, n, C, HW, norm, pre_norm, gamma, saved, A, J, dout, ws, dx, dgamma, false, stream);
+}
+
+extern "C" int mmt_ciam_norm_bwd_ordered(const float* x, const int64_t* group, int n, int C, int HW, int norm, int pre_norm,
+                                         const float* gamma, const float* saved, const float* A, const int* J, const float* dout,
+                                         float* ws, float* dx, float* dgamma, void* stream) {
+  return ciam_norm_bwd_launch(x, group, n, C, HW, norm, pre_norm, gamma, saved, A, J, dout, ws, dx, dgamma, true, stream);
 }

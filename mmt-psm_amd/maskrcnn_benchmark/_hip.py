@@ -227,10 +227,18 @@ _SIGS = {
     "mmt_box_loss_ordered": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "mmt_ciam_bwd_ordered": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p],
+    "mmt_ciam_norm_fwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mmt_ciam_norm_bwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                          c_void_p, c_void_p, c_void_p],
+    "mmt_ciam_norm_bwd_ordered": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p],
 }
 # the entry points that return `long` (sizes in floats; include/mmtpsm.h), bound like _SIGS with that result type
 _SIGS_LONG = {
     "mmt_stem_wgrad_ws_floats": [c_int, c_int, c_int],
+    "mmt_ciam_norm_lds_bytes": [c_int, c_int, c_int],
+    "mmt_ciam_norm_saved_floats": [c_int, c_int],
+    "mmt_ciam_norm_ws_floats": [c_int, c_int],
 }
 
 _lib = None
@@ -892,7 +900,7 @@ def _lib_raw():
 # this runtime).  Only the input's address is patched.  Queries are not recorded.
 _NO_RECORD = frozenset(("mmt_polygon_mask_words_workspace", "mmt_conv_route", "mmt_conv_switches", "mmt_conv_wgrad_group_workspace",
                         "mmt_conv_wgrad_splits", "mmt_get_conv_precision", "mmt_packed_weight_elems", "mmt_set_conv_precision", "mmt_set_deterministic", "mmt_get_deterministic",
-                        "mmt_stem_wgrad_ws_floats"))
+                        "mmt_stem_wgrad_ws_floats", "mmt_ciam_norm_lds_bytes", "mmt_ciam_norm_saved_floats", "mmt_ciam_norm_ws_floats"))
 LAYOUT_EPOCH = [0]    # bumped when a flat model (re)allocates its plane buffers (engine/flat.py)
 LAUNCH_PLANS = os.environ.get("MMT_LAUNCH_PLANS", "1") != "0"
 _LP_SLOTS = 512
@@ -1547,6 +1555,49 @@ def ciam_bwd(x, group, gamma, A, J, dout):
         return dx, dgamma
     _check(lib().mmt_ciam_bwd(_p(x), _p(group), n, C, HW, n, _p(gamma), _p(A), _p(J), _p(dout), _p(ws), ws.data_ptr() + 4 * n * n, _p(dx),
                               _p(dgamma), _stream()), "mmt_ciam_bwd")
+    return dx, dgamma
+
+
+def ciam_norm_kind(norm):
+    """MODEL.RELATION_MASK.NORM as the kernels read it: 1 ("sum channel"), 2 ("L2 norm"), anything else 0 (none: the reference's
+    else branch takes every other value)"""
+    return int(norm) if norm in (1, 2) else 0
+
+
+def ciam_norm_fits(n, C, HW):
+    """the capacity of mmt_ciam_norm_fwd / _bwd, by the library's own expression (include/mmtpsm.h: mmt_ciam_norm_lds_bytes)"""
+    return 0 < n <= CIAM_MAX_N and 0 < C <= 16 and 0 < HW and 0 < lib().mmt_ciam_norm_lds_bytes(n, C, HW) <= 65536
+
+
+def ciam_norm_fwd(x, group, gamma, norm, pre_norm):
+    """include/mmtpsm.h: mmt_ciam_norm_fwd.  x, group, gamma as ciam_fwd; norm 1 / 2 / other, pre_norm bool
+    -> out like x, A (n, n), J (C, n) int32, saved (the energies and the normalisation's sums, for ciam_norm_bwd)"""
+    n, C = x.shape[0], x.shape[1]
+    HW = x.shape[2] * x.shape[3]
+    if not ciam_norm_fits(n, C, HW):
+        raise RuntimeError("mmt_ciam_norm_fwd: n = %d, C = %d, HW = %d is beyond 1..%d instances, 16 channels or 64 KiB of LDS "
+                           "(mmt_ciam_norm_lds_bytes)" % (n, C, HW, CIAM_MAX_N))
+    out = torch.empty((n, C, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device)
+    A = torch.empty((n, n), dtype=torch.float32, device=x.device)
+    J = torch.empty((C, n), dtype=torch.int32, device=x.device)
+    saved = torch.empty((lib().mmt_ciam_norm_saved_floats(n, C),), dtype=torch.float32, device=x.device)
+    _check(lib().mmt_ciam_norm_fwd(_p(x), _p(group), n, C, HW, ciam_norm_kind(norm), int(bool(pre_norm)), _p(gamma), _p(saved), _p(A),
+                                   _p(J), _p(out), _stream()), "mmt_ciam_norm_fwd")
+    return out, A, J, saved
+
+
+def ciam_norm_bwd(x, group, gamma, norm, pre_norm, saved, A, J, dout):
+    """include/mmtpsm.h: mmt_ciam_norm_bwd; in deterministic mode mmt_ciam_norm_bwd_ordered -> dx, dgamma"""
+    n, C = x.shape[0], x.shape[1]
+    HW = x.shape[2] * x.shape[3]
+    if not ciam_norm_fits(n, C, HW):
+        raise RuntimeError("mmt_ciam_norm_bwd: n = %d, C = %d, HW = %d is beyond the kernels' capacity" % (n, C, HW))
+    dx = torch.empty((n, C, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device)
+    ws = torch.empty((lib().mmt_ciam_norm_ws_floats(n, C),), dtype=torch.float32, device=x.device)
+    dgamma = torch.empty((1,), dtype=torch.float32, device=x.device)
+    f, what = (lib().mmt_ciam_norm_bwd_ordered, "mmt_ciam_norm_bwd_ordered") if _DET else (lib().mmt_ciam_norm_bwd, "mmt_ciam_norm_bwd")
+    _check(f(_p(x), _p(group), n, C, HW, ciam_norm_kind(norm), int(bool(pre_norm)), _p(gamma), _p(saved), _p(A), _p(J), _p(dout), _p(ws),
+             _p(dx), _p(dgamma), _stream()), what)
     return dx, dgamma
 
 

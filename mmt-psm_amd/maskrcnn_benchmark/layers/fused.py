@@ -961,18 +961,30 @@ class RelationAttentionFn(torch.autograd.Function):
 class CIAMFn(torch.autograd.Function):
     """IR-Net's cross-instance attention (reference relation/mask_relation_module.py:199-242) over all (image, class) groups
     of the batch: one forward launch, two backward launches (csrc/relation.hip): x (n, C, H, W), group (n,) int64 with
-    equal ids contiguous, gamma (1,) -> gamma * attention(x) + x"""
+    equal ids contiguous, gamma (1,) -> gamma * attention(x) + x.  norm / pre_norm: MODEL.RELATION_MASK.NORM (1, 2, anything
+    else = none) and PRE_NORM; the default pair (none, False) goes to mmt_ciam_fwd / _bwd, every other pair to
+    mmt_ciam_norm_fwd / _bwd"""
 
     @staticmethod
-    def forward(ctx, x, group, gamma):
+    def forward(ctx, x, group, gamma, norm=-1, pre_norm=False):
         ctx.xtype = x.dtype
+        ctx.variant = (H.ciam_norm_kind(norm), bool(pre_norm))
         x = x.float().contiguous()          # NCHW-dense rows [C][H W] per instance
-        out, A, J = H.ciam_fwd(x, group.contiguous(), gamma)
-        ctx.save_for_backward(x, group, gamma, A, J)
+        if ctx.variant == (0, False):
+            out, A, J = H.ciam_fwd(x, group.contiguous(), gamma)
+            ctx.save_for_backward(x, group, gamma, A, J)
+        else:
+            out, A, J, saved = H.ciam_norm_fwd(x, group.contiguous(), gamma, *ctx.variant)
+            ctx.save_for_backward(x, group, gamma, A, J, saved)
         return out if out.dtype == ctx.xtype else out.to(ctx.xtype)
 
     @staticmethod
     def backward(ctx, g):
-        x, group, gamma, A, J = ctx.saved_tensors
-        dx, dgamma = H.ciam_bwd(x, group.contiguous(), gamma, A, J, g.float().contiguous())
-        return (dx if dx.dtype == ctx.xtype else dx.to(ctx.xtype)), None, dgamma
+        if ctx.variant == (0, False):
+            x, group, gamma, A, J = ctx.saved_tensors
+            dx, dgamma = H.ciam_bwd(x, group.contiguous(), gamma, A, J, g.float().contiguous())
+        else:
+            x, group, gamma, A, J, saved = ctx.saved_tensors
+            dx, dgamma = H.ciam_norm_bwd(x, group.contiguous(), gamma, ctx.variant[0], ctx.variant[1], saved, A, J,
+                                         g.float().contiguous())
+        return (dx if dx.dtype == ctx.xtype else dx.to(ctx.xtype)), None, dgamma, None, None

@@ -6,7 +6,8 @@ max-pooled 14x14) is concatenated to the 256-channel ROI feature, pushed through
 mixed across instances by the cross-instance channel attention CIAM, then deconv(16) + 1x1(3) give the second
 mask logits.  Parameter names as in the reference (mask_heads.mask.mask_relation_module.*).  The convolutions run
 on the MFMA implicit GEMM (the 257-channel input is carried as 272 channels, weights zero-padded on the fly);
-CIAM is one launch forward, two backward (csrc/relation.hip: mmt_ciam_fwd / mmt_ciam_bwd) and nothing else: CPU tensors and
+CIAM is one launch forward, two backward (csrc/relation.hip: mmt_ciam_fwd / mmt_ciam_bwd; with RELATION_MASK.NORM 1 / 2 or
+PRE_NORM mmt_ciam_norm_fwd / _bwd, up to three and four) and nothing else: CPU tensors and
 batches beyond the kernel's capacity raise; the formulation with two batched library GEMMs it is tested against lives in
 tests/tensor_formulations.py."""
 import torch
@@ -49,26 +50,36 @@ class RoiAlignMaskFeatureExtractor(nn.Module):
 class CIAM_Module(nn.Module):
     def __init__(self, cfg):
         super().__init__()
-        if cfg.MODEL.RELATION_MASK.NORM in (1, 2) or cfg.MODEL.RELATION_MASK.PRE_NORM:
-            raise NotImplementedError("CIAM NORM / PRE_NORM variants are off in the shipped configuration")
+        # the reference's switches in front of the softmax (mask_relation_module.py:193-198, :214-234), read once: NORM 1 "sum
+        # channel", 2 "L2 norm", any other value none (its else branch); they add no parameter
+        self.norm = _H.ciam_norm_kind(cfg.MODEL.RELATION_MASK.NORM)
+        self.prenorm = bool(cfg.MODEL.RELATION_MASK.PRE_NORM)
         self.gamma = nn.Parameter(torch.zeros(1))
-        self.topk = cfg.MODEL.RELATION_MASK.TOPK
+        self.topk = cfg.MODEL.RELATION_MASK.TOPK     # (computed and never read by the reference)
 
     def forward(self, x, group=None):
         """x (n, C, H, W).  `group` (n,) int: the attention runs inside every group of equal ids separately -- what the
         reference gets by calling the module once per (image, class) slice (mask_relation_module.py:82-92), here as ONE pass
         with the cross-group entries masked out (exp(-inf) = 0 exactly: the same softmax over the same values), so that no
-        group size ever has to reach the host."""
+        group size ever has to reach the host.  With NORM / PRE_NORM the sums the reference takes over its slice run over the
+        group."""
         n, C, Hh, Ww = x.size()
         if group is None:
             group = torch.zeros((n,), dtype=torch.int64, device=x.device)     # one group: the reference's per-slice call
-        if not (x.is_cuda and 0 < n <= _H.CIAM_MAX_N and C <= 16 and 4 * (C * Hh * Ww + (C + 1) * n) <= 65536):
+        if (self.norm, self.prenorm) == (0, False):
+            fits = 0 < n <= _H.CIAM_MAX_N and C <= 16 and 4 * (C * Hh * Ww + (C + 1) * n) <= 65536
+            limit = "4 (C H W + (C + 1) n) <= 65536 bytes of LDS"
+        else:
+            fits = x.is_cuda and _H.ciam_norm_fits(n, C, Hh * Ww)
+            limit = "4 max(C H W + (C + 1) n, (C + 4) n) <= 65536 bytes of LDS (mmt_ciam_norm_lds_bytes) with NORM %d, PRE_NORM %s" \
+                % (self.norm, self.prenorm)
+        if not (x.is_cuda and fits):
             # (the kernel's LDS: the instance's feature + its energy rows)
-            raise RuntimeError("CIAM: GPU tensors, 1..%d instances per batch, <= 16 channels (csrc/relation.hip is the only "
-                               "implementation)" % _H.CIAM_MAX_N)
+            raise RuntimeError("CIAM: GPU tensors, 1..%d instances per batch, <= 16 channels, %s (csrc/relation.hip is the only "
+                               "implementation)" % (_H.CIAM_MAX_N, limit))
         # one forward launch, two backward launches for all groups of the batch (csrc/relation.hip); `group` is sorted by
         # the caller (forward_batch orders the instances by (image, class)): equal ids are contiguous
-        return fused.CIAMFn.apply(x, group, self.gamma)
+        return fused.CIAMFn.apply(x, group, self.gamma, self.norm, self.prenorm)
 
 
 class MaskRelationRefineNet(nn.Module):
