@@ -486,7 +486,7 @@ int mmt_sum_stats(const float* a, const float* b, const float* c, const float* d
                   float* slot /*device, zeroed*/, void* stream);
 /* statistics slot of a tensor whose elements are convex combinations of elements of n source tensors (the pooled features of
  * mmt_roi_align_forward: bilinear taps of the pyramid levels, poolers.py:91-121): out[0] = the largest of the sources' maxima (an
- * upper bound: what a consumer's power-of-two scale needs), sums / counts added.  slots: HOST array of n <= 8 device pointers to
+ * upper bound: what a consumer's power-of-two scale needs; NaN when a source's maximum is NaN), sums / counts added.  slots: HOST array of n <= 8 device pointers to
  * 33-float slots (they travel in the kernel arguments).  Replaces a reduction pass over the 51-205 MB pooled tensor in front of
  * fc6 / the mask head. */
 int mmt_stats_combine(const float* const* slots /*[host]*/, int n, float* out /*device, 33 floats*/, void* stream);
@@ -584,7 +584,11 @@ int mmt_split_planes_f16_rb(const float* x, void* planes, long plane_stride, int
  *   3x3 data gradient behind it (reference: autograd of backbone/fpn.py:57-69 / rpn/rpn.py:39-46).
  * mmt_rb_scales_update: once per training step over the host side's table of producing sites, state[2 i] = scale, state[2 i + 1] =
  *   pending maximum (what y_amax_next / amax_next accumulated): scale <- the power of two that puts 2 x pending into [2^13, 2^14),
- *   pending <- 0; sites without a pending maximum keep their scale. */
+ *   pending <- 0; sites without a pending maximum keep their scale, and so do sites whose pending maximum is inf or NaN.
+ * Every maximum these entry points and the convolutions' epilogues record (mmt_amax*, mmt_sum_stats*, y_amax, y_amax_next, stat[2 d])
+ * is NaN when the tensor holds a NaN (NaN orders above every number in the atomic maximum on the bits): the fp16 split's range guard
+ * then computes with exact fp32 products, which carry the NaN.  The split passes (mmt_split_planes_f16 / _rb, mmt_pack_weight*_f16,
+ * mmt_sum_stats_rb) saturate FINITE values that a stale scale pushes past +-65504 and leave a NaN or inf of the input as it is. */
 /* Round 6: the weight gradients of a BATCH of layers (what a backward pass hands over at a time) as grouped launches -- replaces the
  * per-layer conv2d weight gradients autograd issues behind layers/misc.py:30-43 for backbone/resnet.py:202-274, backbone/fpn.py:43-69,
  * rpn/rpn.py:39-46 and the heads.  Every job is what mmt_conv_wgrad takes (a, dy, rowscale, dw, dbias; a.f16_x_amax / f16_dy_amax and
@@ -624,7 +628,9 @@ int mmt_conv_forward_pg(const mmt_conv_args* a /*[host]*/, const float* s_x /*de
  * the split-bf16 modes.  Plane q (q = 0..2, at planes + q*plane_stride bf16 elements) holds the q-th term of the
  * round-to-nearest bf16 expansion w = w0 + w1 + w2 (exact to 2^-27 |w|), tiled as
  * [K/16][ceil(Cout/32)][32 rows][2 halves][8] -- the LDS image of the kernels, so that their global->LDS DMA reads
- * 1 KiB of consecutive memory per instruction.  mmt_packed_weight_elems = elements per plane (-1 if unsupported).
+ * 1 KiB of consecutive memory per instruction.  The two 8-element halves of a row's 16-k step are SWAPPED in rows 8-15 and 24-31
+ * of every 32-row block: half h of row r holds k = 16 step + 8 (h ^ ((r >> 3) & 1)) .. + 7 (the kernels' LDS reads of a fragment
+ * then fall into different banks).  Rows >= Cout of the last block are zero.  mmt_packed_weight_elems = elements per plane (-1 if unsupported).
  * mmt_pack_weights packs many matrices of one fp32 buffer in a single launch (engine/flat.py: once per SGD / EMA step):
  * descs[] (device) gives per matrix its offset in `base`, its offset inside a plane, Cout, K and its first unit index
  * (unit = one 1 KiB tile = 512 elements); unit_desc[u] (device) = index of the matrix unit u belongs to. */

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void gconv_fwd_kernel(GcArgs p) {
       f32x4 v = acc[m] * sc + sh;
       if (p.relu) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+        for (int e = 0; e < 4; ++e) v[e] = __builtin_elementwise_maximum(v[e], 0.f);   // (keeps NaN, fmaxf would not)
       }
       if (p.mask) {
         const f32x4 mk = *reinterpret_cast<const f32x4*>(p.mask + o);

@@ -71,7 +71,7 @@ __device__ __forceinline__ void conv_amax_commit(const ConvP& p, AmaxAcc a, cons
   const bool stats = p.amax_stats && (lin & 63) == 0;   // mean |y| from a SAMPLE of the blocks: atomics on the two cache
                                                          // lines of a slot serialise at the L2
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) a.amx = fmaxf(a.amx, __shfl_xor(a.amx, o, 64));
+  for (int o = 32; o > 0; o >>= 1) a.amx = max_nan(a.amx, __shfl_xor(a.amx, o, 64));
   if (stats) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { a.asum += __shfl_xor(a.asum, o, 64); a.acnt += __shfl_xor(a.acnt, o, 64); }
@@ -80,10 +80,10 @@ __device__ __forceinline__ void conv_amax_commit(const ConvP& p, AmaxAcc a, cons
   __syncthreads();
   if (t == 0) {
     float m = red[0][0], sm = red[1][0], cn = red[2][0];
-    for (int i = 1; i < nw; i++) { m = fmaxf(m, red[0][i]); sm += red[1][i]; cn += red[2][i]; }
-    const unsigned bits = __builtin_bit_cast(unsigned, m);
-    if (m > 0.f && bits > __hip_atomic_load(p.amax_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.amax_out, bits);
-    if (p.amax_next && m > 0.f && bits > __hip_atomic_load(p.amax_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.amax_next, bits);
+    for (int i = 1; i < nw; i++) { m = max_nan(m, red[0][i]); sm += red[1][i]; cn += red[2][i]; }
+    const unsigned bits = __builtin_bit_cast(unsigned, m);   // (m >= 0 or NaN, whose bits order above every number's)
+    if (bits > __hip_atomic_load(p.amax_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.amax_out, bits);
+    if (p.amax_next && bits > __hip_atomic_load(p.amax_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.amax_next, bits);
     if (stats && cn > 0.f) {
       const int k = (lin >> 6) & 15;
       atomicAdd((float*)p.amax_out + 1 + k, sm);
@@ -182,7 +182,7 @@ __device__ __forceinline__ void conv_epilogue_finish(const ConvP& p, float* lds,
           }
           if (p.relu) {
 #pragma unroll
-            for (int e = 0; e < 4; e++) v[e] = fmaxf(v[e], 0.f);
+            for (int e = 0; e < 4; e++) v[e] = max_nan(v[e], 0.f);
           }
           if (p.mask) {
 #pragma unroll
@@ -194,7 +194,7 @@ __device__ __forceinline__ void conv_epilogue_finish(const ConvP& p, float* lds,
           }
           if (p.amax_out) {
 #pragma unroll
-            for (int e = 0; e < 4; e++) { const float av = e < nv ? fabsf(v[e]) : 0.f; amx = fmaxf(amx, av); asum += av; }
+            for (int e = 0; e < 4; e++) { const float av = e < nv ? fabsf(v[e]) : 0.f; amx = max_nan(amx, av); asum += av; }
             acnt += (float)nv;
           }
           if (p.io & IO_Y) {  // y is a bf16 tensor: round to nearest even, nothing else is written
@@ -219,7 +219,7 @@ __device__ __forceinline__ void conv_epilogue_finish(const ConvP& p, float* lds,
     }
   }
   if (p.amax_out) {
-    if (acc) { acc->amx = fmaxf(acc->amx, amx); acc->asum += asum; acc->acnt += acnt; }
+    if (acc) { acc->amx = max_nan(acc->amx, amx); acc->asum += asum; acc->acnt += acnt; }
     else conv_amax_commit(p, AmaxAcc{amx, asum, acnt}, blockIdx.x);
   }
 }
@@ -1723,11 +1723,11 @@ __global__ __launch_bounds__(256, 2) void conv1x1_rows_kernel(const ConvP p, con
     for (int r = 0; r < 16; r++) {   // same expressions as conv_epilogue
       float v = acc[r] * sc + sh;
       v += has_res ? ur[S][r] : 0.f;
-      v = p.relu ? fmaxf(v, 0.f) : v;
+      v = p.relu ? max_nan(v, 0.f) : v;
       if constexpr (MASK) v = um[S][r] > 0.f ? v * p.mask_scale : 0.f;
       const bool ok = cb != 0x80000000u && mlane + 8 * (r >> 2) + (r & 3) < p.M;
       const float av = ok ? fabsf(v) : 0.f;
-      amx = fmaxf(amx, av);
+      amx = max_nan(amx, av);
       asum += av;
       acnt += ok ? 1.f : 0.f;
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, (int)(ylane + row_off(r) + cb), 0, 0);

@@ -428,7 +428,7 @@ __global__ __launch_bounds__(256) void split_planes_f16_rb_kernel(const float* _
     if (i < total) {
       const int px = i / c4n, c4 = i - px * c4n;
       uint2 o[2];
-      split4h(v[u], s, o);
+      split4h<true>(v[u], s, o);
 #pragma unroll
       for (int q = 0; q < 2; q++) *(uint2*)(tile + (q * 16 + (c4 >> 2)) * CBS + px * 32 + (c4 & 3) * 8) = o[q];
     }
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(256) void split_planes_f16_rb_small_kernel(const fl
   const long row = pix / W;
   const int w = (int)(pix - row * W);
   uint2 o[2];
-  split4h(ldg4(x + i * 4), s, o);
+  split4h<true>(ldg4(x + i * 4), s, o);
   const long dst = ((row * (C >> 4) + (c4 >> 2)) * W + w) * 16 + (c4 & 3) * 4;
 #pragma unroll
   for (int q = 0; q < 2; q++) *(uint2*)(pl + q * plane_stride + dst) = o[q];
@@ -504,19 +504,19 @@ __global__ __launch_bounds__(256) void sum_stats_rb_kernel(const float* __restri
     if (i < total) {
       const int px = i / c4n, c4 = i - px * c4n;
       *(f32x4*)(y + base + (long)px * C + c4 * 4) = v[u];
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(v[u][0]), fabsf(v[u][1])), fmaxf(fabsf(v[u][2]), fabsf(v[u][3]))));
+      m = max_nan(m, max_abs4(v[u]));
       sum += (fabsf(v[u][0]) + fabsf(v[u][1])) + (fabsf(v[u][2]) + fabsf(v[u][3]));
       cnt += 4.f;
       if (pl) {
         uint2 o[2];
-        split4h(v[u], s, o);
+        split4h<true>(v[u], s, o);
 #pragma unroll
         for (int q = 0; q < 2; q++) *(uint2*)(tile + (q * 16 + (c4 >> 2)) * CBS + px * 32 + (c4 & 3) * 8) = o[q];
       }
     }
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { m = fmaxf(m, __shfl_xor(m, o, 64)); sum += __shfl_xor(sum, o, 64); cnt += __shfl_xor(cnt, o, 64); }
+  for (int o = 32; o > 0; o >>= 1) { m = max_nan(m, __shfl_xor(m, o, 64)); sum += __shfl_xor(sum, o, 64); cnt += __shfl_xor(cnt, o, 64); }
   if ((threadIdx.x & 63) == 0) { wred[0][threadIdx.x >> 6] = m; wred[1][threadIdx.x >> 6] = sum; wred[2][threadIdx.x >> 6] = cnt; }
   __syncthreads();
   const int per_cb = npx * 2;
@@ -530,10 +530,10 @@ __global__ __launch_bounds__(256) void sum_stats_rb_kernel(const float* __restri
     }
   }
   if (threadIdx.x == 0) {
-    const float mm = fmaxf(fmaxf(wred[0][0], wred[0][1]), fmaxf(wred[0][2], wred[0][3]));
-    const unsigned bits = __builtin_bit_cast(unsigned, mm);
-    if (mm > 0.f && bits > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, bits);
-    if (next && mm > 0.f && bits > __hip_atomic_load(next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(next, bits);
+    const float mm = max_nan(max_nan(wred[0][0], wred[0][1]), max_nan(wred[0][2], wred[0][3]));
+    const unsigned bits = __builtin_bit_cast(unsigned, mm);   // (mm >= 0 or NaN, whose bits order above every number's)
+    if (bits > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, bits);
+    if (next && bits > __hip_atomic_load(next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(next, bits);
     const int lin = blockIdx.y * gridDim.x + blockIdx.x;
     if ((lin & 15) == 0) {
       const float sm = (wred[1][0] + wred[1][1]) + (wred[1][2] + wred[1][3]), cn = (wred[2][0] + wred[2][1]) + (wred[2][2] + wred[2][3]);
@@ -548,7 +548,8 @@ __global__ __launch_bounds__(256) void sum_stats_rb_kernel(const float* __restri
 
 // the producing sites' scales for the NEXT step (one launch per step): state[i] = {scale, pending maximum (float bits)}; a site that
 // recorded a maximum since the last call gets the power of two that puts 2 x that maximum into [2^13, 2^14) -- one binade of
-// head-room over the largest value any call of the site produced -- and its pending maximum is cleared; sites nobody called keep theirs
+// head-room over the largest value any call of the site produced -- and its pending maximum is cleared; sites nobody called keep theirs,
+// and so does a site whose pending maximum is inf or NaN (no scale fits such a tensor: its consumers' range guard takes the exact path)
 __global__ void rb_scales_update_kernel(float* __restrict__ state, const int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

@@ -30,17 +30,18 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
 __device__ __forceinline__ void block_amax_commit(float m, unsigned* __restrict__ out) {
   __shared__ float wmax[4];
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  for (int o = 32; o > 0; o >>= 1) m = max_nan(m, __shfl_xor(m, o, 64));
   if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-    const unsigned bits = __builtin_bit_cast(unsigned, m);
-    if (m > 0.f && bits > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, bits);
+    m = max_nan(max_nan(wmax[0], wmax[1]), max_nan(wmax[2], wmax[3]));
+    const unsigned bits = __builtin_bit_cast(unsigned, m);   // m >= 0, or NaN (a NaN in the tensor): its bits order above every number's
+    if (bits > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, bits);
   }
 }
 
-// out[0] = max(out[0], max |x[i] * rowscale[(i / inner) % rows]|) as a float (non-negative floats order like their bits)
+// out[0] = max(out[0], max |x[i] * rowscale[(i / inner) % rows]|) as a float (non-negative floats order like their bits, NaN above
+// them all: a tensor that holds a NaN records a NaN maximum)
 template <bool STATS>  // STATS: out is a 33-float slot, sum |x| and count of every 16th block's share added to it (see ConvP.amax_stats)
 __global__ __launch_bounds__(256) void amax_kernel(const float* __restrict__ x, const long n4, const float* __restrict__ rowscale,
                                                    const long inner4, const int rows, unsigned* __restrict__ out) {
@@ -48,7 +49,7 @@ __global__ __launch_bounds__(256) void amax_kernel(const float* __restrict__ x, 
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
     const f32x4 v = ((const f32x4*)x)[i];
     const float rs = rowscale ? fabsf(rowscale[(i / inner4) % rows]) : 1.f;
-    m = fmaxf(m, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))) * rs);
+    m = max_nan(m, max_abs4(v) * rs);
     if (STATS) { sum += ((fabsf(v[0]) + fabsf(v[1])) + (fabsf(v[2]) + fabsf(v[3]))) * rs; cnt += 4.f; }
   }
   block_amax_commit(m, out);
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(256) void sum_stats_kernel(const float* __restrict_
     if (c) v += ((const f32x4*)c)[i];
     if (d) v += ((const f32x4*)d)[i];
     ((f32x4*)y)[i] = v;
-    m = fmaxf(m, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+    m = max_nan(m, max_abs4(v));
     sum += (fabsf(v[0]) + fabsf(v[1])) + (fabsf(v[2]) + fabsf(v[3]));
     cnt += 4.f;
   }
@@ -103,12 +104,11 @@ __global__ __launch_bounds__(256) void split_planes_f16_kernel(const float* __re
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
     const f32x4 v0 = ((const f32x4*)x)[2 * i], v1 = ((const f32x4*)x)[2 * i + 1];
     if (amax_next) {
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(v0[0]), fabsf(v0[1])), fmaxf(fabsf(v0[2]), fabsf(v0[3]))));
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(v1[0]), fabsf(v1[1])), fmaxf(fabsf(v1[2]), fabsf(v1[3]))));
+      m = max_nan(m, max_nan(max_abs4(v0), max_abs4(v1)));
     }
     uint2 o0[2], o1[2];
-    split4h(v0, s, o0);
-    split4h(v1, s, o1);
+    split4h<true>(v0, s, o0);
+    split4h<true>(v1, s, o1);
 #pragma unroll
     for (int q = 0; q < 2; q++)
       ((uint4*)(pl + q * plane_stride))[i] = uint4{o0[q].x, o0[q].y, o1[q].x, o1[q].y};
@@ -166,8 +166,8 @@ __global__ __launch_bounds__(256) void pack_one_f16_kernel(const float* __restri
     v1 = ldg4(src + 4);
   }
   uint2 o0[2], o1[2];
-  split4h(v0, s, o0);
-  split4h(v1, s, o1);
+  split4h<true>(v0, s, o0);
+  split4h<true>(v1, s, o1);
 #pragma unroll
   for (int q = 0; q < 2; q++)
     *(uint4*)(dst + q * plane_stride + (long)unit * 512 + lane * 8) = uint4{o0[q].x, o0[q].y, o1[q].x, o1[q].y};
@@ -225,8 +225,8 @@ __global__ __launch_bounds__(256) void pack_flip_f16_kernel(const float* __restr
     v[j] = ci < Cin ? w[((long)co * KH * KW + tap) * Cin + ci] * (scale ? scale[co] : 1.f) : 0.f;
   }
   uint2 o0[2], o1[2];
-  split4h(f32x4{v[0], v[1], v[2], v[3]}, s, o0);
-  split4h(f32x4{v[4], v[5], v[6], v[7]}, s, o1);
+  split4h<true>(f32x4{v[0], v[1], v[2], v[3]}, s, o0);
+  split4h<true>(f32x4{v[4], v[5], v[6], v[7]}, s, o1);
 #pragma unroll
   for (int q = 0; q < 2; q++)
     *(uint4*)(dst + q * plane_stride + (long)unit * 512 + lane * 8) = uint4{o0[q].x, o0[q].y, o1[q].x, o1[q].y};
@@ -300,8 +300,8 @@ __device__ __forceinline__ void load_flip_unit(const float* __restrict__ w, cons
 __device__ __forceinline__ void store_unit_f16(const f32x4 v0, const f32x4 v1, const float s, unsigned short* __restrict__ dst,
                                                long plane_stride, int unit, int lane) {
   uint2 o0[2], o1[2];
-  split4h(v0, s, o0);
-  split4h(v1, s, o1);
+  split4h<true>(v0, s, o0);
+  split4h<true>(v1, s, o1);
 #pragma unroll
   for (int q = 0; q < 2; q++)
     *(uint4*)(dst + q * plane_stride + (long)unit * 512 + lane * 8) = uint4{o0[q].x, o0[q].y, o1[q].x, o1[q].y};
@@ -311,13 +311,12 @@ __device__ __forceinline__ void store_unit_f16(const f32x4 v0, const f32x4 v1, c
 // next matrix and at its end -- one atomic per 1 KiB unit made this launch 5x slower than the packing launch itself
 __device__ __forceinline__ void wave_amax_commit(float m, unsigned* __restrict__ out) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  for (int o = 32; o > 0; o >>= 1) m = max_nan(m, __shfl_xor(m, o, 64));
   const unsigned bits = __builtin_bit_cast(unsigned, m);
-  if ((threadIdx.x & 63) == 0 && m > 0.f && bits > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, bits);
+  if ((threadIdx.x & 63) == 0 && bits > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, bits);
 }
 __device__ __forceinline__ float amax8(const f32x4 v0, const f32x4 v1) {
-  return fmaxf(fmaxf(fmaxf(fabsf(v0[0]), fabsf(v0[1])), fmaxf(fabsf(v0[2]), fabsf(v0[3]))),
-               fmaxf(fmaxf(fabsf(v1[0]), fabsf(v1[1])), fmaxf(fabsf(v1[2]), fabsf(v1[3]))));
+  return max_nan(max_abs4(v0), max_abs4(v1));
 }
 constexpr int PACK_RUN = 32;   // units per wave in the reduction launches
 
@@ -340,7 +339,7 @@ __global__ __launch_bounds__(256) void pack_many_amax_kernel(const float* __rest
     const long e = (long)(unit - d.unit0) * 512 + lane * 8, numel = (long)d.Cout * d.K;
     if (e < numel) {   // (K % 16 == 0: the 8 elements of a lane lie inside the matrix)
       const float* src = base + d.src_off + e;
-      m = fmaxf(m, amax8(ldg4(src), ldg4(src + 4)));
+      m = max_nan(m, amax8(ldg4(src), ldg4(src + 4)));
     }
   }
   if (cur >= 0) wave_amax_commit(m, (unsigned*)stat + 2 * cur);
@@ -381,10 +380,10 @@ __global__ __launch_bounds__(256) void pack_flip_many_amax_kernel(const FlipDesc
       if ((rowlen & 7) == 0) {   // the 8 elements of a lane share their output channel
         const float sc = d.scale ? d.scale[e / rowlen] : 1.f;
         const f32x4 a = ldg4(d.w + e), b = ldg4(d.w + e + 4);
-        m = fmaxf(m, amax8(f32x4{a[0] * sc, a[1] * sc, a[2] * sc, a[3] * sc}, f32x4{b[0] * sc, b[1] * sc, b[2] * sc, b[3] * sc}));
+        m = max_nan(m, amax8(f32x4{a[0] * sc, a[1] * sc, a[2] * sc, a[3] * sc}, f32x4{b[0] * sc, b[1] * sc, b[2] * sc, b[3] * sc}));
       } else {
         for (int j = 0; j < 8 && e + j < numel; j++)
-          m = fmaxf(m, fabsf(d.w[e + j] * (d.scale ? d.scale[(e + j) / rowlen] : 1.f)));
+          m = max_nan(m, fabsf(d.w[e + j] * (d.scale ? d.scale[(e + j) / rowlen] : 1.f)));
       }
     }
   }
@@ -572,7 +571,8 @@ extern "C" int mmt_amax_stats(const float* x, long n, float* slot, void* stream)
 
 // out <- the statistics of a tensor whose every element is a CONVEX combination of elements of the tensors behind `slots`
 // (ROIAlign: bilinear taps of the pyramid levels, averaged): max = the largest of the maxima -- an upper bound, which is all the
-// consumer's power-of-two scale needs -- sums and counts added (the mean of such a tensor is about that of its sources)
+// consumer's power-of-two scale needs -- sums and counts added (the mean of such a tensor is about that of its sources).  A source
+// whose maximum is NaN gives a NaN maximum (the consumer's range guard then takes the exact path).
 struct StatSlots { const float* s[8]; };
 __global__ void stats_combine_kernel(const StatSlots slots, const int n, float* __restrict__ out) {
   const int i = threadIdx.x;
@@ -580,7 +580,7 @@ __global__ void stats_combine_kernel(const StatSlots slots, const int n, float* 
   float v = 0.f;
 #pragma unroll
   for (int k = 0; k < 8; k++)
-    if (k < n) v = i == 0 ? fmaxf(v, slots.s[k][0]) : v + slots.s[k][i];
+    if (k < n) v = i == 0 ? max_nan(v, slots.s[k][0]) : v + slots.s[k][i];
   out[i] = v;
 }
 

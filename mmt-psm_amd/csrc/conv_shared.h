@@ -76,7 +76,10 @@ using namespace mmtconv;
 // the producer recorded max / sampled mean of x in its statistics slot.  Every block of an fp16-split kernel reads the slot
 // first and, for such a tensor, computes its tile with plain fp32 FMAs from the fp32 operands instead (conv_slow_tile: exact
 // products, ~100 x slower, a handful of launches) -- until the host has seen the same statistics and moved the site to the
-// 3-term bf16 split (_hip._site_ok), which is fast and range-free.  NaN / inf maxima take the slow path too (they propagate).
+// 3-term bf16 split (_hip._site_ok), which is fast and range-free.  NaN / inf maxima take the slow path too, and the fp32 FMAs carry
+// the NaN or inf to the outputs that depend on it.  That rests on the maxima BEING NaN when the tensor holds one: every recorded
+// max |x| is accumulated with max_nan (below), never fmaxf, which drops a NaN operand; the clamps of the split passes let
+// non-finite values through (split4h<true>); a weight has no guard, its planes carry the NaN / inf into the matrix products.
 // Two halves, so that the slot's scalar loads are ISSUED at the top of a kernel and WAITED FOR behind its prologue copies: read at
 // the point of the branch they cost ~1 us of exposed latency per launch (+0.5 ms of conv time per step, measured; the slot was
 // last written by L2 atomics of several XCDs and misses this XCD's L2).  Nine values: the maximum and the first four of the
@@ -90,8 +93,8 @@ __device__ __forceinline__ F16Guard f16_guard_load(const float* __restrict__ slo
 }
 __device__ __forceinline__ bool f16_guard_bad(const F16Guard& g) {
   const float tot = (g.s0 + g.s1) + (g.s2 + g.s3), cnt = (g.c0 + g.c1) + (g.c2 + g.c3);
+  if (!(g.amax == g.amax) || g.amax > 3.0e38f) return true;   // (before the sample is looked at: its sum is NaN with the maximum)
   if (!(tot > 0.f)) return false;                       // nothing sampled (or an all-zero sample): no statement
-  if (!(g.amax == g.amax) || g.amax > 3.0e38f) return true;
   // (Tried in round 6 and withdrawn: the mean of the BULK, the maximum taken out of the sample's sum -- it also fires on SPARSE
   // tensors, whose few non-zero values fp16 holds exactly: the RPN's gradient is non-zero at 512 of 1.3 M anchors, and every tenth
   // step took the exact path somewhere: p90 of the step 32.5 -> 42 ms.  A lone outlier INSIDE a small sample therefore stays
@@ -118,6 +121,11 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
+
+// IEEE 754-2019 `maximum`: NaN when either operand is (fmaxf returns the other one) -- one v_maximum3_f32.  The statistics' maxima
+// and the epilogues' ReLU are built on it: a NaN in a tensor must reach the recorded max |x|, and max(NaN, 0) is NaN.
+__device__ __forceinline__ float max_nan(const float a, const float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float max_abs4(const f32x4 v) { return max_nan(max_nan(fabsf(v[0]), fabsf(v[1])), max_nan(fabsf(v[2]), fabsf(v[3]))); }
 
 __device__ __forceinline__ unsigned pk_bf16(float a, float b) {
   const f32x2 v = {a, b};
@@ -155,10 +163,16 @@ __device__ __forceinline__ f32x4 ldg4(const float* p) { return *(const f32x4*)p;
 // The caller scales each tensor by a power of two so that its largest magnitude sits near 2^14: h is then a normal fp16
 // number down to 2^-28 of the tensor's maximum and l down to 2^-17 of it (below that l turns subnormal: absolute error
 // <= 2^-25 in scaled units, i.e. <= 2^-39 of the maximum).
+// KEEP (the split PASSES, which are HBM-bound): a NaN or inf of x stays one (h = x, l = NaN) instead of being clamped to a finite
+// number.  The in-register splits of the convolution kernels do without: the range guard sends such a tensor to the exact path.
+template <bool KEEP = false>
 __device__ __forceinline__ void split4h(const f32x4 v, const float s, uint2 (&o)[2]) {
   float r[4] = {v[0] * s, v[1] * s, v[2] * s, v[3] * s};
 #pragma unroll
-  for (int e = 0; e < 4; e++) r[e] = fminf(fmaxf(r[e], -65504.f), 65504.f);   // a scale from an older tensor may be too large: saturate
+  for (int e = 0; e < 4; e++) {
+    const float c = fminf(fmaxf(r[e], -65504.f), 65504.f);   // a scale from an older tensor may be too large: saturate
+    r[e] = KEEP && !(fabsf(v[e]) < __builtin_inff()) ? v[e] : c;
+  }
   _Float16 h[4], l[4];
 #pragma unroll
   for (int e = 0; e < 4; e++) { h[e] = (_Float16)r[e]; l[e] = (_Float16)(r[e] - (float)h[e]); }
@@ -275,7 +289,7 @@ __device__ __forceinline__ void conv_slow_tile(const int m_first, const int run,
       const float* rp = pk->res + (((long)img * (pk->Ho * 2) + 2 * ho) * w2 + 2 * wo) * pk->Cout + n;
       v += (rp[0] + rp[pk->Cout]) + (rp[(long)w2 * pk->Cout] + rp[(long)w2 * pk->Cout + pk->Cout]);
     }
-    if (pk->relu) v = fmaxf(v, 0.f);
+    if (pk->relu) v = max_nan(v, 0.f);
     if (pk->mask) v = pk->mask[oidx] > 0.f ? v * pk->mask_scale : 0.f;
     if (pk->mul) v *= pk->mul[(long)m * pk->Cout + n];
     pk->y[oidx] = v;
@@ -287,11 +301,12 @@ __device__ __forceinline__ void conv_slow_tile(const int m_first, const int run,
       pk->yrb[pk->yrb_stride + e] = (unsigned short)(hl >> 16);
     }
     const float av = fabsf(v);
-    amx = fmaxf(amx, av); asum += av; acnt += 1.f;
+    amx = max_nan(amx, av); asum += av; acnt += 1.f;
   }
   if (!raw && pk->amax_out) {
-    if (amx > 0.f) atomicMax(pk->amax_out, __builtin_bit_cast(unsigned, amx));
-    if (amx > 0.f && pk->amax_next) atomicMax(pk->amax_next, __builtin_bit_cast(unsigned, amx));
+    const unsigned bits = __builtin_bit_cast(unsigned, amx);   // (amx >= 0 or NaN: non-zero bits, and NaN's order above every number's)
+    if (bits) atomicMax(pk->amax_out, bits);
+    if (bits && pk->amax_next) atomicMax(pk->amax_next, bits);
     if (pk->amax_stats && (lin & 63) == 0 && acnt > 0.f) {
       const int k = (lin >> 6) & 15;
       atomicAdd((float*)pk->amax_out + 1 + k, asum);
@@ -375,11 +390,11 @@ __device__ __forceinline__ void conv_epilogue_direct(const ConvP& p, const f32x1
     for (int r = 0; r < 16; r++) {
       float v = acc[a][b][r] * sc[b] + sh[b];
       if (has_res) v += ur[r];
-      if (p.relu) v = fmaxf(v, 0.f);
+      if (p.relu) v = max_nan(v, 0.f);
       if (has_mask) v = um[r] > 0.f ? v * p.mask_scale : 0.f;
       const bool ok = cok[b] && a * 32 + 8 * (r >> 2) + (r & 3) < rows_left;
       const float av = ok ? fabsf(v) : 0.f;
-      amx = fmaxf(amx, av);
+      amx = max_nan(amx, av);
       asum += av;
       acnt += ok ? 1.f : 0.f;
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, (int)(ok ? off(a, b, r) : OOB), 0, 0);
@@ -408,7 +423,7 @@ __device__ __forceinline__ void conv_epilogue_direct(const ConvP& p, const f32x1
     const int nw = (int)(blockDim.x >> 6);
     const bool stats = p.amax_stats && (lin & 63) == 0;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amx = fmaxf(amx, __shfl_xor(amx, o, 64));
+    for (int o = 32; o > 0; o >>= 1) amx = max_nan(amx, __shfl_xor(amx, o, 64));
     if (stats) {
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) { asum += __shfl_xor(asum, o, 64); acnt += __shfl_xor(acnt, o, 64); }
@@ -417,10 +432,10 @@ __device__ __forceinline__ void conv_epilogue_direct(const ConvP& p, const f32x1
     __syncthreads();
     if (tid == 0) {
       float m = red[0], sm = red[16], cn = red[32];
-      for (int i = 1; i < nw; i++) { m = fmaxf(m, red[i]); sm += red[16 + i]; cn += red[32 + i]; }
-      const unsigned bits = __builtin_bit_cast(unsigned, m);
-      if (m > 0.f && bits > __hip_atomic_load(p.amax_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.amax_out, bits);
-      if (p.amax_next && m > 0.f && bits > __hip_atomic_load(p.amax_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.amax_next, bits);
+      for (int i = 1; i < nw; i++) { m = max_nan(m, red[i]); sm += red[16 + i]; cn += red[32 + i]; }
+      const unsigned bits = __builtin_bit_cast(unsigned, m);   // (m >= 0 or NaN, whose bits order above every number's)
+      if (bits > __hip_atomic_load(p.amax_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.amax_out, bits);
+      if (p.amax_next && bits > __hip_atomic_load(p.amax_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.amax_next, bits);
       if (stats && cn > 0.f) {
         const int k = (lin >> 6) & 15;
         atomicAdd((float*)p.amax_out + 1 + k, sm);

@@ -348,9 +348,9 @@ __device__ __forceinline__ void c64_tail_exact(const ConvP& p, const C64Tail& t,
       const long o = ((long)(img * p.Ho + oy) * p.Wo + ox) * 256 + c;
       float v = acc * sc + sh;
       if (t.res) v += t.res[o];
-      v = fmaxf(v, 0.f);
+      v = max_nan(v, 0.f);
       t.out[o] = v;
-      amx = fmaxf(amx, v); asum += v; acnt += 1.f;
+      amx = max_nan(amx, v); asum += v; acnt += 1.f;
     }
   }
 }
@@ -379,8 +379,8 @@ __device__ __forceinline__ float c64_o2_exact(const ConvP& p, float* lds, const 
         }
       }
       v = acc * sc + sh;
-      if (p.relu) v = fmaxf(v, 0.f);
-      amx = fmaxf(amx, fabsf(v));
+      if (p.relu) v = max_nan(v, 0.f);
+      amx = max_nan(amx, fabsf(v));
     }
     o2[i * 64 + lane] = v;
   }
@@ -392,7 +392,7 @@ __device__ __forceinline__ void c64_commit(unsigned* const slot, const bool stat
                                            const int wave, const int lane, const int tid, unsigned* const next = nullptr) {
   const bool stats = stats_on && (blockIdx.x & 63) == 0;
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) amx = fmaxf(amx, __shfl_xor(amx, o, 64));
+  for (int o = 32; o > 0; o >>= 1) amx = max_nan(amx, __shfl_xor(amx, o, 64));
   if (stats) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { asum += __shfl_xor(asum, o, 64); acnt += __shfl_xor(acnt, o, 64); }
@@ -401,10 +401,10 @@ __device__ __forceinline__ void c64_commit(unsigned* const slot, const bool stat
   __syncthreads();
   if (tid == 0) {
     float m = red[0], sm_ = red[16], cn = red[32];
-    for (int i = 1; i < 4; i++) { m = fmaxf(m, red[i]); sm_ += red[16 + i]; cn += red[32 + i]; }
+    for (int i = 1; i < 4; i++) { m = max_nan(m, red[i]); sm_ += red[16 + i]; cn += red[32 + i]; }
     const unsigned bits = __builtin_bit_cast(unsigned, m);
-    if (m > 0.f && bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
-    if (next && m > 0.f && bits > __hip_atomic_load(next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(next, bits);
+    if (bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
+    if (next && bits > __hip_atomic_load(next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(next, bits);
     if (stats && cn > 0.f) {
       const int k = (blockIdx.x >> 6) & 15;
       atomicAdd((float*)slot + 1 + k, sm_);
@@ -427,9 +427,9 @@ __device__ __forceinline__ void c64_next_exact(const ConvP& p, const C64Tail& t,
     const float* const xr = t.out + m * 256;
     float acc = 0.f;
     for (int k = 0; k < 256; k++) acc = fmaf(__hip_atomic_load(xr + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), wr[k], acc);   // (past this CU's L1)
-    const float v = fmaxf(acc * sc + sh, 0.f);
+    const float v = max_nan(acc * sc + sh, 0.f);
     t.o1n[m * 64 + lane] = v;
-    amx = fmaxf(amx, v); asum += v; acnt += 1.f;
+    amx = max_nan(amx, v); asum += v; acnt += 1.f;
   }
 }
 
@@ -451,8 +451,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvP p, cons
     if constexpr (FUSE) {       // both convolutions exact, o2 through LDS
       float m = c64_o2_exact(p, lds, img, oy0, ox0, wave, lane);
 #pragma unroll
-      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-      if (t.o2_amax_next && lane == 0 && m > 0.f) atomicMax(t.o2_amax_next, __builtin_bit_cast(unsigned, m));
+      for (int o = 32; o > 0; o >>= 1) m = max_nan(m, __shfl_xor(m, o, 64));
+      if (t.o2_amax_next && lane == 0 && __builtin_bit_cast(unsigned, m) != 0u) atomicMax(t.o2_amax_next, __builtin_bit_cast(unsigned, m));
       __syncthreads();
       float amx = 0.f, asum = 0.f, acnt = 0.f;
       c64_tail_exact(p, t, lds, img, oy0, ox0, wave, lane, amx, asum, acnt);
@@ -558,10 +558,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvP p, cons
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         float v = acc[b][r] * sc + sh;
-        if (p.relu) v = fmaxf(v, 0.f);
+        if (p.relu) v = max_nan(v, 0.f);
         o2v[b][r] = v;
         const float av = po[r] != 0x80000000u ? fabsf(v) : 0.f;
-        m2 = fmaxf(m2, av);
+        m2 = max_nan(m2, av);
         s2 += av;
         c2 += av > 0.f ? 1.f : 0.f;
       }
@@ -576,7 +576,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvP p, cons
       }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-      m2 = fmaxf(m2, __shfl_xor(m2, o, 64));
+      m2 = max_nan(m2, __shfl_xor(m2, o, 64));
       s2 += __shfl_xor(s2, o, 64);
       c2 += __shfl_xor(c2, o, 64);
     }
@@ -608,10 +608,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvP p, cons
     asm volatile("" ::: "memory");
     copy_w3(0);   // into the buffer of tap 7: everybody left it before the barrier of tap 8
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the patch and tap 8's planes are dead from here on
-    const float tmax = fmaxf(fmaxf(red0[0], red0[1]), fmaxf(red0[2], red0[3]));
+    const float tmax = max_nan(max_nan(red0[0], red0[1]), max_nan(red0[2], red0[3]));
     const float ttot = (red0[4] + red0[5]) + (red0[6] + red0[7]), tcnt = (red0[8] + red0[9]) + (red0[10] + red0[11]);
     const float s_o2 = t.s_o2_amax ? f16_scale_of(*t.s_o2) : *t.s_o2;
-    if (tid == 0 && t.o2_amax_next && tmax > 0.f &&
+    if (tid == 0 && t.o2_amax_next &&
         __builtin_bit_cast(unsigned, tmax) > __hip_atomic_load(t.o2_amax_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
       atomicMax(t.o2_amax_next, __builtin_bit_cast(unsigned, tmax));
     // the tile's own range test at the scale it was given (f16_guard_bad_lag's, on the tile's non-zero values): uniform over the block
@@ -723,10 +723,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvP p, cons
           for (int r = 0; r < 16; r++) {   // same expressions as conv1x1_rows_kernel
             float v = a3[b][r] * sc + sh;
             v += ur[US][b][r];
-            v = fmaxf(v, 0.f);
+            v = max_nan(v, 0.f);
             const bool ok = po[r] != 0x80000000u;
             const float av = ok ? fabsf(v) : 0.f;
-            amx = fmaxf(amx, av);
+            amx = max_nan(amx, av);
             asum += av;
             acnt += ok ? 1.f : 0.f;
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rout, (int)po[r], (pn * 64 + b * 32) * 4, 0);
@@ -774,7 +774,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvP p, cons
         float wm = amx, ws = asum, wc = cnz;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-          wm = fmaxf(wm, __shfl_xor(wm, o, 64));
+          wm = max_nan(wm, __shfl_xor(wm, o, 64));
           ws += __shfl_xor(ws, o, 64);
           wc += __shfl_xor(wc, o, 64);
         }
@@ -792,10 +792,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvP p, cons
 #pragma unroll
             for (int r = 0; r < 16; r++) {
               float v = acc1[b][r] * sc + sh;
-              v = fmaxf(v, 0.f);
+              v = max_nan(v, 0.f);
               const bool ok = po[r] != 0x80000000u;
               const float av = ok ? fabsf(v) : 0.f;
-              nmx = fmaxf(nmx, av);
+              nmx = max_nan(nmx, av);
               nsum += av;
               ncnt += ok ? 1.f : 0.f;
               const unsigned o = ok ? ((po[r] - (unsigned)col_l * 4u) >> 2) + (unsigned)col_l * 4u : 0x80000000u;
@@ -829,10 +829,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvP p, cons
       const int i = 8 * (r >> 2) + (r & 3) + 4 * rq;
       const int oy = oy0 + 2 * wave + (i >> 4), ox = ox0 + (i & 15);
       float v = acc[b][r] * sc + sh;
-      if (p.relu) v = fmaxf(v, 0.f);
+      if (p.relu) v = max_nan(v, 0.f);
       const bool ok = oy < p.Ho && ox < p.Wo;
       const float av = ok ? fabsf(v) : 0.f;
-      amx = fmaxf(amx, av);
+      amx = max_nan(amx, av);
       asum += av;
       acnt += ok ? 1.f : 0.f;
       const unsigned off = ok ? (unsigned)(((img * p.Ho + oy) * p.Wo + ox) * 64 + b * 32 + col_l) * 4u : 0x80000000u;
@@ -844,7 +844,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvP p, cons
     float* const red = lds;
     const bool stats = p.amax_stats && (blockIdx.x & 63) == 0;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amx = fmaxf(amx, __shfl_xor(amx, o, 64));
+    for (int o = 32; o > 0; o >>= 1) amx = max_nan(amx, __shfl_xor(amx, o, 64));
     if (stats) {
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) { asum += __shfl_xor(asum, o, 64); acnt += __shfl_xor(acnt, o, 64); }
@@ -853,11 +853,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvP p, cons
     __syncthreads();
     if (tid == 0) {
       float m = red[0], sm_ = red[16], cn = red[32];
-      for (int i = 1; i < 4; i++) { m = fmaxf(m, red[i]); sm_ += red[16 + i]; cn += red[32 + i]; }
+      for (int i = 1; i < 4; i++) { m = max_nan(m, red[i]); sm_ += red[16 + i]; cn += red[32 + i]; }
       const unsigned bits = __builtin_bit_cast(unsigned, m);
-      if (m > 0.f && bits > __hip_atomic_load(p.amax_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.amax_out, bits);
+      if (bits > __hip_atomic_load(p.amax_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.amax_out, bits);
       // (the producing site's pending maximum: what the fused launch's scale of o2 is folded from while the two launches still run)
-      if (p.amax_next && m > 0.f && bits > __hip_atomic_load(p.amax_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.amax_next, bits);
+      if (p.amax_next && bits > __hip_atomic_load(p.amax_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p.amax_next, bits);
       if (stats && cn > 0.f) {
         const int k = (blockIdx.x >> 6) & 15;
         atomicAdd((float*)p.amax_out + 1 + k, sm_);

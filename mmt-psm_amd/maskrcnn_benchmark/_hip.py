@@ -5,6 +5,7 @@ an op is not a CUDA/HIP tensor, the call raises.  PyTorch is used for device mem
 autograd bookkeeping only; tensors cross the boundary as raw device pointers.
 """
 import ctypes
+import gc as _gc
 import weakref
 import os
 import threading as _threading
@@ -1009,6 +1010,30 @@ class LaunchPlan(object):
 
 
 _POOL_GRAVE = []   # MemPool objects of dead plans, destroyed by _drain_pools
+_POOL_CTX = [0, False]   # threads inside torch.cuda.use_mem_pool right now, and whether the cyclic collector is to be switched on again
+
+
+class _no_gc_in_pool(object):
+    """around torch.cuda.use_mem_pool: the cyclic collector stays off while ANY thread records a plan.  The graveyard above covers a
+    dead plan's MemPool and the collector of the recording thread; the teacher's thread records its plans while the step's thread
+    allocates, and a collection THERE -- the launch plans, streams and pooled tensors of a trainer that died -- aborted the process
+    the same way ("Fatal Python error: Aborted", the step's thread "Garbage-collecting", the teacher's inside this context;
+    tests/test_deterministic_backbones_gpu.py, two trainers in one process).  A recording is one backbone pass per plan: the
+    collector misses a few milliseconds; reference counting frees as ever."""
+
+    def __enter__(self):
+        with _LP_LOCK:
+            if _POOL_CTX[0] == 0:
+                _POOL_CTX[1] = _gc.isenabled()
+                _gc.disable()
+            _POOL_CTX[0] += 1
+
+    def __exit__(self, *exc):
+        with _LP_LOCK:
+            _POOL_CTX[0] -= 1
+            if _POOL_CTX[0] == 0 and _POOL_CTX[1]:
+                _gc.enable()
+        return False
 
 
 def _drain_pools():
@@ -1039,7 +1064,9 @@ def planned(tag, fn, x):
     key = (tag, tuple(x.shape), x.dtype, _stream(), _PLAN_EPOCH[0], PLANES_EPOCH, LAYOUT_EPOCH[0], F16X2, _PREC, _BF16_STORAGE, _RB_EPOCH[0], _DET,
            lib().mmt_conv_switches())
     if getattr(_TLS, "rec", None) is None and _POOL_GRAVE:
-        _drain_pools()
+        with _LP_LOCK:
+            if _POOL_CTX[0] == 0:   # (no thread inside a pool context, and none enters one while the pools go: it takes this lock)
+                _drain_pools()
     with _LP_LOCK:
         plan = _LAUNCH_PLANS.pop(key, None)
         if plan is None:
@@ -1056,7 +1083,7 @@ def planned(tag, fn, x):
     if plan.seen == 2:
         _TLS.rec = plan
         try:
-            with torch.cuda.use_mem_pool(plan.pool):
+            with _no_gc_in_pool(), torch.cuda.use_mem_pool(plan.pool):
                 plan.result = fn(x)
         except BaseException:
             with _LP_LOCK:
