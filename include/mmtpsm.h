@@ -449,9 +449,46 @@ typedef struct {
   int switches;            /* mmt_conv_switches() as read for this answer */
 } mmt_conv_route_t;   /* (the function below carries the plain name) */
 int mmt_conv_route(const mmt_conv_args* a /*[host]*/, int entry, int assume, mmt_conv_route_t* out /*[host]*/);
-/* the six forward switches of the environment, read per call (A/B timing, parity tests): bit set = on (anything but "0") */
-enum { MMT_SW_SPLITK = 1, MMT_SW_STRIP = 2, MMT_SW_ROWS = 4, MMT_SW_PG = 8, MMT_SW_C64 = 16, MMT_SW_DIRECT_EPI = 32 };
+/* the switches of the environment, read per call (A/B timing, parity tests): bit set = on (anything but "0").  Bits 0-5: the six
+ * forward switches; bits 6, 7: the weight gradient's MMT_WGRAD_PLANES and MMT_WGRAD_GROUP (mmt_conv_wgrad_route) */
+enum { MMT_SW_SPLITK = 1, MMT_SW_STRIP = 2, MMT_SW_ROWS = 4, MMT_SW_PG = 8, MMT_SW_C64 = 16, MMT_SW_DIRECT_EPI = 32,
+       MMT_SW_WGRAD_PLANES = 64, MMT_SW_WGRAD_GROUP = 128 };
 int mmt_conv_switches(void);
+/* THE ROUTE of a weight-gradient call: which kernel mmt_conv_wgrad / mmt_conv_wgrad_planes / mmt_conv_wgrad_group run it on, with how
+ * many pixel ranges and how much workspace.  One host function decides it (csrc/conv_route.hip: wgrad_route); the three launching
+ * entry points switch on its answer, and this query returns the same answer without launching.
+ *   have   what the caller holds beyond the block: MMT_WG_HAVE_MAXIMA both operands' recorded maxima (the two-term fp16 split of mode
+ *          3; implied when a->f16_x_amax and a->f16_dy_amax are set), MMT_WG_HAVE_PLANES both operands' row-blocked fp16 planes.
+ * a->x may be NULL (a shape question).  The answer holds for the arithmetic mode and the environment switches as they stand at the
+ * call.  Returns 0, or the code the launch would return for a malformed block. */
+enum { MMT_WG_HAVE_MAXIMA = 1, MMT_WG_HAVE_PLANES = 2 };
+enum {
+  MMT_WGRAD_NONE = 0,       /* no kernel takes the call (the launch returns MMT_EINVAL), or there is nothing to launch (M or Cout 0) */
+  MMT_WGRAD_FP32_FAST = 1,  /* conv_wgrad_kernel<true>: fp32-input MFMA, Cout % 4 == 0 and Ho, Wo >= 8 */
+  MMT_WGRAD_FP32_SLOW = 2,  /* conv_wgrad_kernel<false> */
+  MMT_WGRAD_SPLIT = 3,      /* conv_wgrad_split_kernel: `terms` bf16 terms split in registers, 64-bit addressing */
+  MMT_WGRAD_PIPE = 4,       /* conv_wgrad_pipe_kernel: the same arithmetic, software-pipelined buffer loads (operands < 2^31 bytes) */
+  MMT_WGRAD_PIPE_F16 = 5,   /* conv_wgrad_pipe_kernel, two-term fp16 split (mmt_conv_wgrad with the maxima in the block) */
+  MMT_WGRAD_PLANES_1 = 6,   /* wgrad_pl_kernel<1>: plane-fed, one tap per block (mmt_conv_wgrad_planes) */
+  MMT_WGRAD_PLANES_3 = 7    /* wgrad_pl_kernel<3>: plane-fed, the three kw taps of a 3x3 per block */
+};
+typedef struct {
+  int family;           /* MMT_WGRAD_* */
+  int terms;            /* operand terms: 1-3 bf16 terms (the arithmetic mode), 2 on the fp16 split, 0 on fp32 */
+  int decode;           /* pixel-decode form of the register-splitting kernels: 0 divisions (Ho or Wo < 8), 1 carry-select, 2 ... with Wo % 4 == 0 */
+  int vec4;             /* Cout % 4 == 0: 4-channel loads of dy */
+  int bf;               /* operands stored as bf16: bit 0 x, bit 1 dy (mode 1) */
+  int splits;           /* pixel ranges across blocks of a launch of its own (> 1: slabs in the workspace, summed by a reduce launch) */
+  int mps;              /* pixels per range (a multiple of 32); 0 on the plane-fed kernels, which cut 32-pixel super-steps */
+  long ws_floats;       /* workspace of that launch: splits * Cout * KH * KW * Cin floats, 0 when splits == 1 */
+  int lds_bytes;        /* dynamic LDS of the kernel */
+  int dbias_in_kernel;  /* dbias is summed by the kernel's epilogue; 0: by a colsum launch behind it */
+  int group_kind;       /* mmt_conv_wgrad_group: 0 a launch of its own, 1 the plane-fed group, 2 + decode a register-splitting group
+                         * (before the batch's own rules: a shared dw or dbias, a kind with one member) */
+  int group_splits, group_mps;   /* pixel ranges inside a group: a quarter of `splits`, rounded up, within the kernel's limits */
+  int switches;         /* mmt_conv_switches() as read for this answer */
+} mmt_conv_wgrad_route_t;
+int mmt_conv_wgrad_route(const mmt_conv_args* a /*[host]*/, int have, mmt_conv_wgrad_route_t* out /*[host]*/);
 /* arithmetic of the convolution GEMMs -- forward, data gradient and weight gradient (process-wide; initial value from
  * the environment variable MMT_CONV_PRECISION, default 3):
  *   3  fp32 operands split on the fly into three bf16 terms x = x0 + x1 + x2 (round-to-nearest at each level, exact to
@@ -549,14 +586,14 @@ int mmt_c64_conv3_fused(const float* x, int N, int H, int W, const float* w2, co
  * conv2d weight gradient behind layers/misc.py:30-43 where the planes exist anyway: the forward launch's input planes and the
  * data-gradient launch's gradient planes, mmt_split_planes_f16_rb): dw += rowscale[co] * dy^T im2col(x), dbias += column sums of dy.
  * a: shapes (+ x for the exact path, f16_guard_x / f16_guard_dy); s_x / s_dy: device scalars, the planes' scales.
- * mmt_conv_wgrad_planes_splits: 0 when the layer is not taken (needs W % 32 == 0, Cin % 128 == 0, Cout % 128 == 0, odd square
- * kernel with pad (k - 1) / 2, stride 1, mode 3; MMT_WGRAD_PLANES=0), else the number of pixel ranges across blocks: workspace
- * (device, splits * Cout * KH * KW * Cin floats) is needed when it is > 1.  mmt_conv_wgrad_planes returns 1 and touches nothing
- * when the layer is not taken.  Products (h l), (l h), (h h) per 16 pixels, fp32 accumulation: the arithmetic of mmt_conv_wgrad's
+ * The layers it takes (mmt_conv_wgrad_route with MMT_WG_HAVE_PLANES: family MMT_WGRAD_PLANES_1 / _3) need W % 32 == 0, Cin % 128 == 0,
+ * Cout % 128 == 0, an odd square kernel with pad (k - 1) / 2, stride 1, mode 3 and MMT_WGRAD_PLANES not 0 in the environment; the
+ * route's `splits` is the number of pixel ranges across blocks: workspace (device, ws_floats = splits * Cout * KH * KW * Cin floats) is
+ * needed when it is > 1.  A call the route does not send here is MMT_EINVAL, with nothing touched: callers ask first.
+ * Products (h l), (l h), (h h) per 16 pixels, fp32 accumulation: the arithmetic of mmt_conv_wgrad's
  * fp16-split form, another summation order.  A 3x3 layer runs the three-tap form (one block = 128 co x (kh, 128 ci) x the three kw
  * taps from one copy of the operands, Cout / 128 x KH Cin / 128 tiles, 0.12 KB copied per MFMA); other kernel sizes the one-tap form
  * (Cout / 128 x KH KW Cin / 128 tiles, 0.33 KB per MFMA).  The meaning of the split count is the same for both. */
-int mmt_conv_wgrad_planes_splits(const mmt_conv_args* a /*[host]*/);
 int mmt_conv_wgrad_planes(const mmt_conv_args* a /*[host]*/, const float* dy, const void* x_planes, long x_plane_stride,
                           const void* dy_planes, long dy_plane_stride, const float* s_x, const float* s_dy, const float* rowscale,
                           float* dw, float* dbias, float* workspace, void* stream);
@@ -664,10 +701,9 @@ int mmt_pack_weights_flipped_f16(const mmt_flip_desc* descs /*[dev]*/, const int
 
 /* weight gradient: dw[co,kh,kw,ci] += rowscale[co] * sum_{n,ho,wo} dy[n,ho,wo,co] * x[n,ho*s+kh-p,wo*s+kw-p,ci]
  * (dw = the caller's gradient buffer, same layout as the weight; Cin % 4 == 0); optional dbias[co] += sum dy[..,co].
- * The pixel dimension is split over `mmt_conv_wgrad_splits(a)` blocks; when that is > 1 the caller passes a
- * workspace of splits * Cout*KH*KW*Cin floats (partial tiles are stored there and summed by a second kernel --
+ * The pixel dimension is split over `splits` blocks (mmt_conv_wgrad_route without MMT_WG_HAVE_PLANES); when that is > 1 the caller
+ * passes a workspace of ws_floats = splits * Cout*KH*KW*Cin floats (partial tiles are stored there and summed by a second kernel --
  * fp32 atomics measured 1.6x slower on mid-size layers).  Uses N,H,W,Cin,Cout,KH,KW,stride,pad,Ho,Wo of a. */
-int mmt_conv_wgrad_splits(const mmt_conv_args* a /*[host]*/);
 int mmt_conv_wgrad(const mmt_conv_args* a /*[host]; x = input, mask/mul/res unused*/, const float* dy,
                    const float* rowscale /*[Cout] or NULL*/, float* dw, float* dbias /*or NULL*/,
                    float* workspace /*or NULL when splits == 1*/, void* stream);

@@ -1927,13 +1927,8 @@ int launch_rows_k(const ConvP& p, hipStream_t s, int panels) {
   return MMT_EINVAL;
 }
 
-// run-time values of the route as compile-time constants: the number of bf16 terms of a split mode, the tile of a tiled kernel
-template <class F>
-int with_terms(int mode, F&& f) {
-  if (mode == 1) return f(std::integral_constant<int, 1>{});
-  if (mode == 2) return f(std::integral_constant<int, 2>{});
-  return f(std::integral_constant<int, 3>{});
-}
+// run-time values of the route as compile-time constants: the number of bf16 terms of a split mode (with_terms, conv_shared.h), the
+// tile of a tiled kernel
 template <class F>
 int with_tile(const Route& r, F&& f) {
   typedef std::integral_constant<int, 128> c128;

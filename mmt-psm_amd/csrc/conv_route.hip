@@ -1,4 +1,5 @@
-// Which kernel a convolution call runs on: the ONE owner of that decision (include/mmtpsm.h: mmt_conv_route).  Host code only.
+// Which kernel a convolution call runs on: the ONE owner of that decision (include/mmtpsm.h: mmt_conv_route; the weight gradient:
+// mmt_conv_wgrad_route, wgrad_route below).  Host code only.
 // mmt_conv_forward, mmt_conv_forward_f16x2, mmt_conv3x3_strip_f16x2 and mmt_conv_forward_pg compute route() and switch on it; the
 // host side asks mmt_conv_route with the same block.  Every shape test, tuned threshold and forward switch of the environment lives
 // in this file and is private to it; the tuned values are those of profiles/r04_dispatch_sweep.txt unless a comment says otherwise.
@@ -7,12 +8,16 @@
 namespace {
 using namespace mmtconv;
 
-// the six forward switches (A/B timing, parity tests): read per route, i.e. per call -- the tests flip them between launches
+// the six forward switches and the weight gradient's two (A/B timing, parity tests): read per route, i.e. per call -- the tests flip
+// them between launches
+bool on(const char* name) {
+  const char* e = getenv(name);
+  return !(e && atoi(e) == 0);
+}
 int read_switches() {
-  auto on = [](const char* e) { return !(e && atoi(e) == 0); };
-  return (on(getenv("MMT_SPLITK")) ? MMT_SW_SPLITK : 0) | (on(getenv("MMT_STRIP")) ? MMT_SW_STRIP : 0) |
-         (on(getenv("MMT_ROWS")) ? MMT_SW_ROWS : 0) | (on(getenv("MMT_PG")) ? MMT_SW_PG : 0) | (on(getenv("MMT_C64")) ? MMT_SW_C64 : 0) |
-         (on(getenv("MMT_DIRECT_EPI")) ? MMT_SW_DIRECT_EPI : 0);
+  return (on("MMT_SPLITK") ? MMT_SW_SPLITK : 0) | (on("MMT_STRIP") ? MMT_SW_STRIP : 0) | (on("MMT_ROWS") ? MMT_SW_ROWS : 0) |
+         (on("MMT_PG") ? MMT_SW_PG : 0) | (on("MMT_C64") ? MMT_SW_C64 : 0) | (on("MMT_DIRECT_EPI") ? MMT_SW_DIRECT_EPI : 0) |
+         wgrad_switches();
 }
 
 // operands that are in the block or promised by the caller (promised planes are promised aligned)
@@ -172,9 +177,90 @@ void take_strip(Route& r, int x_form) {
   r.family = MMT_ROUTE_STRIP; r.tag = 4; r.bm = 256; r.bn = 128; r.ksplit = r.strip_ksplit; r.x_form = x_form;
 }
 
+// ---- the weight gradient
+
+// pixel ranges of the register-fed kernels: `want` of them, each at least 512 pixels (32 k-tiles per block) and a multiple of 32
+void wg_ranges(int M, long want, int& splits, int& mps) {
+  constexpr int min_px = 512;   // (tuned: profiles/r04_dispatch_sweep.txt; in the step: profiles/r04_history.md)
+  if (want > mmt_cdiv(M, min_px)) want = mmt_cdiv(M, min_px);
+  if (want < 1) want = 1;
+  mps = (mmt_cdiv(M, (int)want) + 31) / 32 * 32;
+  splits = mmt_cdiv(M, mps);
+}
+
+// pixel ranges across blocks of the plane-fed kernel, 0: not one of its layers.  T: the 32-pixel super-steps of the reduction
+int wgpl_ranges(const ConvP& p, int mode, int sw, long& T) {
+  T = ((long)p.N * p.H * p.W) >> 5;
+  if (mode != 3 || !(sw & MMT_SW_WGRAD_PLANES) || p.stride != 1 || p.Ho != p.H || p.Wo != p.W || (p.W & 31) || (p.Cin & 127) ||
+      (p.Cout & 127) || p.KH != p.KW || p.pad != (p.KH - 1) / 2 || !(p.KH & 1) || p.io || T < 2 ||
+      (long)p.N * p.H * p.W * (p.Cin > p.Cout ? p.Cin : p.Cout) >= (1L << 29))
+    return 0;
+  // blocks per launch the pixel ranges aim at: profiles/r06_history.md.  The three-tap form has a third of the tiles and blocks that
+  // multiply three times as much per super-step: the same target gives it three times the ranges and blocks of the same duration
+  // (sweep of 128 / 192 / 256 / 384, isolated and in the step: profiles/wgrad_kw3_ab.txt)
+  constexpr long target = 256;
+  long ks = target / ((long)(p.Cout >> 7) * wg_tiles_n(p.KH, p.KW, p.Cin));
+  if (ks > T / 8) ks = T / 8;     // >= 4 super-steps per group and range (one tap); >= 8 per range behind the ring's three (three taps)
+  return ks < 1 ? 1 : (int)ks;
+}
+
 }  // namespace
 
 namespace mmtconv {
+
+int wgrad_switches() { return (on("MMT_WGRAD_PLANES") ? MMT_SW_WGRAD_PLANES : 0) | (on("MMT_WGRAD_GROUP") ? MMT_SW_WGRAD_GROUP : 0); }
+
+WgradRoute wgrad_route(const ConvP& p, int mode, int have, int sw) {
+  WgradRoute r = {};
+  r.switches = sw;
+  r.splits = r.group_splits = 1;
+  if (p.M == 0 || p.Cout == 0) return r;   // nothing to launch
+  // Pixel ranges per job inside a group: 1 / WG_DIV of what the job would use ALONE.  Measured in the step (profiles/r06_history.md
+  // section 7): filling the chip as a group makes blocks that own a CU for ~150 us and hold up the step stream's latency-bound chain
+  // (+2 ms); the jobs' own ranges only save launches and reduces (-0.3 ms); a quarter of them is the optimum (-0.5 ... -0.75 ms):
+  // blocks four times as long, a quarter of the slab traffic, still short
+  // (WG_DIV_PL: the plane-fed jobs' divisor.  The three-tap form has a third of the tiles and three times the ranges of the one-tap
+  // form at equal block duration; swept again in the step with it, 2 / 4 / 8 are not separable: profiles/wgrad_kw3_ab.txt)
+  constexpr int WG_DIV = 4, WG_DIV_PL = 4;
+  const bool group = (sw & MMT_SW_WGRAD_GROUP) != 0;
+  long T;
+  const int ks = (have & MMT_WG_HAVE_PLANES) ? wgpl_ranges(p, mode, sw, T) : 0;
+  if (ks) {
+    r.family = p.KW == 3 ? MMT_WGRAD_PLANES_3 : MMT_WGRAD_PLANES_1;
+    r.terms = 2; r.splits = ks; r.lds_bytes = WGPL_LDS; r.dbias_in_kernel = 1;
+    r.ws_floats = ks > 1 ? (long)ks * p.Cout * p.K : 0;
+    long gs = (ks + WG_DIV_PL - 1) / WG_DIV_PL;
+    if (gs > T / 8) gs = T / 8;
+    r.group_splits = gs < 1 ? 1 : (int)gs;
+    r.group_kind = group ? 1 : 0;
+  } else {
+    // all blocks of a launch run equally long: fill the 512 resident slots (256 CUs x 2 blocks) ONCE.  (640 = 1.25
+    // rounds cost a second, 20 %-full round: 92 -> 105 TFLOP/s fp32, 103 -> 136 split-bf16 on the FPN 3x3 shapes)
+    constexpr int slots = 512;    // (tuned: profiles/r04_dispatch_sweep.txt; in the step: r04 / r06 history)
+    const long tiles = (long)mmt_cdiv(p.K, 128) * mmt_cdiv(p.Cout, 128);
+    wg_ranges(p.M, tiles >= slots ? 1 : slots / tiles, r.splits, r.mps);
+    r.ws_floats = r.splits > 1 ? (long)r.splits * p.Cout * p.K : 0;
+    wg_ranges(p.M, (r.splits + WG_DIV - 1) / WG_DIV, r.group_splits, r.group_mps);
+    r.decode = !(p.Wo >= 8 && p.Ho >= 8) ? 0 : ((p.Wo & 3) == 0 ? 2 : 1);
+    r.vec4 = (p.Cout & 3) == 0;
+    r.bf = ((p.io & IO_X) ? 1 : 0) | ((p.io & IO_DY) ? 2 : 0);   // bf16 storage of x / dy: mode 1, the pipelined kernel with 4-channel loads only
+    // the pipelined kernel addresses both operands with 32-bit byte offsets (buffer loads)
+    const bool small = (long)p.N * p.H * p.W * p.Cin * 4 < (1L << 31) && (long)p.M * p.Cout * 4 < (1L << 31);
+    r.lds_bytes = 65536;   // the 64 KB epilogue tile (>= 3 stages of 16 KB); fp32: 4 stages of 4096 floats
+    r.dbias_in_kernel = 1;
+    const bool f16 = (have & MMT_WG_HAVE_MAXIMA) != 0;   // the two-term fp16 split: mode 3, fp32 tensors
+    if (!p.cin4 || (f16 ? !(mode == 3 && !r.bf && r.vec4 && small) : (r.bf && !(mode == 1 && r.vec4 && small)))) return r;   // no kernel
+    if (f16) {
+      r.family = MMT_WGRAD_PIPE_F16; r.terms = 2;
+      r.group_kind = group && !p.io ? 2 + r.decode : 0;
+    } else if (mode > 0 && small) {
+      r.family = MMT_WGRAD_PIPE; r.terms = mode;
+      if (mode >= 3) r.lds_bytes = 73728;            // the three operand stages of the 3-term split (3 x 24 KB)
+    } else if (mode > 0 && r.vec4) { r.family = MMT_WGRAD_SPLIT; r.terms = mode; }
+    else { r.family = r.vec4 && r.decode ? MMT_WGRAD_FP32_FAST : MMT_WGRAD_FP32_SLOW; r.dbias_in_kernel = 0; }
+  }
+  return r;
+}
 
 Route route(const ConvP& p, int mode, int entry, int assume) {
   Route r = {};
@@ -237,6 +323,15 @@ extern "C" int mmt_conv_route(const mmt_conv_args* a, int entry, int assume, mmt
   const int e = fill(p, a, (assume & MMT_ASSUME_X) != 0);
   if (e) return e;
   *out = route(p, precision(), entry, assume);
+  return 0;
+}
+
+extern "C" int mmt_conv_wgrad_route(const mmt_conv_args* a, int have, mmt_conv_wgrad_route_t* out) {
+  ConvP p;
+  if (!out) return MMT_EINVAL;
+  const int e = fill(p, a, true);
+  if (e) return e;
+  *out = wgrad_route(p, precision(), have | (a->f16_x_amax && a->f16_dy_amax ? MMT_WG_HAVE_MAXIMA : 0), read_switches());
   return 0;
 }
 

@@ -60,9 +60,16 @@ struct WgReduceItem { const float* ws; const float* rowscale; float* dw; int spl
 int launch_wgrad_reduce_group(const WgReduceItem* items, int n, hipStream_t s);
 struct WgPlJob { const mmt_conv_args* a; const float* dy; const void* xpl; long xpl_stride; const void* dpl; long dpl_stride;
                  const float* s_x; const float* s_dy; const float* rowscale; float* dw; float* dbias; float* ws; int ksplit; };
-int wgpl_eligible_splits(const mmt_conv_args* a);   // > 0: the plane-fed weight gradient takes the layer
-long wgpl_super_steps(const mmt_conv_args* a);      // 32-pixel super-steps of the layer's reduction
 int launch_wgpl_group(const WgPlJob* jobs, int n, hipStream_t s);
+int launch_wgpl_single(const WgPlJob& job, hipStream_t s);   // a launch of its own (+ its reduce launch) with job.ksplit ranges
+// THE decision which kernel a weight-gradient call runs on, with how many pixel ranges and how much workspace (conv_route.hip;
+// include/mmtpsm.h: mmt_conv_wgrad_route).  `have`: MMT_WG_HAVE_*.  mmt_conv_wgrad, mmt_conv_wgrad_planes and mmt_conv_wgrad_group
+// switch on the answer; nothing else tests a shape or reads a weight-gradient switch.
+// sw: wgrad_switches(), the weight gradient's two switches of the environment as they stand (an entry point reads them once per call).
+typedef mmt_conv_wgrad_route_t WgradRoute;
+int wgrad_switches();
+WgradRoute wgrad_route(const ConvP& p, int mode, int have, int sw);
+constexpr int WGPL_LDS = 4 * 32 * (1024 + 128);   // dynamic LDS of both forms of the plane-fed weight gradient (conv_wgpl.hip: WgForm)
 // layer1's 3x3 (64 -> 64 channels) on the patch kernel of conv_stem.hip (MMT_ROUTE_C64)
 int launch_c64(const ConvP& p, hipStream_t s);
 }  // namespace mmtconv
@@ -156,6 +163,17 @@ __device__ __forceinline__ float f16_scale_of(const float amax) {
   e = e > 100 ? 100 : (e < -100 ? -100 : e);
   return ldexpf(1.f, e);
 }
+
+// a run-time value of a route as a compile-time constant: the number of bf16 terms of a split mode
+template <class F>
+int with_terms(int mode, F&& f) {
+  if (mode == 1) return f(std::integral_constant<int, 1>{});
+  if (mode == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 3>{});
+}
+
+// column tiles of a plane-fed weight gradient: 128 (tap, ci) columns each -- or, in the three-tap form, the 3 x 128 columns of one (kh, ci block)
+__host__ __device__ __forceinline__ int wg_tiles_n(int KH, int KW, int Cin) { return (KW == 3 ? KH * Cin : KH * KW * Cin) >> 7; }
 
 __device__ __forceinline__ f32x4 ldg4(const float* p) { return *(const f32x4*)p; }
 // ---- EXPERIMENT (mmt_conv3x3_strip_f16x2, tools/bench_f16x2.py): two-term fp16 split of a pre-scaled value, x * s = h + l

@@ -78,9 +78,6 @@ struct WgP {
   int lag;   // round 6: bit 0 / bit 1 -- the planes of x / of dy were written by their producer's epilogue with a scale fixed beforehand
 };
 
-// column tiles of a layer: 128 (tap, ci) columns each -- or, in the three-tap form, the 3 x 128 columns of one (kh, ci block)
-__host__ __device__ __forceinline__ int wg_tiles_n(int KH, int KW, int Cin) { return (KW == 3 ? KH * Cin : KH * KW * Cin) >> 7; }
-
 // bid_in / nwg: this block's index among the blocks of its launch -- or, in a grouped launch (wgrad_pl_group_kernel), of its item
 template <int TAPS> __device__ __forceinline__ void wgrad_pl_body(const WgP& p, const int bid_in, const int nwg_in) {
   typedef WgForm<TAPS> F;
@@ -423,33 +420,42 @@ __global__ __launch_bounds__(256) void wgrad_pl_reduce_kernel(const float* __res
   }
 }
 
-// does the plane-fed weight gradient take this layer, and with how many pixel ranges across blocks?  0 = no
-int wgpl_splits(const mmt_conv_args* a) {
-  if (precision() != 3 || a->stride != 1 || a->Ho != a->H || a->Wo != a->W || (a->W & 31) || (a->Cin & 127) || (a->Cout & 127) ||
-      a->KH != a->KW || a->pad != (a->KH - 1) / 2 || !(a->KH & 1) || a->N < 1 || a->io_bf16 ||
-      (long)a->N * a->H * a->W * (a->Cin > a->Cout ? a->Cin : a->Cout) >= (1L << 29))
-    return 0;
-  const char* e = getenv("MMT_WGRAD_PLANES");   // read per call (A/B timing, parity tests)
-  if (e && atoi(e) == 0) return 0;
-  const long T = ((long)a->N * a->H * a->W) >> 5;
-  const long tiles = (long)(a->Cout >> 7) * wg_tiles_n(a->KH, a->KW, a->Cin);
-  // (blocks per launch the pixel ranges aim at: profiles/r06_history.md.  The three-tap form -- target3 -- has a third of the tiles
-  // and blocks that multiply three times as much per super-step: the same target gives it three times the ranges and blocks of the
-  // same duration.  Sweep of 128 / 192 / 256 / 384, isolated and in the step: profiles/wgrad_kw3_ab.txt)
-  constexpr long target = 256, target3 = 256;
-  long ks = (a->KW == 3 ? target3 : target) / tiles;
-  if (ks > T / 8) ks = T / 8;     // >= 4 super-steps per group and range (one tap); >= 8 per range behind the ring's three (three taps)
-  if (ks < 1) ks = 1;
-  if (T < 2) return 0;
-  return (int)ks;
+static_assert(WgForm<1>::LDS == (size_t)WGPL_LDS, "the route reports this size");
+
+// a job -> the kernel's parameter block; false: an operand is missing or misaligned
+bool wgp_of(const WgPlJob& j, WgP& p) {
+  const mmt_conv_args* a = j.a;
+  if (!a->x || !j.dy || !j.xpl || !j.dpl || !j.s_x || !j.s_dy || !j.dw || ((size_t)j.xpl & 15) || ((size_t)j.dpl & 15) ||
+      (j.xpl_stride & 7) || (j.dpl_stride & 7) || j.ksplit < 1 || (j.ksplit > 1 && !j.ws))
+    return false;
+  p.x = a->x; p.dy = j.dy;
+  p.xpl = (const unsigned short*)j.xpl; p.xpl_stride = j.xpl_stride;
+  p.dpl = (const unsigned short*)j.dpl; p.dpl_stride = j.dpl_stride;
+  p.s_x = j.s_x; p.s_dy = j.s_dy;
+  p.guard_x = (const float*)a->f16_guard_x; p.guard_dy = (const float*)a->f16_guard_dy;
+  p.rowscale = j.rowscale; p.dw = j.dw; p.ws = j.ws; p.dbias = j.dbias;
+  p.lag = a->x_planes_lag;
+  p.N = a->N; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.KH = a->KH; p.KW = a->KW; p.pad = a->pad; p.ksplit = j.ksplit;
+  return true;
+}
+
+// one launcher per form: the LDS attribute once per instantiation
+template <int TAPS>
+int launch_wgpl(const WgP& p, int blocks, hipStream_t s) {
+  static bool done = false;
+  if (!done) {
+    const hipError_t e = hipFuncSetAttribute((const void*)wgrad_pl_kernel<TAPS>, hipFuncAttributeMaxDynamicSharedMemorySize, WGPL_LDS);
+    if (e != hipSuccess) return (int)e;
+    done = true;
+  }
+  hipLaunchKernelGGL(wgrad_pl_kernel<TAPS>, dim3(blocks), dim3(768), (size_t)WGPL_LDS, s, p);
+  MMT_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace
 
 namespace mmtconv {
-int wgpl_eligible_splits(const mmt_conv_args* a) { return a ? wgpl_splits(a) : 0; }
-long wgpl_super_steps(const mmt_conv_args* a) { return ((long)a->N * a->H * a->W) >> 5; }
-
 int launch_wgrad_reduce_group(const WgReduceItem* items, int n, hipStream_t s) {
   for (int i0 = 0; i0 < n; i0 += WG_MAXR) {
     WgReduceGroup g;
@@ -475,79 +481,51 @@ int launch_wgpl_group(const WgPlJob* jobs, int n, hipStream_t s) {
   g.n = n;
   int nb = 0;
   for (int i = 0; i < n; i++) {
-    const WgPlJob& j = jobs[i];
-    const mmt_conv_args* a = j.a;
-    if (!a->x || !j.dy || !j.xpl || !j.dpl || !j.s_x || !j.s_dy || !j.dw || ((size_t)j.xpl & 15) || ((size_t)j.dpl & 15) ||
-        (j.xpl_stride & 7) || (j.dpl_stride & 7) || j.ksplit < 1 || (j.ksplit > 1 && !j.ws))
-      return MMT_EINVAL;
-    WgP& p = g.it[i];
-    p.x = a->x; p.dy = j.dy;
-    p.xpl = (const unsigned short*)j.xpl; p.xpl_stride = j.xpl_stride;
-    p.dpl = (const unsigned short*)j.dpl; p.dpl_stride = j.dpl_stride;
-    p.s_x = j.s_x; p.s_dy = j.s_dy;
-    p.guard_x = (const float*)a->f16_guard_x; p.guard_dy = (const float*)a->f16_guard_dy;
-    p.rowscale = j.rowscale; p.dw = j.dw; p.ws = j.ws; p.dbias = j.dbias;
-    p.lag = a->x_planes_lag;
-    p.N = a->N; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.KH = a->KH; p.KW = a->KW; p.pad = a->pad; p.ksplit = j.ksplit;
+    if (!wgp_of(jobs[i], g.it[i])) return MMT_EINVAL;
+    const mmt_conv_args* a = jobs[i].a;
     g.first[i] = nb;
-    const int blocks = (a->Cout >> 7) * wg_tiles_n(a->KH, a->KW, a->Cin) * j.ksplit;
+    const int blocks = (a->Cout >> 7) * wg_tiles_n(a->KH, a->KW, a->Cin) * jobs[i].ksplit;
     nb += (blocks + 7) & ~7;
   }
   g.first[n] = nb;
-  constexpr size_t lds = WgForm<3>::LDS;
   static bool done = false;
   if (!done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)wgrad_pl_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = hipFuncSetAttribute((const void*)wgrad_pl_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WGPL_LDS);
     if (e != hipSuccess) return (int)e;
     done = true;
   }
-  hipLaunchKernelGGL(wgrad_pl_group_kernel, dim3(nb), dim3(768), lds, s, g);
+  hipLaunchKernelGGL(wgrad_pl_group_kernel, dim3(nb), dim3(768), (size_t)WGPL_LDS, s, g);
   MMT_LAUNCH_CHECK();
+  return 0;
+}
+
+// one plane-fed job as a launch of its own, with the route's pixel ranges in job.ksplit, and the reduce launch behind it
+int launch_wgpl_single(const WgPlJob& j, hipStream_t s) {
+  WgP p;
+  if (!wgp_of(j, p)) return MMT_EINVAL;
+  const mmt_conv_args* a = j.a;
+  const int NP = a->KH * a->KW * a->Cin, blocks = (a->Cout >> 7) * wg_tiles_n(a->KH, a->KW, a->Cin) * j.ksplit;
+  const int e = a->KW == 3 ? launch_wgpl<3>(p, blocks, s) : launch_wgpl<1>(p, blocks, s);
+  if (e) return e;
+  if (j.ksplit > 1) {
+    const long n4 = (long)a->Cout * NP / 4;
+    int rb = (int)((n4 + 255) / 256);
+    if (rb > 4096) rb = 4096;
+    hipLaunchKernelGGL(wgrad_pl_reduce_kernel, dim3(rb), dim3(256), 0, s, j.ws, j.ksplit, a->Cout, NP, j.rowscale, j.dw);
+    MMT_LAUNCH_CHECK();
+  }
   return 0;
 }
 }  // namespace mmtconv
 
-extern "C" int mmt_conv_wgrad_planes_splits(const mmt_conv_args* a) { return a ? wgpl_splits(a) : 0; }
-
 extern "C" int mmt_conv_wgrad_planes(const mmt_conv_args* a, const float* dy, const void* x_planes, long x_plane_stride,
                                      const void* dy_planes, long dy_plane_stride, const float* s_x, const float* s_dy,
                                      const float* rowscale, float* dw, float* dbias, float* workspace, void* stream) {
-  if (!a) return MMT_EINVAL;
-  const int ks = wgpl_splits(a);
-  if (ks == 0) return 1;   // not taken: the caller runs mmt_conv_wgrad
-  if (!a->x || !dy || !x_planes || !dy_planes || !s_x || !s_dy || !dw || ((size_t)x_planes & 15) || ((size_t)dy_planes & 15) ||
-      (x_plane_stride & 7) || (dy_plane_stride & 7) || (ks > 1 && !workspace))
-    return MMT_EINVAL;
-  WgP p;
-  p.x = a->x; p.dy = dy;
-  p.xpl = (const unsigned short*)x_planes; p.xpl_stride = x_plane_stride;
-  p.dpl = (const unsigned short*)dy_planes; p.dpl_stride = dy_plane_stride;
-  p.s_x = s_x; p.s_dy = s_dy;
-  p.guard_x = (const float*)a->f16_guard_x; p.guard_dy = (const float*)a->f16_guard_dy;
-  p.rowscale = rowscale; p.dw = dw; p.ws = workspace; p.dbias = dbias;
-  p.lag = a->x_planes_lag;
-  p.N = a->N; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.KH = a->KH; p.KW = a->KW; p.pad = a->pad; p.ksplit = ks;
-  const int NP = a->KH * a->KW * a->Cin;
-  const int tiles = (a->Cout >> 7) * wg_tiles_n(a->KH, a->KW, a->Cin);
-  const bool kw3 = a->KW == 3;
-  const size_t lds = kw3 ? WgForm<3>::LDS : WgForm<1>::LDS;
-  static bool done[2] = {false, false};
-  if (!done[kw3]) {
-    const hipError_t e = hipFuncSetAttribute(kw3 ? (const void*)wgrad_pl_kernel<3> : (const void*)wgrad_pl_kernel<1>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    done[kw3] = true;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  if (kw3) hipLaunchKernelGGL(wgrad_pl_kernel<3>, dim3(tiles * ks), dim3(768), lds, s, p);
-  else hipLaunchKernelGGL(wgrad_pl_kernel<1>, dim3(tiles * ks), dim3(768), lds, s, p);
-  MMT_LAUNCH_CHECK();
-  if (ks > 1) {
-    const long n4 = (long)a->Cout * NP / 4;
-    int blocks = (int)((n4 + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(wgrad_pl_reduce_kernel, dim3(blocks), dim3(256), 0, s, workspace, ks, a->Cout, NP, rowscale, dw);
-    MMT_LAUNCH_CHECK();
-  }
-  return 0;
+  ConvP p;
+  const int e = fill(p, a);
+  if (e) return e;
+  const WgradRoute r = wgrad_route(p, precision(), MMT_WG_HAVE_PLANES, wgrad_switches());
+  if (r.family != MMT_WGRAD_PLANES_1 && r.family != MMT_WGRAD_PLANES_3) return MMT_EINVAL;   // callers ask the route first
+  return launch_wgpl_single(WgPlJob{a, dy, x_planes, x_plane_stride, dy_planes, dy_plane_stride, s_x, s_dy, rowscale, dw, dbias, workspace,
+                                    r.splits}, (hipStream_t)stream);
 }

@@ -860,114 +860,103 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ d
 
 }  // namespace
 
-extern "C" int mmt_conv_wgrad_splits(const mmt_conv_args* a) {
-  ConvP p;
-  int e = fill(p, a);
-  if (e) return e;
-  if (p.M == 0 || p.Cout == 0) return 1;
-  const int NP = p.KH * p.KW * p.Cin;
-  const int tx = mmt_cdiv(NP, 128), ty = mmt_cdiv(p.Cout, 128);
-  // all blocks of a launch run equally long: fill the 512 resident slots (256 CUs x 2 blocks) ONCE.  (640 = 1.25
-  // rounds cost a second, 20 %-full round: 92 -> 105 TFLOP/s fp32, 103 -> 136 split-bf16 on the FPN 3x3 shapes)
-  const long tiles = (long)tx * ty;
-  constexpr int slots = 512;    // (tuned: profiles/r04_dispatch_sweep.txt; in the step: r04 / r06 history)
-  constexpr int min_px = 512;   // (tuned: profiles/r04_dispatch_sweep.txt; in the step: profiles/r04_history.md)
-  int split = (int)(tiles >= slots ? 1 : slots / tiles);
-  const int max_split = mmt_cdiv(p.M, min_px);  // at least min_px / 16 k-tiles per block
-  if (split > max_split) split = max_split;
-  if (split < 1) split = 1;
-  int mps = mmt_cdiv(p.M, split);
-  mps = (mps + 31) / 32 * 32;
-  return mmt_cdiv(p.M, mps);
+namespace {
+// ---- launchers: one per kernel family, used by mmt_conv_wgrad and by the single launches of mmt_conv_wgrad_group.  Each holds the
+// LDS size of its kernel and sets the attribute for a size above 64 KiB once per instantiation.
+struct WgCall { ConvP p; const float* dy; const float* rowscale; float* dw; float* dbias; float* ws; int splits, mps; hipStream_t s; };
+dim3 wg_grid(const WgCall& c) { return dim3(mmt_cdiv(c.p.K, 128), mmt_cdiv(c.p.Cout, 128), c.splits); }
+
+template <bool FAST>
+int launch_fp32(const WgCall& c) {
+  hipLaunchKernelGGL(conv_wgrad_kernel<FAST>, wg_grid(c), dim3(256), (size_t)4 * 4096 * sizeof(float), c.s, c.p, c.dy, c.rowscale, c.dw, c.mps, c.ws);
+  MMT_LAUNCH_CHECK();
+  return 0;
 }
+template <int NS, bool INC>
+int launch_split(const WgCall& c) {
+  hipLaunchKernelGGL((conv_wgrad_split_kernel<NS, INC>), wg_grid(c), dim3(256), (size_t)65536, c.s, c.p, c.dy, c.rowscale, c.dw, c.mps, c.ws, c.dbias);
+  MMT_LAUNCH_CHECK();
+  return 0;
+}
+template <int NS, int MODE, bool VEC4, int BF, bool F16>
+int launch_pipe(const WgCall& c) {
+  // LDS: the 64 KB epilogue tile (the fp16 split's 3 stages of 16 KB fit in it), or the three operand stages of the 3-term split (3 x 24 KB)
+  constexpr size_t lds = !F16 && NS >= 3 ? 73728 : 65536;
+  auto kern = conv_wgrad_pipe_kernel<NS, MODE, VEC4, BF, F16>;
+  static bool done = false;  // per instantiation
+  if (lds > 65536 && !done) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    done = true;
+  }
+  hipLaunchKernelGGL(kern, wg_grid(c), dim3(256), lds, c.s, c.p, c.dy, c.rowscale, c.dw, c.mps, c.ws, c.dbias);
+  MMT_LAUNCH_CHECK();
+  return 0;
+}
+
+// the route's pixel-decode form as a compile-time constant
+template <class F>
+int with_decode(int decode, F&& f) {
+  if (decode == 2) return f(std::integral_constant<int, 2>{});
+  if (decode == 1) return f(std::integral_constant<int, 1>{});
+  return f(std::integral_constant<int, 0>{});
+}
+
+// one register-fed weight gradient as a launch of its own: the route's kernel, the reduce launch behind `splits` > 1 ranges, the
+// column sums where the kernel's epilogue does not add dbias
+int launch_wgrad(const mmt_conv_args* a, const WgradRoute& r, WgCall c) {
+  if (!c.dy || !c.dw || !c.p.cin4) return MMT_EINVAL;
+  if (c.p.M == 0 || c.p.Cout == 0) return 0;
+  if (c.splits > 1 && !c.ws) return MMT_EINVAL;
+  if (c.splits == 1) c.ws = nullptr;
+  int e = MMT_EINVAL;   // (MMT_WGRAD_NONE: no kernel takes the call)
+  if (r.family == MMT_WGRAD_PIPE_F16) {   // x_amax / dy_amax = device maxima of the two operands
+    c.p.f16_sx = (const float*)a->f16_x_amax;
+    c.p.f16_sw = (const float*)a->f16_dy_amax;
+    e = with_decode(r.decode, [&](auto D) { return launch_pipe<2, decltype(D)::value, true, 0, true>(c); });
+  } else if (r.family == MMT_WGRAD_PIPE) {
+    e = with_terms(r.terms, [&](auto NS) {
+      return with_decode(r.decode, [&](auto D) {
+        constexpr int ns = decltype(NS)::value, d = decltype(D)::value;
+        if constexpr (ns == 1) {   // bf16 storage: mode 1 only (the route)
+          if (r.bf == 1) return launch_pipe<1, d, true, 1, false>(c);
+          if (r.bf == 2) return launch_pipe<1, d, true, 2, false>(c);
+          if (r.bf == 3) return launch_pipe<1, d, true, 3, false>(c);
+        }
+        return r.vec4 ? launch_pipe<ns, d, true, 0, false>(c) : launch_pipe<ns, d, false, 0, false>(c);
+      });
+    });
+  } else if (r.family == MMT_WGRAD_SPLIT) {
+    e = with_terms(r.terms, [&](auto NS) {
+      return r.decode ? launch_split<decltype(NS)::value, true>(c) : launch_split<decltype(NS)::value, false>(c);
+    });
+  } else if (r.family == MMT_WGRAD_FP32_FAST) e = launch_fp32<true>(c);
+  else if (r.family == MMT_WGRAD_FP32_SLOW) e = launch_fp32<false>(c);
+  if (e) return e;
+  if (c.splits > 1) {
+    const long n4 = (long)c.p.Cout * c.p.K / 4;
+    int blocks = (int)((n4 + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, c.s, c.ws, c.splits, c.p.Cout, c.p.K, c.rowscale, c.dw);   // (the slabs are un-scaled)
+    MMT_LAUNCH_CHECK();
+  }
+  if (c.dbias && !r.dbias_in_kernel) {
+    const int rpb = 1024;
+    hipLaunchKernelGGL(colsum_kernel, dim3(mmt_cdiv(c.p.Cout, 64), mmt_cdiv(c.p.M, rpb)), dim3(256), 0, c.s, c.dy, c.p.M, c.p.Cout, c.dbias, rpb);
+    MMT_LAUNCH_CHECK();
+  }
+  return 0;
+}
+}  // namespace
 
 extern "C" int mmt_conv_wgrad(const mmt_conv_args* a, const float* dy, const float* rowscale, float* dw,
                               float* dbias, float* workspace, void* stream) {
   ConvP p;
-  int e = fill(p, a);
+  const int e = fill(p, a);
   if (e) return e;
-  if (!dy || !dw || !p.cin4) return MMT_EINVAL;
-  if (p.M == 0 || p.Cout == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  const int NP = p.KH * p.KW * p.Cin;
-  const int tx = mmt_cdiv(NP, 128), ty = mmt_cdiv(p.Cout, 128);
-  const int split = mmt_conv_wgrad_splits(a);
-  int mps = mmt_cdiv(p.M, split);
-  mps = (mps + 31) / 32 * 32;
-  if (split > 1 && !workspace) return MMT_EINVAL;
-  float* ws = split > 1 ? workspace : nullptr;
-  const bool fast = (p.Cout & 3) == 0 && p.Wo >= 8 && p.Ho >= 8;
-  const int prec = precision();
-  // bf16 storage of x (IO_X) / dy (IO_DY): mode 1, the pipelined kernel with 4-channel loads only
-  const int bf = ((p.io & IO_X) ? 1 : 0) | ((p.io & IO_DY) ? 2 : 0);
-  // opt-in fp16 two-term split (mode 3 only): x_amax / dy_amax = device maxima of the two operands
-  const bool f16 = a->f16_x_amax && a->f16_dy_amax;
-  if (f16) {
-    if (prec != 3 || bf || (p.Cout & 3) || (mps & 15) || !((long)p.N * p.H * p.W * p.Cin * 4 < (1L << 31) && (long)p.M * p.Cout * 4 < (1L << 31)))
-      return MMT_EINVAL;
-    p.f16_sx = (const float*)a->f16_x_amax;
-    p.f16_sw = (const float*)a->f16_dy_amax;
-    const dim3 grid(tx, ty, split);
-    const int mode = !(p.Wo >= 8 && p.Ho >= 8) ? 0 : ((p.Wo & 3) == 0 ? 2 : 1);
-#define WGF(MODE) hipLaunchKernelGGL((conv_wgrad_pipe_kernel<2, MODE, true, 0, true>), grid, dim3(256), (size_t)65536, s, p, dy, rowscale, dw, mps, ws, dbias)   /* 3 stages of 16 KB <= the 64 KB epilogue tile */
-    if (mode == 2) WGF(2); else if (mode == 1) WGF(1); else WGF(0);
-#undef WGF
-    MMT_LAUNCH_CHECK();
-    if (split > 1) {
-      const long n4 = (long)p.Cout * NP / 4;
-      int blocks = (int)((n4 + 255) / 256);
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, ws, split, p.Cout, NP, rowscale, dw);   // (the slabs are un-scaled)
-      MMT_LAUNCH_CHECK();
-    }
-    return 0;
-  }
-  if (bf && !(prec == 1 && (p.Cout & 3) == 0 && (mps & 15) == 0 && (long)p.N * p.H * p.W * p.Cin * 4 < (1L << 31) &&
-              (long)p.M * p.Cout * 4 < (1L << 31)))
-    return MMT_EINVAL;
-  constexpr int pipe_any = 1;   // (tuned: profiles/r04_dispatch_sweep.txt)
-  const bool small_t = (long)p.N * p.H * p.W * p.Cin * 4 < (1L << 31) && (long)p.M * p.Cout * 4 < (1L << 31);
-  if (prec > 0 && ((p.Cout & 3) == 0 || (pipe_any && small_t)) && (mps & 15) == 0) {
-    const dim3 grid(tx, ty, split);
-    constexpr int pipe = 1;   // (tuned: profiles/r04_dispatch_sweep.txt)
-    // the pipelined kernel addresses both operands with 32-bit byte offsets (buffer loads)
-    const bool small = (long)p.N * p.H * p.W * p.Cin * 4 < (1L << 31) && (long)p.M * p.Cout * 4 < (1L << 31);
-    const int mode = !(p.Wo >= 8 && p.Ho >= 8) ? 0 : ((p.Wo & 3) == 0 ? 2 : 1);
-    const bool vec4 = (p.Cout & 3) == 0;
-    // LDS: the 64 KB epilogue tile, or the three operand stages of the 3-term split (3 x 24 KB)
-    const size_t wg_lds = prec >= 3 ? 73728 : 65536;
-#define WGPL(K) do { if (wg_lds > 65536) { const hipError_t er = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_lds); if (er != hipSuccess) return (int)er; } hipLaunchKernelGGL(K, grid, dim3(256), wg_lds, s, p, dy, rowscale, dw, mps, ws, dbias); } while (0)
-#define WGP(NS, MODE) do { if (bf && NS == 1) { if (bf == 1) WGPL((conv_wgrad_pipe_kernel<1, MODE, true, 1>)); else if (bf == 2) WGPL((conv_wgrad_pipe_kernel<1, MODE, true, 2>)); else WGPL((conv_wgrad_pipe_kernel<1, MODE, true, 3>)); } else if (vec4) WGPL((conv_wgrad_pipe_kernel<NS, MODE, true>)); else WGPL((conv_wgrad_pipe_kernel<NS, MODE, false>)); } while (0)
-#define WGP3(NS) do { if (mode == 2) WGP(NS, 2); else if (mode == 1) WGP(NS, 1); else WGP(NS, 0); } while (0)
-#define WGS(NS, INC) do { if ((pipe && small) || bf) WGP3(NS); else hipLaunchKernelGGL((conv_wgrad_split_kernel<NS, INC>), grid, dim3(256), (size_t)65536, s, p, dy, rowscale, dw, mps, ws, dbias); } while (0)
-    if (fast) { if (prec == 1) WGS(1, true); else if (prec == 2) WGS(2, true); else WGS(3, true); }
-    else { if (prec == 1) WGS(1, false); else if (prec == 2) WGS(2, false); else WGS(3, false); }
-#undef WGP3
-#undef WGP
-#undef WGPL
-#undef WGS
-    dbias = nullptr;  // summed inside the kernel
-  } else if (fast)
-    hipLaunchKernelGGL(conv_wgrad_kernel<true>, dim3(tx, ty, split), dim3(256), (size_t)4 * 4096 * sizeof(float), s, p,
-                       dy, rowscale, dw, mps, ws);
-  else
-    hipLaunchKernelGGL(conv_wgrad_kernel<false>, dim3(tx, ty, split), dim3(256), (size_t)4 * 4096 * sizeof(float), s, p,
-                       dy, rowscale, dw, mps, ws);
-  MMT_LAUNCH_CHECK();
-  if (split > 1) {
-    const long n4 = (long)p.Cout * NP / 4;
-    int blocks = (int)((n4 + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, ws, split, p.Cout, NP, rowscale, dw);
-    MMT_LAUNCH_CHECK();
-  }
-  if (dbias) {
-    int rpb = 1024;
-    hipLaunchKernelGGL(colsum_kernel, dim3(mmt_cdiv(p.Cout, 64), mmt_cdiv(p.M, rpb)), dim3(256), 0, s, dy, p.M,
-                       p.Cout, dbias, rpb);
-    MMT_LAUNCH_CHECK();
-  }
-  return 0;
+  // opt-in fp16 two-term split (mode 3 only): both maxima in the block
+  const WgradRoute r = wgrad_route(p, precision(), a->f16_x_amax && a->f16_dy_amax ? MMT_WG_HAVE_MAXIMA : 0, wgrad_switches());
+  return launch_wgrad(a, r, WgCall{p, dy, rowscale, dw, dbias, workspace, r.splits, r.mps, (hipStream_t)stream});
 }
 
 // ---- round 6: the weight gradients of a BATCH of layers -- what a backward pass hands to the side stream at a
@@ -975,89 +964,50 @@ extern "C" int mmt_conv_wgrad(const mmt_conv_args* a, const float* dy, const flo
 // <= 12 on wgrad_pl_group_kernel, the fp16-split jobs without planes in groups of <= 6 per pixel-decode mode on
 // conv_wgrad_pipe_group_kernel, ONE reduce launch for every slab of the batch; whatever fits neither (and any group of one) goes out
 // as the single launch it always was.  Inside a group the tiles of all layers fill the chip together, so a layer needs fewer pixel
-// ranges than alone -- a quarter of them (see wg_plan): longer reductions per block, a quarter of the slab traffic.
+// ranges than alone -- a quarter of them (the route's group_splits): longer reductions per block, a quarter of the slab traffic.
 // Summation order: fixed by (the batch's composition, shapes) -- repeatable, but not the single launches' order when ranges differ.
 namespace {
 // jobs per grouped launch: at most what the kernel-argument segment holds (the sweep of profiles/r06_history.md)
 constexpr int WG_CAP_PL = 12, WG_CAP_PIPE = WGP_MAXG;
-struct WgJobPlan { int kind; int split; int mps; long ws_off; };   // kind 0: single launch (mmt_conv_wgrad / _planes); 1: plane-fed group; 2 + mode: pipe group
+// kind 0: single launch; 1: plane-fed group; 2 + decode: pipe group.  err: the job's block is malformed (the launch returns it)
+struct WgJobPlan { ConvP p; WgradRoute r; int err, kind, split, mps; long ws_off; };
 constexpr int WGJ_MAX = 96;
+static_assert(sizeof(WgJobPlan) * WGJ_MAX <= 64 * 1024, "a batch's plan lives on the calling thread's stack");
 
-static bool wg_job_pipe_ok(const mmt_wgrad_job& j, ConvP& p) {
-  if (fill(p, &j.a) || !j.dy || !j.dw || !p.cin4 || p.M == 0 || p.Cout == 0) return false;
-  if (!j.a.f16_x_amax || !j.a.f16_dy_amax || precision() != 3 || p.io || (p.Cout & 3)) return false;
-  return (long)p.N * p.H * p.W * p.Cin * 4 < (1L << 31) && (long)p.M * p.Cout * 4 < (1L << 31);
-}
-
-// -> workspace floats; plan[i] filled; chunk boundaries are recomputed by the launcher the same way
-static long wg_plan(const mmt_wgrad_job* jobs, int n, WgJobPlan* plan) {
-  const char* e = getenv("MMT_WGRAD_GROUP");   // read per call (A/B timing, the bit-equality tests of the schedules)
-  const bool on = !(e && atoi(e) == 0);
-  // Pixel ranges per job inside a group: 1 / WG_DIV of what the job would use ALONE.  Measured in the step (profiles/r06_history.md
-  // section 7): filling the chip as a group makes blocks that own a CU for ~150 us and hold up the step stream's latency-bound chain
-  // (+2 ms); the jobs' own ranges only save launches and reduces (-0.3 ms); a quarter of them is the optimum (-0.5 ... -0.75 ms):
-  // blocks four times as long, a quarter of the slab traffic, still short
-  // (WG_DIV_PL: the plane-fed jobs' divisor.  The three-tap form has a third of the tiles and three times the ranges of the one-tap
-  // form at equal block duration; swept again in the step with it, 2 / 4 / 8 are not separable: profiles/wgrad_kw3_ab.txt)
-  constexpr int WG_DIV = 4, WG_DIV_PL = 4;
-  int kind[WGJ_MAX];
+// -> workspace floats; plan[i] filled.  Each job's kernel and ranges are its route's; what is decided here is about the batch: a
+// shared dw / dbias, a kind with one member, the slabs' places in the workspace
+long wg_plan(const mmt_wgrad_job* jobs, int n, WgJobPlan* plan) {
+  const int mode = precision(), sw = wgrad_switches();   // (read per call: A/B timing, the bit-equality tests of the schedules)
   for (int i = 0; i < n; i++) {
-    ConvP p;
-    kind[i] = 0;
-    if (on && jobs[i].x_planes && jobs[i].dy_planes && wgpl_eligible_splits(&jobs[i].a) > 0) kind[i] = 1;
-    else if (on && wg_job_pipe_ok(jobs[i], p)) kind[i] = 2 + (!(p.Wo >= 8 && p.Ho >= 8) ? 0 : ((p.Wo & 3) == 0 ? 2 : 1));
+    const mmt_wgrad_job& j = jobs[i];
+    WgJobPlan& pl = plan[i];
+    pl.err = fill(pl.p, &j.a);
+    pl.r = WgradRoute{};
+    if (!pl.err)
+      pl.r = wgrad_route(pl.p, mode, (j.x_planes && j.dy_planes ? MMT_WG_HAVE_PLANES : 0) | (j.a.f16_x_amax && j.a.f16_dy_amax ? MMT_WG_HAVE_MAXIMA : 0), sw);
+    pl.kind = j.dy && j.dw ? pl.r.group_kind : 0;
   }
   // a weight shared by several jobs of the batch (the RPN head over the pyramid levels): only its FIRST job may ride in a group -- the
   // items of a group run concurrently and accumulate into dw without atomics; the others follow as single launches, in order
   for (int i = 1; i < n; i++)
     for (int j = 0; j < i; j++)
-      if (jobs[j].dw == jobs[i].dw || (jobs[i].dbias && jobs[j].dbias == jobs[i].dbias)) { kind[i] = 0; break; }
+      if (jobs[j].dw == jobs[i].dw || (jobs[i].dbias && jobs[j].dbias == jobs[i].dbias)) { plan[i].kind = 0; break; }
   // a kind with a single member is a single launch
   for (int k = 1; k <= 4; k++) {
     int cnt = 0, last = -1;
-    for (int i = 0; i < n; i++) if (kind[i] == k) { cnt++; last = i; }
-    if (cnt == 1) kind[last] = 0;
+    for (int i = 0; i < n; i++) if (plan[i].kind == k) { cnt++; last = i; }
+    if (cnt == 1) plan[last].kind = 0;
   }
   long ws = 0;
-  for (int k = 1; k <= 4; k++)
+  for (int k = 1; k <= 5; k++)   // the groups' slabs kind by kind, then the single launches'
     for (int i = 0; i < n; i++) {
-      if (kind[i] != k) continue;
-      const mmt_conv_args& a = jobs[i].a;
-      const int NP = a.KH * a.KW * a.Cin;
       WgJobPlan& pl = plan[i];
-      pl.kind = k; pl.mps = 0;
-      if (k == 1) {
-        long ks = (wgpl_eligible_splits(&a) + WG_DIV_PL - 1) / WG_DIV_PL;
-        const long T = wgpl_super_steps(&a);
-        if (ks > T / 8) ks = T / 8;
-        if (ks < 1) ks = 1;
-        pl.split = (int)ks;
-      } else {
-        const int M = a.N * a.Ho * a.Wo;
-        long sp = (mmt_conv_wgrad_splits(&a) + WG_DIV - 1) / WG_DIV;
-        const long mx = mmt_cdiv(M, 512);
-        if (sp > mx) sp = mx;
-        if (sp < 1) sp = 1;
-        int mps = mmt_cdiv(M, (int)sp);
-        mps = (mps + 31) / 32 * 32;
-        pl.mps = mps;
-        pl.split = mmt_cdiv(M, mps);
-      }
+      if (pl.kind != k % 5) continue;
+      pl.split = pl.kind ? pl.r.group_splits : (pl.r.splits < 1 ? 1 : pl.r.splits);
+      pl.mps = pl.kind ? pl.r.group_mps : pl.r.mps;
       pl.ws_off = ws;
-      if (pl.split > 1) ws += (long)pl.split * a.Cout * NP;
+      if (pl.split > 1) ws += (long)pl.split * jobs[i].a.Cout * jobs[i].a.KH * jobs[i].a.KW * jobs[i].a.Cin;
     }
-  for (int i = 0; i < n; i++) {
-    if (kind[i] != 0) continue;
-    WgJobPlan& pl = plan[i];
-    const mmt_conv_args& a = jobs[i].a;
-    pl.kind = 0; pl.mps = 0;
-    int sp = 0;
-    if (jobs[i].x_planes && jobs[i].dy_planes) sp = wgpl_eligible_splits(&a);
-    if (sp <= 0) sp = mmt_conv_wgrad_splits(&a);
-    pl.split = sp < 1 ? 1 : sp;
-    pl.ws_off = ws;
-    if (pl.split > 1) ws += (long)pl.split * a.Cout * a.KH * a.KW * a.Cin;
-  }
   return ws;
 }
 }  // namespace
@@ -1078,6 +1028,12 @@ extern "C" int mmt_conv_wgrad_group(const mmt_wgrad_job* jobs, int n, float* wor
   hipStream_t s = (hipStream_t)stream;
   WgReduceItem red[WGJ_MAX];
   int nred = 0;
+  auto slab = [&](int i) { return plan[i].split > 1 ? workspace + plan[i].ws_off : nullptr; };
+  auto pl_job = [&](int i) {
+    const mmt_wgrad_job& j = jobs[i];
+    return WgPlJob{&j.a, j.dy, j.x_planes, j.x_plane_stride, j.dy_planes, j.dy_plane_stride, j.s_x, j.s_dy, j.rowscale, j.dw, j.dbias, slab(i),
+                   plan[i].split};
+  };
   // plane-fed groups
   {
     WgPlJob g[WG_CAP_PL];
@@ -1091,11 +1047,9 @@ extern "C" int mmt_conv_wgrad_group(const mmt_wgrad_job* jobs, int n, float* wor
     for (int i = 0; i < n; i++) {
       if (plan[i].kind != 1) continue;
       const mmt_wgrad_job& j = jobs[i];
-      float* ws = plan[i].split > 1 ? workspace + plan[i].ws_off : nullptr;
-      g[m++] = WgPlJob{&j.a, j.dy, j.x_planes, j.x_plane_stride, j.dy_planes, j.dy_plane_stride, j.s_x, j.s_dy, j.rowscale, j.dw, j.dbias, ws,
-                       plan[i].split};
+      g[m++] = pl_job(i);
       if (plan[i].split > 1)
-        red[nred++] = WgReduceItem{ws, j.rowscale, j.dw, plan[i].split, j.a.Cout, j.a.KH * j.a.KW * j.a.Cin, 0};
+        red[nred++] = WgReduceItem{slab(i), j.rowscale, j.dw, plan[i].split, j.a.Cout, j.a.KH * j.a.KW * j.a.Cin, 0};
       if (m == WG_CAP_PL) { const int e = flush(); if (e) return e; }
     }
     const int e = flush();
@@ -1121,12 +1075,12 @@ extern "C" int mmt_conv_wgrad_group(const mmt_wgrad_job* jobs, int n, float* wor
       if (plan[i].kind != 2 + mode) continue;
       const mmt_wgrad_job& j = jobs[i];
       WgPipeItem& it = g.it[g.n];
-      if (!wg_job_pipe_ok(j, it.p) || (plan[i].mps & 15)) return MMT_EINVAL;
+      it.p = plan[i].p;
       it.p.f16_sx = (const float*)j.a.f16_x_amax;
       it.p.f16_sw = (const float*)j.a.f16_dy_amax;
-      const int NP = it.p.KH * it.p.KW * it.p.Cin;
+      const int NP = it.p.K;
       it.dy = j.dy; it.rowscale = j.rowscale; it.dw = j.dw; it.dbias = j.dbias;
-      it.ws = plan[i].split > 1 ? workspace + plan[i].ws_off : nullptr;
+      it.ws = slab(i);
       it.mps = plan[i].mps; it.tx = mmt_cdiv(NP, 128); it.ty = mmt_cdiv(it.p.Cout, 128); it.tz = plan[i].split;
       if (plan[i].split > 1) red[nred++] = WgReduceItem{it.ws, j.rowscale, j.dw, plan[i].split, it.p.Cout, NP, 0};
       g.first[g.n] = nb;
@@ -1142,12 +1096,12 @@ extern "C" int mmt_conv_wgrad_group(const mmt_wgrad_job* jobs, int n, float* wor
   for (int i = 0; i < n; i++) {
     if (plan[i].kind != 0) continue;
     const mmt_wgrad_job& j = jobs[i];
-    float* ws = plan[i].split > 1 ? workspace + plan[i].ws_off : nullptr;
-    int e = 1;
-    if (j.x_planes && j.dy_planes)
-      e = mmt_conv_wgrad_planes(&j.a, j.dy, j.x_planes, j.x_plane_stride, j.dy_planes, j.dy_plane_stride, j.s_x, j.s_dy, j.rowscale, j.dw,
-                                j.dbias, ws, stream);
-    if (e == 1) e = mmt_conv_wgrad(&j.a, j.dy, j.rowscale, j.dw, j.dbias, ws, stream);
+    const WgradRoute& r = plan[i].r;
+    int e = plan[i].err;
+    if (!e)
+      e = r.family == MMT_WGRAD_PLANES_1 || r.family == MMT_WGRAD_PLANES_3
+              ? launch_wgpl_single(pl_job(i), s)
+              : launch_wgrad(&j.a, r, WgCall{plan[i].p, j.dy, j.rowscale, j.dw, j.dbias, slab(i), plan[i].split, plan[i].mps, s});
     if (e) return e;
   }
   return 0;

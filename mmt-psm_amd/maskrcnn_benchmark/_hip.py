@@ -57,6 +57,15 @@ ASSUME_X, ASSUME_W, ASSUME_W_PLANES, ASSUME_X_PLANES, ASSUME_F16_SCALARS = 1, 2,
 ROUTE_NONE, ROUTE_STRIP, ROUTE_PG = 0, 6, 7                                        # ... family (the ones the host side tells apart)
 
 
+class WgradRoute(ctypes.Structure):   # include/mmtpsm.h: mmt_conv_wgrad_route_t
+    _fields_ = ([(n, c_int) for n in ("family", "terms", "decode", "vec4", "bf", "splits", "mps")] + [("ws_floats", ctypes.c_long)] +
+                [(n, c_int) for n in ("lds_bytes", "dbias_in_kernel", "group_kind", "group_splits", "group_mps", "switches")])
+
+
+WG_HAVE_MAXIMA, WG_HAVE_PLANES = 1, 2                  # mmt_conv_wgrad_route: have
+WGRAD_NONE, WGRAD_PLANES_1, WGRAD_PLANES_3 = 0, 6, 7   # ... family (the ones the host side tells apart)
+
+
 class WgradJob(ctypes.Structure):   # include/mmtpsm.h: mmt_wgrad_job
     _fields_ = [("a", ConvArgs), ("dy", c_void_p), ("rowscale", c_void_p), ("dw", c_void_p), ("dbias", c_void_p),
                 ("x_planes", c_void_p), ("x_plane_stride", ctypes.c_long), ("dy_planes", c_void_p), ("dy_plane_stride", ctypes.c_long),
@@ -133,7 +142,7 @@ _SIGS = {
     "mmt_pack_weights_f16": [c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "mmt_pack_weights_flipped_f16": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "mmt_pack_weight_flipped": [c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, c_void_p],
-    "mmt_conv_wgrad_splits": [ctypes.POINTER(ConvArgs)],
+    "mmt_conv_wgrad_route": [ctypes.POINTER(ConvArgs), c_int, ctypes.POINTER(WgradRoute)],
     "mmt_conv_wgrad": [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "mmt_colsum": [c_void_p, c_int, c_int, c_void_p, c_void_p],
     "mmt_weight_flip_transpose": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
@@ -166,7 +175,6 @@ _SIGS = {
     "mmt_sum_stats_rb": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_void_p,
                          c_void_p, c_void_p],
     "mmt_rb_scales_update": [c_void_p, c_int, c_void_p],
-    "mmt_conv_wgrad_planes_splits": [ctypes.POINTER(ConvArgs)],
     "mmt_conv_wgrad_planes": [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, ctypes.c_long, c_void_p, ctypes.c_long, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "mmt_pack_weight_f16": [c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
@@ -598,8 +606,9 @@ def f16_split(x, site=None):
     return xp, st
 
 
-WG_PLANES = os.environ.get("MMT_WGRAD_PLANES", "1") != "0"   # weight gradients of 3x3 layers from the row-blocked planes of both operands
-_WPLAN_PL = {}
+# weight gradients from the row-blocked planes of both operands.  A test hook (MMT_WGRAD_PLANES=0 at import): off, the planes are not
+# OFFERED to the weight gradient's route; whether an offered layer runs plane-fed is the route's answer (mmt_conv_wgrad_route)
+WG_PLANES = os.environ.get("MMT_WGRAD_PLANES", "1") != "0"
 PG_RB = os.environ.get("MMT_PG_RB", "1") != "0"   # input planes of the plane-fed and tap-strip kernels in the row-blocked order (A/B timing: 0)
 
 
@@ -900,7 +909,7 @@ def _lib_raw():
 # on: ~70 ctypes calls instead of the Python that derives them (a manual graph: hipGraph replays of the two models serialise in
 # this runtime).  Only the input's address is patched.  Queries are not recorded.
 _NO_RECORD = frozenset(("mmt_polygon_mask_words_workspace", "mmt_conv_route", "mmt_conv_switches", "mmt_conv_wgrad_group_workspace",
-                        "mmt_conv_wgrad_splits", "mmt_get_conv_precision", "mmt_packed_weight_elems", "mmt_set_conv_precision", "mmt_set_deterministic", "mmt_get_deterministic",
+                        "mmt_conv_wgrad_route", "mmt_get_conv_precision", "mmt_packed_weight_elems", "mmt_set_conv_precision", "mmt_set_deterministic", "mmt_get_deterministic",
                         "mmt_stem_wgrad_ws_floats", "mmt_ciam_norm_lds_bytes", "mmt_ciam_norm_saved_floats", "mmt_ciam_norm_ws_floats"))
 LAYOUT_EPOCH = [0]    # bumped when a flat model (re)allocates its plane buffers (engine/flat.py)
 LAUNCH_PLANS = os.environ.get("MMT_LAUNCH_PLANS", "1") != "0"
@@ -1802,7 +1811,7 @@ def planes_of(x):
 # unusual (profiling, bf16 storage, explicit planes / outputs, a site that fell back to the 3-term bf16 split) takes the
 # general path below; a plan is tied to the weight OBJECT (addresses are re-used) and to the mode epoch.
 _PLAN = {}
-_WPLAN = {}   # weight gradient: (shapes, stride, pad, dtypes) -> (shape half of mmt_conv_args, split count)
+_WPLAN = {}   # weight gradient: (shapes, stride, pad, dtypes, what the caller holds, arithmetic, switch mask) -> (shape half of mmt_conv_args, route)
 _PLAN_EPOCH = [0]
 FAST_PLANS = True
 # the path of a convolution call: the library's own dispatch (fp32 MFMA, bf16, the bf16 splits), or the two-term fp16 split on the
@@ -2402,12 +2411,12 @@ def wgrad_prepare(x, dy):
         _amax_of(nhwc(dy))
 
 
-def _wgrad_stats(x, dy, dw, passes):
+def _wgrad_stats(x, dy, dw):
     """the recorded statistics (slot, version) of both operands of a weight gradient on the two-term fp16 split (3 products instead of
-    6), or None: not eligible -- an operand nobody recorded a maximum of (`passes`: big operands, where the saving pays for it, take a
+    6), or None: not eligible -- an operand nobody recorded a maximum of (big operands, where the saving pays for it, take a
     reduction pass here), or a site whose range defeats fp16 (lagged crest-factor test)"""
     ax, ad = _recorded(x), _recorded(dy)
-    if passes and x.numel() >= WGRAD_F16_MIN_ELEMS:
+    if x.numel() >= WGRAD_F16_MIN_ELEMS:
         if ax is None:
             ax = _amax_of(x)
         if ad is None:
@@ -2417,54 +2426,89 @@ def _wgrad_stats(x, dy, dw, passes):
     return ax, ad
 
 
-def _wgrad_planes(x, dy, st=None):
+def _wgrad_planes(x, dy, st):
     """the row-blocked fp16 planes both operands carry for the whole batch -> (x's record, dy's record, lag bits), or None.  Planes a
-    producer's epilogue wrote carry a scale fixed beforehand: the kernel's guard tests it (bit 0: x, bit 1: dy), so with the operands'
-    statistics `st` at hand both guards must be there"""
+    producer's epilogue wrote carry a scale fixed beforehand: the kernel's guard tests it (bit 0: x, bit 1: dy), so both guards of the
+    operands' statistics `st` must be there"""
     xr, dr = _rb_of(x), _rb_of(dy)
     if xr is None or dr is None or xr[4] is not None or dr[4] is not None:
         return None
     lag = (1 if xr[3] == "epi" else 0) | (2 if dr[3] == "epi" else 0)
-    if st is not None and lag and (_guard(st[0]) is None or _guard(st[1]) is None):
+    if lag and (_guard(st[0]) is None or _guard(st[1]) is None):
         return None
     return xr, dr, lag
 
 
-def _conv_wgrad_planes(x, dy, w_shape, stride, pad, dw, rowscale, dbias):
-    """the weight gradient from the row-blocked fp16 planes both operands already have (include/mmtpsm.h: mmt_conv_wgrad_planes;
-    csrc/conv_wgpl.hip) -> False when the operands have none, or no recorded maxima, or the library does not take the layer"""
-    pl = _wgrad_planes(x, dy)
-    if pl is None:
-        return False
-    Cout, Cin, KH, KW = w_shape
-    key = (x.shape, dy.shape, w_shape, stride, pad)
-    plan = _WPLAN_PL.get(key)
+def _wgrad_job(x, dy, w_shape, stride, pad, dw, rowscale, dbias, sw):
+    """THE preparation of a weight gradient (x, dy dense NHWC; sw: mmt_conv_switches() of this call or batch) -> (j, r, f16, alive):
+    j the filled mmt_wgrad_job (argument block, statistics and guards, the planes when both operands carry them for the whole batch,
+    with the lag bits), r its route as a launch of its own, f16: on the two-term fp16 split (the arithmetic the grouped launches
+    take), alive: the plane tensors j points to.
+    Both operands' maxima make it an fp16-split job (big operands nobody recorded take their reduction pass here); row-blocked
+    planes of both are offered to the route on top (whoever attaches _mmt_rb has recorded _mmt_amax at the same version -- sum_stats,
+    f16_split_pg, _conv_f16, carry --, so planes never exist without maxima and asking for the maxima first costs no pass).
+    Cout % 4 != 0: no kernel of the fp16 split takes the layer, and no pass is spent on it."""
+    st = pl = None
+    if F16X2 and _PREC == 3 and x.dtype == torch.float32 and dy.dtype == torch.float32 and w_shape[0] % 4 == 0:
+        st = _wgrad_stats(x, dy, dw)
+        if st is not None and WG_PLANES:
+            pl = _wgrad_planes(x, dy, st)
+    have = (WG_HAVE_MAXIMA if st is not None else 0) | (WG_HAVE_PLANES if pl is not None else 0)
+    # the shape half of the job and its route depend on these only: kept after the first call
+    key = (x.shape, dy.shape, w_shape, stride, pad, x.dtype, dy.dtype, have, _PREC, sw)
+    plan = _WPLAN.get(key)
     if plan is None:
-        a = _conv_shape(ConvArgs(), x.shape[0], x.shape[2], x.shape[3], Cin, Cout, KH, KW, stride, pad, dy.shape[2], dy.shape[3])
-        splits = lib().mmt_conv_wgrad_planes_splits(ctypes.byref(a))
-        if len(_WPLAN_PL) > 4096:
-            _WPLAN_PL.clear()
-        plan = _WPLAN_PL[key] = (bytes(a), splits)
-    splits = plan[1]
-    if splits <= 0:
-        return False
-    st = _wgrad_stats(x, dy, dw, False)
-    xr, dr, lag = pl
-    if st is None or (lag and (_guard(st[0]) is None or _guard(st[1]) is None)):
-        return False
-    a = ConvArgs.from_buffer_copy(plan[0])
+        Cout, Cin, KH, KW = w_shape
+        j = WgradJob()
+        _conv_shape(j.a, x.shape[0], x.shape[2], x.shape[3], Cin, Cout, KH, KW, stride, pad, dy.shape[2], dy.shape[3])
+        j.a.io_bf16 = (IO_X if x.dtype == torch.bfloat16 else 0) | (IO_DY if dy.dtype == torch.bfloat16 else 0)
+        r = WgradRoute()
+        if lib().mmt_conv_wgrad_route(ctypes.byref(j.a), have, ctypes.byref(r)) != 0:
+            r = WgradRoute(splits=1)   # (a block the library refuses: the launch reports it)
+        if len(_WPLAN) > 4096:
+            _WPLAN.clear()
+        plan = _WPLAN[key] = (bytes(j), r)
+    j = WgradJob.from_buffer_copy(plan[0])
+    a = j.a
     a.x = x.data_ptr()
-    a.f16_guard_x, a.f16_guard_dy, a.x_planes_lag = _guard(st[0]), _guard(st[1]), lag
-    ws = torch.empty((splits * Cout * KH * KW * Cin,), dtype=torch.float32, device=x.device) if splits > 1 else None
-    _TLS.last_ws = ws
-    rc = lib().mmt_conv_wgrad_planes(ctypes.byref(a), dy.data_ptr(), xr[0].data_ptr(), xr[0].stride(0), dr[0].data_ptr(), dr[0].stride(0),
-                                     xr[1].data_ptr(), dr[1].data_ptr(), _p(rowscale), _p(dw), _p(dbias), _p(ws), _stream())
-    if rc == 1:
-        _TLS.last_ws = None
-        return False
-    _check(rc, "mmt_conv_wgrad_planes")
-    F16_STATS["wgrad_pl"] = F16_STATS.get("wgrad_pl", 0) + 1
-    return True
+    j.dy, j.rowscale, j.dw, j.dbias = dy.data_ptr(), _p(rowscale), dw.data_ptr(), _p(dbias)
+    if st is not None:
+        a.f16_x_amax, a.f16_dy_amax = st[0][0].data_ptr(), st[1][0].data_ptr()
+        a.f16_guard_x, a.f16_guard_dy = _guard(st[0]), _guard(st[1])
+    if pl is None:
+        return j, plan[1], st is not None, ()
+    xr, dr, a.x_planes_lag = pl
+    j.x_planes, j.x_plane_stride = xr[0].data_ptr(), xr[0].stride(0)
+    j.dy_planes, j.dy_plane_stride = dr[0].data_ptr(), dr[0].stride(0)
+    j.s_x, j.s_dy = xr[1].data_ptr(), dr[1].data_ptr()
+    return j, plan[1], True, (xr[0], dr[0])
+
+
+def _wgrad_launch(j, r, f16, device):
+    """a prepared weight gradient as a launch of its own, on the kernel its route names -> the split-K workspace it allocated (the
+    caller keeps it alive or records the side stream) or None"""
+    ws = torch.empty((r.ws_floats,), dtype=torch.float32, device=device) if r.ws_floats > 0 else None
+    if r.family in (WGRAD_PLANES_1, WGRAD_PLANES_3):
+        _check(lib().mmt_conv_wgrad_planes(ctypes.byref(j.a), j.dy, j.x_planes, j.x_plane_stride, j.dy_planes, j.dy_plane_stride, j.s_x, j.s_dy,
+                                           j.rowscale, j.dw, j.dbias, _p(ws), _stream()), "mmt_conv_wgrad_planes")
+        F16_STATS["wgrad_pl"] = F16_STATS.get("wgrad_pl", 0) + 1
+        return ws
+    if f16:   # both operands carry their recorded maximum: two-term fp16 split
+        F16_STATS["wgrad"] += 1
+    e0 = _ev() if PROFILE is not None and PROFILE_ALL else None
+    _check(lib().mmt_conv_wgrad(ctypes.byref(j.a), j.dy, j.rowscale, j.dw, j.dbias, _p(ws), _stream()), "mmt_conv_wgrad")
+    if e0 is not None:
+        _profiled(j.a, e0, "wgrad", r.splits, None, 0)
+    return ws
+
+
+def _hand_over(ws, side, keep):
+    """a workspace a side-stream launch reads: kept by the caller until it has joined the stream, or recorded on the stream"""
+    if ws is not None:
+        if keep is not None:
+            keep.append(ws)
+        else:
+            ws.record_stream(side)
 
 
 def conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale=None, dbias=None, side=None, keep=None):
@@ -2474,59 +2518,32 @@ def conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale=None, dbias=None, side=
     the caller until it has joined the side stream."""
     if side is not None:
         _TLS.stream = side.cuda_stream
+        ws = None
         try:
-            return conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale, dbias)
+            ws = _conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale, dbias)
         finally:
             _TLS.stream = None
-            ws = getattr(_TLS, "last_ws", None)
-            if ws is not None:
-                if keep is not None:
-                    keep.append(ws)
-                else:
-                    ws.record_stream(side)
-                _TLS.last_ws = None
+            _hand_over(ws, side, keep)
             _drain_det_ws(side, keep)
+    else:
+        _conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale, dbias)
+
+
+def _conv_wgrad(x, dy, w_shape, stride, pad, dw, rowscale, dbias):
+    """conv_wgrad on the stream in force -> the split-K workspace the launch reads, or None"""
     x = nhwc(x)
     dy = nhwc(dy)
-    Cout, Cin, KH, KW = w_shape
     bias_to = None
     if _DET and dbias is not None:
         if dy.dtype != torch.float32:
             raise NotImplementedError("deterministic mode: the ordered bias gradient reads fp32 gradients")
         bias_to, dbias = dbias, None   # the weight-gradient kernels' bias epilogues use float atomics: an ordered column sum instead
-    f16 = F16X2 and x.dtype == torch.float32 and dy.dtype == torch.float32 and get_conv_precision() == 3
-    if f16 and WG_PLANES and _conv_wgrad_planes(x, dy, w_shape, stride, pad, dw, rowscale, dbias):
-        if bias_to is not None:
-            _bias_ordered(dy, bias_to)
-        return
-    # the shape half of the argument block and the split count depend on the shapes only: kept after the first call
-    key = (x.shape, dy.shape, w_shape, stride, pad, x.dtype, dy.dtype)
-    plan = _WPLAN.get(key)
-    if plan is None:
-        a = _conv_shape(ConvArgs(), x.shape[0], x.shape[2], x.shape[3], Cin, Cout, KH, KW, stride, pad, dy.shape[2], dy.shape[3])
-        a.io_bf16 = (IO_X if x.dtype == torch.bfloat16 else 0) | (IO_DY if dy.dtype == torch.bfloat16 else 0)
-        a.x = x.data_ptr()
-        splits = lib().mmt_conv_wgrad_splits(ctypes.byref(a))
-        a.x = None
-        if len(_WPLAN) > 4096:
-            _WPLAN.clear()
-        plan = _WPLAN[key] = (bytes(a), splits)
-    a, splits = ConvArgs.from_buffer_copy(plan[0]), plan[1]
-    a.x = x.data_ptr()
-    st = _wgrad_stats(x, dy, dw, True) if f16 and Cout % 4 == 0 else None
-    if st is not None:
-        # both operands carry their recorded maximum: two-term fp16 split
-        a.f16_x_amax, a.f16_dy_amax = st[0][0].data_ptr(), st[1][0].data_ptr()
-        a.f16_guard_x, a.f16_guard_dy = _guard(st[0]), _guard(st[1])
-        F16_STATS["wgrad"] += 1
-    ws = torch.empty((splits * Cout * KH * KW * Cin,), dtype=torch.float32, device=x.device) if splits > 1 else None
-    _TLS.last_ws = ws
-    e0 = _ev() if PROFILE is not None and PROFILE_ALL else None
-    _check(lib().mmt_conv_wgrad(ctypes.byref(a), _p(dy), _p(rowscale), _p(dw), _p(dbias), _p(ws), _stream()), "mmt_conv_wgrad")
-    if e0 is not None:
-        _profiled(a, e0, "wgrad", splits, None, 0)
+    get_conv_precision()
+    j, r, f16, _ = _wgrad_job(x, dy, w_shape, stride, pad, dw, rowscale, dbias, lib().mmt_conv_switches())
+    ws = _wgrad_launch(j, r, f16, x.device)
     if bias_to is not None:
         _bias_ordered(dy, bias_to)
+    return ws
 
 
 def _bias_ordered(dy, out):
@@ -2554,10 +2571,7 @@ def _drain_det_ws(side, keep):
     kept = getattr(_TLS, "det_ws", None)
     if kept:
         for ws in kept:
-            if keep is not None:
-                keep.append(ws)
-            else:
-                ws.record_stream(side)
+            _hand_over(ws, side, keep)
         kept.clear()
 
 
@@ -2566,60 +2580,48 @@ def _drain_det_ws(side, keep):
 WGRAD_GROUP = os.environ.get("MMT_WGRAD_GROUP", "1") != "0"
 
 
-def _wgrad_group_job(x, dy, w_shape, stride, pad, dw, rowscale, dbias, keep):
-    """-> a filled WgradJob for mmt_conv_wgrad_group, or None when the job must go out through conv_wgrad (another arithmetic, bf16
-    storage, an operand without a recorded maximum, a site on the bf16 fall-back).  The preparation of conv_wgrad, without the launch."""
-    if not (F16X2 and _PREC == 3 and x.dtype == torch.float32 and dy.dtype == torch.float32):
-        return None
-    Cout, Cin, KH, KW = w_shape
-    if Cout % 4 or Cin % 4:
-        return None
-    st = _wgrad_stats(x, dy, dw, True)
-    if st is None:
-        return None
-    j = WgradJob()
-    a = _conv_shape(j.a, x.shape[0], x.shape[2], x.shape[3], Cin, Cout, KH, KW, stride, pad, dy.shape[2], dy.shape[3])
-    a.x = x.data_ptr()
-    a.f16_x_amax, a.f16_dy_amax = st[0][0].data_ptr(), st[1][0].data_ptr()
-    a.f16_guard_x, a.f16_guard_dy = _guard(st[0]), _guard(st[1])
-    j.dy, j.rowscale, j.dw, j.dbias = dy.data_ptr(), _p(rowscale), dw.data_ptr(), _p(dbias)
-    pl = _wgrad_planes(x, dy, st) if WG_PLANES else None
-    if pl is not None:
-        xr, dr, a.x_planes_lag = pl
-        j.x_planes, j.x_plane_stride = xr[0].data_ptr(), xr[0].stride(0)
-        j.dy_planes, j.dy_plane_stride = dr[0].data_ptr(), dr[0].stride(0)
-        j.s_x, j.s_dy = xr[1].data_ptr(), dr[1].data_ptr()
-        keep.extend((xr[0], dr[0]))
-    return j
-
-
 def conv_wgrad_group(jobs, side=None, keep=None):
     """the weight gradients of a batch of layers -- jobs: (x, dy, w_shape, stride, pad, dw, rowscale, dbias) -- through
-    mmt_conv_wgrad_group (include/mmtpsm.h: grouped launches); jobs it does not take go out through conv_wgrad, in order.  `side`,
-    `keep` as in conv_wgrad."""
+    mmt_conv_wgrad_group (include/mmtpsm.h: grouped launches); jobs of another arithmetic (bf16 storage, an operand without a recorded
+    maximum, a site on the bf16 fall-back, a shape no kernel of the fp16 split takes) go out as conv_wgrad launches them, in order.
+    `side`, `keep` as in conv_wgrad.  WGRAD_GROUP off (a test hook; MMT_WGRAD_GROUP=0 at import): nothing is offered to the grouped
+    entry point -- which reads the same variable per call and then launches every job singly."""
+    wss = []   # the launches' workspaces
     if side is not None:
         _TLS.stream = side.cuda_stream
-        try:
-            return conv_wgrad_group(jobs, None, keep)
-        finally:
+    try:
+        _conv_wgrad_group(jobs, keep if keep is not None else [], wss)
+    finally:
+        if side is not None:
             _TLS.stream = None
+            for ws in wss:
+                _hand_over(ws, side, keep)
             _drain_det_ws(side, keep)
-    keep_ = keep if keep is not None else []
+        elif keep is not None:
+            keep.extend(wss)
+        # (on the current stream without `keep`: the caching allocator orders the buffers' reuse behind the launches)
+
+
+def _conv_wgrad_group(jobs, keep, wss):
+    """conv_wgrad_group on the stream in force.  keep: a list for the operands and planes the grouped launches read; wss: a list
+    for the workspaces allocated here"""
+    get_conv_precision()
     grouped, single, biases = [], [], []   # biases: deterministic mode, (dy, dbias) of the grouped jobs -- ordered column sums behind the launches
     if WGRAD_GROUP and not (PROFILE is not None and PROFILE_ALL):
+        sw = lib().mmt_conv_switches()
         for job in jobs:
             x, dy, w_shape, stride, pad, dw, rowscale, dbias = job
             x, dy = nhwc(x), nhwc(dy)
-            wj = _wgrad_group_job(x, dy, w_shape, stride, pad, dw, rowscale, None if _DET else dbias, keep_)
-            if wj is None:
+            j, r, f16, alive = _wgrad_job(x, dy, w_shape, stride, pad, dw, rowscale, None if _DET else dbias, sw)
+            if not f16 or r.family == WGRAD_NONE:
                 single.append(job)
             else:
-                grouped.append(wj)
-                keep_.extend((x, dy))
+                grouped.append(j)
+                keep.extend(alive + (x, dy))
                 if _DET and dbias is not None:
                     biases.append((dy, dbias))
     else:
-        single = list(jobs)
+        single = jobs
     for c0 in range(0, len(grouped), 96):
         chunk = grouped[c0:c0 + 96]
         arr = (WgradJob * len(chunk))(*chunk)
@@ -2631,17 +2633,13 @@ def conv_wgrad_group(jobs, side=None, keep=None):
         _check(lib().mmt_conv_wgrad_group(ctypes.addressof(arr), len(chunk), _p(ws), need, _stream()), "mmt_conv_wgrad_group")
         F16_STATS["wgrad_grouped"] = F16_STATS.get("wgrad_grouped", 0) + len(chunk)
         if ws is not None:
-            if keep is not None:
-                keep.append(ws)
-            # (callers without `keep` launch on the current stream: the caching allocator orders the buffer's reuse behind it)
+            wss.append(ws)
     for dy, dbias in biases:
         _bias_ordered(dy, dbias)
     for job in single:
-        conv_wgrad(*job)
-        ws = getattr(_TLS, "last_ws", None)
-        if ws is not None and keep is not None:
-            keep.append(ws)
-            _TLS.last_ws = None
+        ws = _conv_wgrad(*job)
+        if ws is not None:
+            wss.append(ws)
 
 
 def colsum(dy2d, out):

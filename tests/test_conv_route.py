@@ -29,6 +29,8 @@ sys.path.insert(0, os.path.join(ROOT, "mmt-psm_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import conv_route_cases as C  # noqa: E402
 
+WGRAD_SWITCHES = ("MMT_WGRAD_PLANES", "MMT_WGRAD_GROUP")   # bits 6, 7 of mmt_conv_switches(): tests/test_wgrad_route.py
+
 
 @pytest.fixture()
 def hip():
@@ -36,7 +38,7 @@ def hip():
     L = ctypes.CDLL(H.LIB_PATH)   # (the bare library: no device, no launch)
     L.mmt_conv_route.argtypes = [ctypes.POINTER(H.ConvArgs), ctypes.c_int, ctypes.c_int, ctypes.POINTER(H.ConvRoute)]
     prev = L.mmt_get_conv_precision()
-    old = {k: os.environ.pop(k, None) for k in C.SWITCHES}
+    old = {k: os.environ.pop(k, None) for k in C.SWITCHES + WGRAD_SWITCHES}
     yield H, L
     for k, v in old.items():
         os.environ.pop(k, None)
@@ -61,7 +63,7 @@ def test_routes_answer_what_the_six_queries_answered(hip):
                 os.environ.pop(k, None)
             if C.SWITCH_LEGS[leg] is not None:
                 os.environ[C.SWITCH_LEGS[leg]] = "0"
-            mask = 63 if leg == 0 else 63 & ~(1 << (leg - 1))
+            mask = (63 if leg == 0 else 63 & ~(1 << (leg - 1))) | 192   # (bits 6, 7: the weight gradient's two, left on here)
             assert L.mmt_conv_switches() == mask
             last = (mode, leg)
         a = ctypes.byref(C.fill(H.ConvArgs, case, io_x, filling, False))

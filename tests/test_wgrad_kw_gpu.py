@@ -79,7 +79,9 @@ def _wgrad(H, x, dy, k, dw0=None, rs=None, bias=False):
 
 def _splits(H, x, dy, k):
     a = H._conv_shape(H.ConvArgs(), x.shape[0], x.shape[2], x.shape[3], x.shape[1], dy.shape[1], k, k, 1, k // 2, dy.shape[2], dy.shape[3])
-    return H.lib().mmt_conv_wgrad_planes_splits(ctypes.byref(a))
+    r = H.WgradRoute()
+    assert H.lib().mmt_conv_wgrad_route(ctypes.byref(a), H.WG_HAVE_PLANES, ctypes.byref(r)) == 0
+    return r.splits if r.family in (H.WGRAD_PLANES_1, H.WGRAD_PLANES_3) else 0
 
 
 @pytest.mark.parametrize("row", [0, 1, 2])
