@@ -9,6 +9,7 @@ import gc as _gc
 import weakref
 import os
 import threading as _threading
+from collections import namedtuple as _namedtuple
 
 import torch
 
@@ -301,6 +302,7 @@ F16_CREST_HI, F16_CREST_LO = 2.0 ** 17, 2.0 ** 15
 
 class _StatPool(object):
     __slots__ = ("dev", "host", "event", "next", "gen", "host_gen", "base")
+    travels = True   # its statistics reach the host (retire); a pool of slots says so, _site_ok queues a slot only where they do
 
     def __init__(self, device):
         self.dev = torch.zeros((_POOL_SLOTS, STAT_W), dtype=torch.float32, device=device)
@@ -328,8 +330,8 @@ _SITES = {}       # consuming site -> [fp16 split allowed, pending (pool, genera
 
 
 class _Slot(object):
-    """one zeroed statistics slot of a pool: what a launch is handed as y_amax and what `tensor._mmt_amax[0]` holds (anything
-    with a data_ptr() works there: tests attach plain one-element tensors)"""
+    """one zeroed statistics slot of a pool (a _StatPool or a launch plan: `base`, `gen`, `travels`): what a launch is handed as y_amax
+    and what `tensor._mmt_amax[0]` holds (anything with a data_ptr() works there: tests attach plain one-element tensors)"""
     __slots__ = ("ptr", "pool", "gen", "idx")
 
     def __init__(self, pool, idx):
@@ -380,56 +382,92 @@ def f16_flush_stats():
 
 # ---- what a producer leaves on a tensor object (plain attributes; each carries the tensor's version counter at the time and is
 # void once the tensor has been modified):
-#   _mmt_amax   (statistics slot -- anything with a data_ptr() --, version)
-#   _mmt_rb     (row-blocked fp16 planes, device view of their scale, version, "epi" | "split", images covered or None = all)
-#   _mmt_planes (bf16 planes of the 3-term split, version)
+#   _mmt_amax   (statistics slot -- anything with a data_ptr() --, version)           written by _record,        read by _recorded
+#   _mmt_rb     _Rb(row-blocked fp16 planes, device view of their scale, version,     written by _rb_attach,     read by _rb_of
+#                   "epi" | "split", images covered or None = all)
+#   _mmt_planes (bf16 planes of the 3-term split, version)                            written by _planes_attach, read by planes_of
+# Nobody else in this module assigns them (drop voids all three).  _stat_ptrs turns a statistics record into the addresses a launch
+# is handed, _full_slot tells a pool's slot from a bare maximum, _Rb answers what consumers ask of planes (covers, lagged).
+def _record(x, slot):   # attach a statistics slot to x at its current version -> the record
+    am = x._mmt_amax = (slot, x._version)
+    return am
+
+
 def _recorded(x):
     """the current (statistics slot, version) of x, or None"""
     am = getattr(x, "_mmt_amax", None)
     return am if am is not None and am[1] == x._version else None
 
 
+def _full_slot(s):   # a slot of a pool (max, sampled sums and counts), not the bare maximum that tests attach as a one-element tensor?
+    return type(s) is _Slot
+
+
+def _stat_ptrs(am):
+    """what a launch needs of a current statistics record -> (the address of the maximum, the address of the full slot for the
+    kernels' on-device range test or None when only a maximum was recorded)"""
+    return (am[0].ptr, am[0].ptr) if _full_slot(am[0]) else (am[0].data_ptr(), None)
+
+
+class _Rb(_namedtuple("_Rb", "planes scale version kind images")):
+    """kind "epi": written by the epilogue of the launch that produced the tensor, with the site's scale of the step before; "split":
+    by a pass over it.  images: planes for the first n images of the batch only"""
+    __slots__ = ()
+
+    def covers(self, n=None):   # planes for the first n images (None: for the whole batch)?
+        return self.images is None or (n is not None and n <= self.images)
+
+    def lagged(self):   # was the scale fixed before the values existed?  (a consumer's guard then tests it)
+        return self.kind == "epi"
+
+
 def _rb_of(x):
     """the current row-blocked planes record of x, or None"""
     rb = getattr(x, "_mmt_rb", None)
-    return rb if rb is not None and rb[2] == x._version else None
+    return rb if rb is not None and rb.version == x._version else None
 
 
 def _rb_attach(x, planes, scale, kind, images=None):
-    """kind "epi": written by the epilogue of the launch that produced x, with the site's scale of the step before (a consumer's guard
-    tests it: lag); "split": by a pass over x.  images: planes for the first n images of the batch only"""
-    x._mmt_rb = (planes, scale, x._version, kind, images)
+    x._mmt_rb = tuple.__new__(_Rb, (planes, scale, x._version, kind, images))   # (_Rb(...) without the generated __new__: per launch)
+
+
+def _planes_attach(x, planes):
+    x._mmt_planes = (planes, x._version)
+
+
+def planes_of(x):
+    """the bf16 planes a producing convolution attached to this very tensor object (still valid: not modified since)"""
+    t = getattr(x, "_mmt_planes", None)
+    return t[0] if t is not None and t[1] == x._version and t[0].shape[1] == x.numel() else None
 
 
 def carry(src, dst, rb=True, planes=True, images=None):
     """dst holds the same values as src (a view, an alias) or, images=(lo, hi), is that batch slice of it: what the producer of src
     left on it goes along -- the statistics always (a maximum over more elements is an upper bound: all the fp16 split's scale
     needs), the planes unless switched off (a reshaped or subsampled tensor has another plane order)"""
-    am = _recorded(src)
-    if am is not None:
-        dst._mmt_amax = (am[0], dst._version)
+    carry_stats(src, dst)
     if planes:
         pl = planes_of(src)
         if pl is not None:
             if images is not None:
                 per = src.numel() // src.shape[0]
                 pl = pl[:, images[0] * per:images[1] * per]
-            dst._mmt_planes = (pl, dst._version)
+            _planes_attach(dst, pl)
     if rb:
         r = _rb_of(src)
         if r is not None:
             if images is None:
-                _rb_attach(dst, r[0], r[1], r[3], r[4])
-            elif r[4] is None or images[1] <= r[4]:   # (image-major planes: a batch slice is a slice, also inside planes of the leading images)
+                _rb_attach(dst, r.planes, r.scale, r.kind, r.images)
+            elif r.covers(images[1]):   # (image-major planes: a batch slice is a slice, also inside planes of the leading images)
                 per = src.numel() // src.shape[0]
-                _rb_attach(dst, r[0][:, images[0] * per:images[1] * per], r[1], r[3])
+                _rb_attach(dst, r.planes[:, images[0] * per:images[1] * per], r.scale, r.kind)
 
 
 def carry_stats(src, dst):
     """the statistics alone: dst is a reshaped view of src, or holds a subset / the window maxima of its non-negative values"""
-    am = getattr(src, "_mmt_amax", None)
-    if am is not None and am[1] == src._version:
-        dst._mmt_amax = (am[0], dst._version)
+    am = _recorded(src)
+    if am is not None:
+        _record(dst, am[0])
 
 
 def drop(x):
@@ -468,18 +506,12 @@ def _site_ok(site, x, count=True):
             ent[1] = None    # overwritten before anybody looked
     if ent[1] is None:
         am = _recorded(x)
-        if am is not None and type(am[0]) is _Slot and type(am[0].pool) is _StatPool:
+        if am is not None and _full_slot(am[0]) and am[0].pool.travels:
             ent[1] = am[0]   # (a launch plan's slots never travel to the host: they would sit here for ever and switch the lagged
                              # test off for the site -- replayed passes rely on the kernels' device-side guard alone)
     if not ent[0] and count:
         F16_STATS["fallback"] = F16_STATS.get("fallback", 0) + 1
     return ent[0]
-
-
-def _guard(am):
-    """the address of a full statistics slot (max, sampled sums and counts) for the kernels' on-device range test, or None when
-    only a maximum was recorded (tests attach plain one-element tensors)"""
-    return am[0].ptr if type(am[0]) is _Slot else None
 
 
 def _amax_of(x):
@@ -497,7 +529,7 @@ def _amax_of(x):
             AMAX_LOG.append((tuple(x.shape), " < ".join(chain)))
         slot = _amax_slot(x.device)
         _check(lib().mmt_amax_stats(x.data_ptr(), x.numel(), slot.ptr, _stream()), "mmt_amax_stats")
-        am = x._mmt_amax = (slot, x._version)
+        am = _record(x, slot)
     return am
 
 
@@ -508,7 +540,7 @@ def stats_of_convex_combination(out, sources):
     slots = []
     for t in sources:
         am = _recorded(t)
-        if am is None or type(am[0]) is not _Slot:
+        if am is None or not _full_slot(am[0]):
             return
         slots.append(am[0].ptr)
     if not slots or len(slots) > 8:
@@ -516,7 +548,7 @@ def stats_of_convex_combination(out, sources):
     arr = (c_void_p * len(slots))(*slots)
     slot = _amax_slot(out.device)
     _check(lib().mmt_stats_combine(arr, len(slots), slot.ptr, _stream()), "mmt_stats_combine")
-    out._mmt_amax = (slot, out._version)
+    _record(out, slot)
 
 
 def sum_stats(ts, rb_site=None):
@@ -541,26 +573,20 @@ def sum_stats(ts, rb_site=None):
     p = [t.data_ptr() for t in ts] + [None] * (4 - len(ts))
     if (rb_site is not None and RB_EPI and PG_RB and a.dim() == 4 and a.shape[1] % 16 == 0 and n < (1 << 30)
             and a.is_contiguous(memory_format=torch.channels_last)):
-        t, i = _rb_site(rb_site, a.device)
-        if t is not None:
-            t.produced.add(i)
-            nxt = t.base + 8 * i + 4
-            if i in t.ready:
-                N, C, Hh, W = a.shape
-                pl = torch.empty((2, n), dtype=torch.float16, device=a.device)
-                _check(lib().mmt_sum_stats_rb(p[0], p[1], p[2], p[3], y.data_ptr(), N * Hh, W, C, slot.ptr, pl.data_ptr(), n,
-                                              t.base + 8 * i, nxt, _stream()), "mmt_sum_stats_rb")
-                y._mmt_amax = (slot, y._version)
-                _rb_attach(y, pl, _rb_scale_view(t, i), "epi")
-                return y
-            # no scale yet: the sum alone (planes NULL); its maximum becomes the site's first pending maximum
+        s = _rb_site(rb_site, a.device)
+        if s is not None:
+            nxt = s.produce()
             N, C, Hh, W = a.shape
-            _check(lib().mmt_sum_stats_rb(p[0], p[1], p[2], p[3], y.data_ptr(), N * Hh, W, C, slot.ptr, None, 0, t.base + 8 * i, nxt,
-                                          _stream()), "mmt_sum_stats_rb")
-            y._mmt_amax = (slot, y._version)
+            # no scale yet: the sum alone (planes NULL); its maximum becomes the site's first pending maximum
+            pl = torch.empty((2, n), dtype=torch.float16, device=a.device) if s.ready else None
+            _check(lib().mmt_sum_stats_rb(p[0], p[1], p[2], p[3], y.data_ptr(), N * Hh, W, C, slot.ptr, _p(pl), 0 if pl is None else n,
+                                          s.scale, nxt, _stream()), "mmt_sum_stats_rb")
+            _record(y, slot)
+            if pl is not None:
+                _rb_attach(y, pl, s.scale_view, "epi")
             return y
     _check(lib().mmt_sum_stats(p[0], p[1], p[2], p[3], y.data_ptr(), n, slot.ptr, _stream()), "mmt_sum_stats")
-    y._mmt_amax = (slot, y._version)
+    _record(y, slot)
     return y
 
 
@@ -577,19 +603,15 @@ def f16_split(x, site=None):
     n = x.numel()
     xp = torch.empty((2, n), dtype=torch.float16, device=x.device)
     am = _recorded(x)
-    if am is not None:
-        # the convolution that produced x recorded max |x| in its epilogue (mmt_conv_args.y_amax): the split pass alone
-        st = torch.empty((1,), dtype=torch.float32, device=x.device)
-        _check(lib().mmt_split_planes_f16(x.data_ptr(), xp.data_ptr(), xp.stride(0), n, 1.0, am[0].data_ptr(), st.data_ptr(),
-                                          None, None, _stream()), "mmt_split_planes_f16")
-        return xp, st
-    ent = _F16SITE.get(site) if site is not None else None
-    if ent is None and site is None:
+    if am is None and site is None:
         am = _amax_of(x)   # one reduction pass; other consumers of this tensor (its weight gradient) then need none of their own
+    if am is not None:
+        # (recorded: the convolution that produced x left max |x| from its epilogue, mmt_conv_args.y_amax) the split pass alone
         st = torch.empty((1,), dtype=torch.float32, device=x.device)
-        _check(lib().mmt_split_planes_f16(x.data_ptr(), xp.data_ptr(), xp.stride(0), n, 1.0, am[0].data_ptr(), st.data_ptr(),
+        _check(lib().mmt_split_planes_f16(x.data_ptr(), xp.data_ptr(), xp.stride(0), n, 1.0, _stat_ptrs(am)[0], st.data_ptr(),
                                           None, None, _stream()), "mmt_split_planes_f16")
         return xp, st
+    ent = _F16SITE.get(site)
     if ent is None:
         F16_STATS["amax_pass"] += 1
         st = torch.zeros((4,), dtype=torch.float32, device=x.device)
@@ -629,39 +651,47 @@ _RB_EPOCH = [0]     # bumped when a site becomes ready (launch plans recorded be
 
 
 class _RbTable(object):
-    __slots__ = ("state", "base", "index", "ready", "produced", "views", "ok")
+    __slots__ = ("state", "base", "sites")
 
     def __init__(self, device):
         self.state = torch.zeros((_RB_MAX, 2), dtype=torch.float32, device=device)   # [site] = (scale, pending max |y| of this step)
         self.state[:, 0] = 1.0
-        self.base = self.state.data_ptr()
-        self.index, self.ready, self.produced, self.views, self.ok = {}, set(), set(), {}, {}
+        # base: what mmt_rb_scales_update folds, with the number of sites; sites: key -> _RbSite, in the order of their rows
+        self.base, self.sites = self.state.data_ptr(), {}
+
+
+# one producing site: its row of the table.  THE place that knows the row's layout (include/mmtpsm.h: mmt_rb_scales_update)
+class _RbSite(object):
+    __slots__ = ("index", "state", "scale_view", "scale", "pending", "produced", "ready", "ok")
+
+    def __init__(self, table, index):
+        self.index = index
+        self.state = table.state[index]       # device view of both words: [0] the scale, [1] the pending max |y| of this step
+        self.scale_view = self.state[0:1]     # (what the planes records of tensors carry)
+        self.scale = table.base + 8 * index   # their addresses, as launches are handed them
+        self.pending = self.scale + 4
+        # produced: a launch of this step recorded a maximum here; ready: has a scale (from the rb_scales_update after the step that
+        # produced here first); ok (_rb_produce): launch shape -> does the kernel it takes write planes?
+        self.produced, self.ready, self.ok = False, False, {}
+
+    def produce(self):   # a launch of this step records max |y| here -> the address it records it at
+        self.produced = True
+        return self.pending
 
 
 def _rb_site(key, device):
-    """-> (table, index) of the producing site `key` (a weight's address and role); (None, -1): table full"""
+    """-> the _RbSite of the producing site `key` (a weight's address and role), the same object every time; None: table full"""
     t = _RB.get(device.index)
-    if t is None:
-        with _RB_LOCK:
+    s = t.sites.get(key) if t is not None else None
+    if s is None:
+        with _RB_LOCK:   # (asked again under the lock: the teacher's thread creates tables and sites too)
             t = _RB.get(device.index)
             if t is None:
                 t = _RB[device.index] = _RbTable(device)
-    i = t.index.get(key)
-    if i is None:
-        with _RB_LOCK:
-            i = t.index.get(key)
-            if i is None:
-                if len(t.index) >= _RB_MAX:
-                    return None, -1
-                i = t.index[key] = len(t.index)
-    return t, i
-
-
-def _rb_scale_view(t, i):
-    v = t.views.get(i)
-    if v is None:
-        v = t.views[i] = t.state[i, 0:1]
-    return v
+            s = t.sites.get(key)
+            if s is None and len(t.sites) < _RB_MAX:
+                s = t.sites[key] = _RbSite(t, len(t.sites))
+    return s
 
 
 class RbLead(int):
@@ -678,24 +708,23 @@ def _rb_produce(a, y, key):
     if type(key[-1]) is RbLead:
         images = int(key[-1]) if 0 < int(key[-1]) < y.shape[0] else None
         key = key[:-1]
-    t, i = _rb_site(key, y.device)
-    if t is None:
+    s = _rb_site(key, y.device)
+    if s is None:
         return None
-    a.y_amax_next = t.base + 8 * i + 4
-    t.produced.add(i)
-    if i not in t.ready:
+    a.y_amax_next = s.produce()
+    if not s.ready:
         return None
-    okk = (i, a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.stride, a.res_mode, a.mask is not None)
-    ok = t.ok.get(okk)
+    okk = (a.N, a.H, a.W, a.Cin, a.Cout, a.KH, a.stride, a.res_mode, a.mask is not None)
+    ok = s.ok.get(okk)
     if ok is None:
-        ok = t.ok[okk] = conv_route(a, ENTRY_F16, ASSUME_F16_SCALARS).writes_rb == 1
+        ok = s.ok[okk] = conv_route(a, ENTRY_F16, ASSUME_F16_SCALARS).writes_rb == 1
     if not ok:
         return None
     n = y.numel() if images is None else (y.numel() // y.shape[0]) * images
     pl = torch.empty((2, n), dtype=torch.float16, device=y.device)
-    a.y_rb, a.y_rb_stride, a.y_rb_scale = pl.data_ptr(), n, t.base + 8 * i
+    a.y_rb, a.y_rb_stride, a.y_rb_scale = pl.data_ptr(), n, s.scale
     a.y_rb_rows = 0 if images is None else images * y.shape[2] * y.shape[3]
-    return pl, _rb_scale_view(t, i), images
+    return pl, s.scale_view, images
 
 
 def rb_scales_update():
@@ -703,15 +732,14 @@ def rb_scales_update():
     maxima become their scales for the next step (include/mmtpsm.h: mmt_rb_scales_update); sites that produced for the first time
     are ready from now on"""
     for t in list(_RB.values()):
-        n = len(t.index)
-        if n == 0 or not t.produced:
+        produced = [s for s in list(t.sites.values()) if s.produced]
+        if not produced:
             continue
-        _check(lib().mmt_rb_scales_update(t.base, n, _stream()), "mmt_rb_scales_update")
-        new = t.produced - t.ready
-        if new:
-            t.ready |= new
+        _check(lib().mmt_rb_scales_update(t.base, len(t.sites), _stream()), "mmt_rb_scales_update")
+        if not all(s.ready for s in produced):
             _RB_EPOCH[0] += 1
-        t.produced = set()
+        for s in produced:
+            s.produced, s.ready = False, True
 
 
 def rb_reset():
@@ -731,9 +759,9 @@ def f16_split_pg(x):
         xp, st = f16_split(x)
         return xp, st, 0, 0
     rb = _rb_of(x)
-    if rb is not None and rb[3] == "epi" and (rb[4] is None or rb[4] >= x.shape[0]):
+    if rb is not None and rb.lagged() and rb.covers(x.shape[0]):
         F16_STATS["rb_epi"] = F16_STATS.get("rb_epi", 0) + 1
-        return rb[0], rb[1], 1, 1
+        return rb.planes, rb.scale, 1, 1
     F16_STATS["rb_split"] = F16_STATS.get("rb_split", 0) + 1
     # (no reuse of planes an earlier consumer left on the tensor: a launch plan's replay rewrites its result tensors in place without
     # touching their version counters -- the teacher's pyramid levels -- and planes made from the previous step's values would pass)
@@ -742,10 +770,10 @@ def f16_split_pg(x):
         # (beyond the row-blocked pass's 32-bit offsets -- planes indexed like x, which the kernels take as layout 0)
         xp, st = f16_split(x)
         return xp, st, 0, 0
-    am = _amax_of(x)
+    amax = _stat_ptrs(_amax_of(x))[0]
     xp = torch.empty((2, x.numel()), dtype=torch.float16, device=x.device)
     st = torch.empty((1,), dtype=torch.float32, device=x.device)
-    _check(lib().mmt_split_planes_f16_rb(x.data_ptr(), xp.data_ptr(), xp.stride(0), N * Hh, W, C, am[0].data_ptr(), st.data_ptr(), _stream()),
+    _check(lib().mmt_split_planes_f16_rb(x.data_ptr(), xp.data_ptr(), xp.stride(0), N * Hh, W, C, amax, st.data_ptr(), _stream()),
            "mmt_split_planes_f16_rb")
     # the planes stay with the tensor: the weight gradient of the same layer takes BOTH operands from planes (conv_wgrad: the input's
     # from the forward launch, the gradient's from the data-gradient launch) -- alive as long as the tensor is.  (ADVICE r5 asked to
@@ -992,16 +1020,15 @@ def _compile_plan(plan):
 
 
 class LaunchPlan(object):
-    __slots__ = ("calls", "result", "in_ptr", "slot_buf", "slot_next", "pool", "base", "gen", "host_gen", "event", "host", "seen", "segs",
-                 "dead")
+    __slots__ = ("calls", "result", "in_ptr", "slot_buf", "slot_next", "pool", "base", "gen", "seen", "segs", "dead")
+    travels = False   # the pool of its own statistics slots (_Slot: base, gen): zeroed before every replay, never copied to the host
 
     def __init__(self, device):
         self.calls, self.result, self.in_ptr, self.seen, self.dead = [], None, None, 0, False
         self.slot_buf = torch.zeros((_LP_SLOTS, STAT_W), dtype=torch.float32, device=device)
         self.slot_next = 0
         self.pool = torch.cuda.MemPool()
-        # (what _Slot / _site_ok look at: a pool whose statistics never travel to the host)
-        self.base, self.gen, self.host_gen, self.event, self.host = self.slot_buf.data_ptr(), 0, -2, None, None
+        self.base, self.gen = self.slot_buf.data_ptr(), 0
 
     def __del__(self):
         # A plan sits in a reference cycle (its result tensors carry statistics slots whose pool it is), so it dies in the cyclic
@@ -1796,14 +1823,6 @@ def planes_wanted_3x3(N, C, H, W, Cout):
     return conv_route(a, ENTRY_LIB, ASSUME_X | ASSUME_W_PLANES | ASSUME_X_PLANES).family == ROUTE_STRIP
 
 
-def planes_of(x):
-    """the bf16 planes a producing convolution attached to this very tensor object (still valid: not modified since)"""
-    t = getattr(x, "_mmt_planes", None)
-    if t is not None and t[1] == x._version and t[0].shape[1] == x.numel():
-        return t[0]
-    return None
-
-
 # ---- launch plans of the default arithmetic.  The step is bound by the interpreter time of its launch-issuing threads
 # (DESIGN.md section 5), and most of conv_forward's is spent re-deriving what never changes for a call site: shapes, the kernel
 # family, the static half of mmt_conv_args.  The first call of a (weight, input shape, epilogue form) on the fp16 split leaves
@@ -1866,8 +1885,7 @@ def _conv_f16(a, kind, x, src, y, slot, rb_site, tile_rows=0, ksplit=0, xp=None,
     kind (conv_forward and its plans), not the explicit conv_forward_pg of tools and tests"""
     wsrc, flipped, fscale = src
     e0 = _ev() if prof is not None and kind != K_TILED else None
-    am = _amax_of(x)
-    a.f16_guard_x = _guard(am)
+    amax, a.f16_guard_x = _stat_ptrs(_amax_of(x))
     # the fp32 weights for the kernels' slow, exact path (a tensor whose range defeats fp16: decided per block on the device)
     if flipped:
         a.w_src, a.w_src_scale = wsrc.data_ptr(), _p(fscale)
@@ -1884,7 +1902,7 @@ def _conv_f16(a, kind, x, src, y, slot, rb_site, tile_rows=0, ksplit=0, xp=None,
             r = conv_route(a, ENTRY_F16, ASSUME_F16_SCALARS)
             if PROFILE_ALL or r.tag == 1:
                 tag, ks, e0 = "fwd%d" % r.tag, r.ksplit, _ev()
-        _check(lib().mmt_conv_forward_f16x2(ctypes.byref(a), am[0].data_ptr(), sw.data_ptr(), _stream()), "mmt_conv_forward_f16x2")
+        _check(lib().mmt_conv_forward_f16x2(ctypes.byref(a), amax, sw.data_ptr(), _stream()), "mmt_conv_forward_f16x2")
     else:                 # x's planes (its producer's, or one split pass), then the launch
         xp16, sx, a.x_planes_layout, a.x_planes_lag = f16_split_pg(x) if xp is None else (tuple(xp) + (0, 0))[:4]
         a.x_planes, a.x_plane_stride = xp16.data_ptr(), xp16.stride(0)
@@ -1898,7 +1916,7 @@ def _conv_f16(a, kind, x, src, y, slot, rb_site, tile_rows=0, ksplit=0, xp=None,
     if e0 is not None:
         _profiled(a, e0, tag, ks, pre, prof)
     if slot is not None:
-        y._mmt_amax = (slot, y._version)
+        _record(y, slot)
     if yrb is not None:   # (y's row-blocked planes came out of this launch's epilogue)
         _rb_attach(y, yrb[0], yrb[1], "epi", yrb[2])
     return y
@@ -2089,9 +2107,9 @@ def conv_forward(x, w, scale=None, shift=None, stride=1, pad=0, relu=False, res=
     if rec:
         _profiled(a, e0, "fwd%d" % r.tag, 1 if r.tag == 4 else r.ksplit, pre, ebytes)   # (K ranges of the tiled kernels, as ever)
     if y_planes is not None:
-        y._mmt_planes = (y_planes, y._version)
+        _planes_attach(y, y_planes)
     if amax_slot is not None:
-        y._mmt_amax = (amax_slot, y._version)
+        _record(y, amax_slot)
     return y
 
 
@@ -2131,14 +2149,14 @@ def stem_fused(x, w_s2d, scale, shift):
         raise RuntimeError("stem_fused: (N, 3, H, W) fp32 NCHW with H, W % 4 == 0 and the 64 x 16 x 4 x 4 space-to-depth filter")
     w = nhwc(w_s2d)
     am = _amax_of(x)
-    if type(am[0]) is not _Slot:
+    if not _full_slot(am[0]):
         raise RuntimeError("stem_fused: the input needs a full statistics slot")
     wp16, sw = f16_weight_planes(w)
     y = empty_nhwc(N, 64, Hh // 4, W // 4, x.device)
     slot = _amax_slot(x.device)
     _check(lib().mmt_stem_fused(x.data_ptr(), N, Hh, W, w.data_ptr(), wp16.data_ptr(), wp16.stride(0), sw.data_ptr(), _p(scale), _p(shift),
                                 am[0].ptr, y.data_ptr(), slot.ptr, _stream()), "mmt_stem_fused")
-    y._mmt_amax = (slot, y._version)
+    _record(y, slot)
     return y
 
 
@@ -2185,15 +2203,14 @@ def c64_conv3_fused(x, w2, scale2, shift2, w3, scale3, shift3, res, o2_amax=None
         return None   # (the lagged crest-factor test sent conv2's site to the 3-term bf16 split)
     pend = None
     if o2_amax is None:
-        t, i = _rb_site(site, x.device)
-        if t is None or i not in t.ready:
+        s = _rb_site(site, x.device)
+        if s is None or not s.ready:
             return None
-        t.produced.add(i)
-        sc, pend = t.base + 8 * i, t.base + 8 * i + 4
+        sc, pend = s.scale, s.produce()
     else:
         sc = o2_amax.data_ptr()
     am = _amax_of(x)
-    if type(am[0]) is not _Slot:
+    if not _full_slot(am[0]):
         return None
     wp2, sw2 = f16_weight_planes(w2)
     wp3, sw3 = f16_weight_planes(w3)
@@ -2207,13 +2224,11 @@ def c64_conv3_fused(x, w2, scale2, shift2, w3, scale3, shift3, res, o2_amax=None
         w1 = nhwc(nxt[0])
         go = True
         if out_amax is None:
-            t1, i1 = _rb_site(out_site(nxt[0]), x.device)
-            go = t1 is not None and o2_amax is None
+            s1 = _rb_site(out_site(nxt[0]), x.device)
+            go = s1 is not None and o2_amax is None
             if go:
-                t1.produced.add(i1)
-                nx[0] = t1.base + 8 * i1 + 4
-                go = i1 in t1.ready
-                osc = t1.base + 8 * i1
+                nx[0] = s1.produce()
+                go, osc = s1.ready, s1.scale
         else:
             go, osc = o2_amax is not None, out_amax.data_ptr()
         ent = _SITES.get((w1.data_ptr(), False))   # (the host's lagged crest-factor verdict on the next conv1's site, if any)
@@ -2228,11 +2243,11 @@ def c64_conv3_fused(x, w2, scale2, shift2, w3, scale3, shift3, res, o2_amax=None
                                      _p(shift2), am[0].ptr, w3.data_ptr(), wp3.data_ptr(), wp3.stride(0), sw3.data_ptr(), _p(scale3),
                                      _p(shift3), res.data_ptr(), out.data_ptr(), slot.ptr, sc, 0 if o2_amax is None else 1, pend,
                                      *nx, _stream()), "mmt_c64_conv3_fused")
-    out._mmt_amax = (slot, out._version)
+    _record(out, slot)
     if nxt is None:
         return out
     if o1n is not None:
-        o1n._mmt_amax = (nslot, o1n._version)
+        _record(o1n, nslot)
     return out, o1n
 
 
@@ -2426,15 +2441,15 @@ def _wgrad_stats(x, dy, dw):
     return ax, ad
 
 
-def _wgrad_planes(x, dy, st):
+def _wgrad_planes(x, dy, guarded):
     """the row-blocked fp16 planes both operands carry for the whole batch -> (x's record, dy's record, lag bits), or None.  Planes a
     producer's epilogue wrote carry a scale fixed beforehand: the kernel's guard tests it (bit 0: x, bit 1: dy), so both guards of the
-    operands' statistics `st` must be there"""
+    operands' statistics must be there (`guarded`)"""
     xr, dr = _rb_of(x), _rb_of(dy)
-    if xr is None or dr is None or xr[4] is not None or dr[4] is not None:
+    if xr is None or dr is None or not (xr.covers() and dr.covers()):
         return None
-    lag = (1 if xr[3] == "epi" else 0) | (2 if dr[3] == "epi" else 0)
-    if lag and (_guard(st[0]) is None or _guard(st[1]) is None):
+    lag = (1 if xr.lagged() else 0) | (2 if dr.lagged() else 0)
+    if lag and not guarded:
         return None
     return xr, dr, lag
 
@@ -2451,8 +2466,10 @@ def _wgrad_job(x, dy, w_shape, stride, pad, dw, rowscale, dbias, sw):
     st = pl = None
     if F16X2 and _PREC == 3 and x.dtype == torch.float32 and dy.dtype == torch.float32 and w_shape[0] % 4 == 0:
         st = _wgrad_stats(x, dy, dw)
-        if st is not None and WG_PLANES:
-            pl = _wgrad_planes(x, dy, st)
+        if st is not None:
+            st = _stat_ptrs(st[0]) + _stat_ptrs(st[1])   # (x's maximum, its guard, dy's maximum, its guard)
+            if WG_PLANES:
+                pl = _wgrad_planes(x, dy, st[1] is not None and st[3] is not None)
     have = (WG_HAVE_MAXIMA if st is not None else 0) | (WG_HAVE_PLANES if pl is not None else 0)
     # the shape half of the job and its route depend on these only: kept after the first call
     key = (x.shape, dy.shape, w_shape, stride, pad, x.dtype, dy.dtype, have, _PREC, sw)
@@ -2473,15 +2490,14 @@ def _wgrad_job(x, dy, w_shape, stride, pad, dw, rowscale, dbias, sw):
     a.x = x.data_ptr()
     j.dy, j.rowscale, j.dw, j.dbias = dy.data_ptr(), _p(rowscale), dw.data_ptr(), _p(dbias)
     if st is not None:
-        a.f16_x_amax, a.f16_dy_amax = st[0][0].data_ptr(), st[1][0].data_ptr()
-        a.f16_guard_x, a.f16_guard_dy = _guard(st[0]), _guard(st[1])
+        a.f16_x_amax, a.f16_guard_x, a.f16_dy_amax, a.f16_guard_dy = st
     if pl is None:
         return j, plan[1], st is not None, ()
     xr, dr, a.x_planes_lag = pl
-    j.x_planes, j.x_plane_stride = xr[0].data_ptr(), xr[0].stride(0)
-    j.dy_planes, j.dy_plane_stride = dr[0].data_ptr(), dr[0].stride(0)
-    j.s_x, j.s_dy = xr[1].data_ptr(), dr[1].data_ptr()
-    return j, plan[1], True, (xr[0], dr[0])
+    j.x_planes, j.x_plane_stride = xr.planes.data_ptr(), xr.planes.stride(0)
+    j.dy_planes, j.dy_plane_stride = dr.planes.data_ptr(), dr.planes.stride(0)
+    j.s_x, j.s_dy = xr.scale.data_ptr(), dr.scale.data_ptr()
+    return j, plan[1], True, (xr.planes, dr.planes)
 
 
 def _wgrad_launch(j, r, f16, device):

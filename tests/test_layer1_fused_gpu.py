@@ -123,10 +123,10 @@ def test_lagged_scale_against_fp64(hip, shape):
     o2, out1 = _unfused(H, blk, o1, zero, site, affine3=False)
     torch.cuda.synchronize()
     assert _conv3_error(o2, blk["w3"], out1) <= 3e-6
-    t, i = H._rb_site(site, o1.device)
-    assert float(t.state[i, 1]) == float(o2.abs().max())                                     # the pending maximum
+    row = H._rb_site(site, o1.device).state
+    assert float(row[1]) == float(o2.abs().max())                                            # the pending maximum
     H.rb_scales_update()
-    s = float(t.state[i, 0])
+    s = float(row[0])
     assert 2.0 ** 12 <= float(o2.abs().max()) * s < 2.0 ** 13
     # step 2: o2 doubles (conv2 without shift is linear in o1 up to the ReLU; with it, nearly) -- the fused launch, lagged scale
     o1b = H.conv_forward(x * 2.0, blk["w1"], s1, b1 * 2.0, relu=True)
@@ -136,7 +136,7 @@ def test_lagged_scale_against_fp64(hip, shape):
     torch.cuda.synchronize()
     assert float(o2b.abs().max()) * s >= 2.0 ** 12.9                                         # (really beyond the scale's own tensor)
     assert _conv3_error(o2b, blk["w3"], out2) <= 3e-6
-    assert float(t.state[i, 1]) == float(o2b.abs().max())
+    assert float(row[1]) == float(o2b.abs().max())
     assert _slot_max(out2) == float(out2.abs().max())
 
 
@@ -163,8 +163,8 @@ def test_a_tile_beyond_the_scales_range_takes_the_exact_path(hip):
     out = H.c64_conv3_fused(o1b, blk["w2"], s2, b2, blk["w3"], None, None, zero)
     assert out is not None and H.F16_STATS.get("fallback", 0) == fb0                          # no site left the fp16 split on the host
     torch.cuda.synchronize()
-    t, i = H._rb_site(site, o1.device)
-    s = float(t.state[i, 0])
+    row = H._rb_site(site, o1.device).state
+    s = float(row[0])
     assert float(o2b.abs().max()) * s >= 1.0e4 * 65504.0                                     # one element 10^4 x the scale's range
     assert _conv3_error(o2b, blk["w3"], out) <= 3e-6
     # WHICH tiles left the matrix path: the same launch told to derive the same scale from a maximum (2^13 / s maps to s) makes no tile
@@ -294,20 +294,20 @@ def test_o1_next_lagged_scales_and_no_scale_against_fp64(hip, shape):
     o2 = H.conv_forward(o1, blk["w2"], s2, b2, 1, 1, relu=True, rb_site=H.o2_site(blk["w3"]))
     out1 = H.conv_forward(o2, blk["w3"], None, None, 1, 0, relu=True, res=zero, res_mode=1, rb_site=H.out_site(w1n))
     torch.cuda.synchronize()
-    t, i = H._rb_site(H.out_site(w1n), o1.device)
-    assert float(t.state[i, 1]) == float(out1.abs().max())
+    row = H._rb_site(H.out_site(w1n), o1.device).state
+    assert float(row[1]) == float(out1.abs().max())
     H.rb_scales_update()
     o1b = H.conv_forward(x * 2.0, blk["w1"], s1, b1 * 2.0, relu=True)
     o2b = H.conv_forward(o1b, blk["w2"], s2, b2, 1, 1, relu=True)
     out, o1n = H.c64_conv3_fused(o1b, blk["w2"], s2, b2, blk["w3"], None, None, zero, nxt=(w1n, None, None))
     assert o1n is not None
     torch.cuda.synchronize()
-    assert float(out.abs().max()) * float(t.state[i, 0]) >= 2.0 ** 12.9
+    assert float(out.abs().max()) * float(row[0]) >= 2.0 ** 12.9
     assert _conv3_error(o2b, blk["w3"], out) <= 3e-6 and _conv1_error(out, w1n, o1n) <= 3e-6
-    assert float(t.state[i, 1]) == float(out.abs().max()) and _slot_max(o1n) == float(o1n.abs().max())
-    t2, i2 = H._rb_site(H.o2_site(blk["w3"]), o1.device)
-    t.state[i, 0] = 0.0
-    t2.state[i2, 0] = 0.0
+    assert float(row[1]) == float(out.abs().max()) and _slot_max(o1n) == float(o1n.abs().max())
+    row2 = H._rb_site(H.o2_site(blk["w3"]), o1.device).state
+    row[0] = 0.0
+    row2[0] = 0.0
     out0, o1n0 = H.c64_conv3_fused(o1b, blk["w2"], s2, b2, blk["w3"], None, None, zero, nxt=(w1n, None, None))
     torch.cuda.synchronize()
     assert _conv3_error(o2b, blk["w3"], out0) <= 3e-6 and _conv1_error(out0, w1n, o1n0) <= 3e-6
@@ -328,8 +328,8 @@ def test_a_wave_beyond_the_out_scales_range_computes_o1_next_exactly(hip):
     rb[1, :, 11, 19] = 1.0e7
     out, o1n = H.c64_conv3_fused(o1, blk["w2"], s2, b2, blk["w3"], s3, b3, rb, nxt=(w1n, None, None))
     torch.cuda.synchronize()
-    t, i = H._rb_site(H.out_site(w1n), o1.device)
-    assert float(out.abs().max()) * float(t.state[i, 0]) >= 1.0e4 * 65504.0
+    row = H._rb_site(H.out_site(w1n), o1.device).state
+    assert float(out.abs().max()) * float(row[0]) >= 1.0e4 * 65504.0
     assert _conv1_error(out, w1n, o1n) <= 3e-6
 
 

@@ -153,9 +153,9 @@ def test_default_mode(hip, tmp_path):
     for step in (1, 2):
         _step(cfg, a, batch, step)
     at_save = _buffers(a)
-    sites = len(H._RB[0].index)
+    sites = len(H._RB[0].sites)
     a.save_model(cfg.MT.START_MT + 401)
-    assert sites > 0 and len(H._RB[0].index) == sites      # outside deterministic mode a save leaves the adaptive state alone
+    assert sites > 0 and len(H._RB[0].sites) == sites      # outside deterministic mode a save leaves the adaptive state alone
     assert os.path.exists(os.path.join(str(tmp_path), "t_model_%07d.pth" % (cfg.MT.START_MT + 401)))
     del a
     torch.manual_seed(123)
