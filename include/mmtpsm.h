@@ -1011,6 +1011,28 @@ int mmt_ciam_norm_bwd_ordered(const float* x, const int64_t* group, int n, int C
                               const float* gamma, const float* saved, const float* A, const int* J, const float* dout, float* ws,
                               float* dx, float* dgamma, void* stream);
 
+/* ---------------------------------------------------------------- test-time augmentation: the merges over views (csrc/tta.hip)
+ * V views of the same n images (GeneralizedRCNN.forward_tta): bit v of flip_mask says that view v was computed on the mirror image.
+ * 1 <= V <= 8, 0 <= flip_mask < 2^V.  Views are added in ascending v by the one thread that owns the output element (no atomics: the
+ * same bits on every run) and the sum is divided by V; without FMA contraction, so one view -- or two equal un-mirrored views --
+ * return that view's value to the bit.  Malformed arguments return MMT_EINVAL before any launch.
+ *
+ * mmt_tta_merge_box: logits [V][R][C], reg [V][R][4C] (the box head's outputs for the same R proposals, mirrored for a mirrored view)
+ *   prob[r][c]      = (sum_v softmax(logits[v][r][:])[c]) / V       softmax subtracts the row maximum and uses expf
+ *   reg_out[r][4c+k] = (sum_v s * reg[v][r][4c+k]) / V               s = -1 for k == 0 (dx) of a mirrored view, 1 otherwise
+ * (decoding dx on the mirrored proposal and mirroring the box back is decoding -dx on the proposal itself: x1' = W - 1 - x2, widths
+ * with the +1 convention).  1 <= C <= 64, the limit of mmt_det_postprocess; R == 0 returns 0 without a launch.  The row maximum is
+ * the IEEE `maximum`: a NaN (or an infinite logit) in one view's row makes that row of prob NaN and no other. */
+int mmt_tta_merge_box(const float* logits, const float* reg, int V, int R, int C, int flip_mask, float* prob, float* reg_out,
+                      void* stream);
+/* mmt_tta_merge_mask: logits [V][D][C][M][M] (the mask head's logits of the same D detections on every view), labels [D] int64 (as
+ * mmt_det_postprocess returns them)
+ *   prob[d][y][x] = (sum_v sigmoid(logits[v][d][labels[d]][y][x_v])) / V      x_v = M - 1 - x for a mirrored view, x otherwise
+ * The sigmoid never overflows for either sign.  A label outside [0, C) writes NaN to that detection's M x M block and reads
+ * nothing.  1 <= C <= 64, 1 <= M <= 1024; D == 0 returns 0 without a launch. */
+int mmt_tta_merge_mask(const float* logits, const int64_t* labels, int V, int D, int C, int M, int flip_mask, float* prob,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -242,6 +242,8 @@ _SIGS = {
                           c_void_p, c_void_p, c_void_p],
     "mmt_ciam_norm_bwd_ordered": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p],
+    "mmt_tta_merge_box": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "mmt_tta_merge_mask": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
 }
 # the entry points that return `long` (sizes in floats; include/mmtpsm.h), bound like _SIGS with that result type
 _SIGS_LONG = {
@@ -1425,6 +1427,52 @@ def det_postprocess(prob, dec, per, score_thresh, nms_thresh, detections_per_img
                                      float(nms_thresh), int(detections_per_img), _p(ws), _p(ob), _p(os_), _p(ol), _p(oc),
                                      _stream()), "mmt_det_postprocess")
     return ob, os_, ol, oc
+
+
+# ------------------------------------------------------------------------------------------ test-time augmentation
+TTA_MAX_VIEWS = 8   # csrc/tta.hip: the bits of flip_mask (the teacher's slot count)
+
+
+def _tta_flip_mask(flips, V):
+    flips = [bool(f) for f in flips]
+    if len(flips) != V:
+        raise ValueError("one flip flag per view: %d flags for %d views" % (len(flips), V))
+    if not 1 <= V <= TTA_MAX_VIEWS:
+        raise ValueError("1 to %d views, not %d" % (TTA_MAX_VIEWS, V))
+    return sum(1 << v for v, f in enumerate(flips) if f)
+
+
+def tta_merge_box(logits, reg, flips):
+    """logits (V, R, C), reg (V, R, 4C) of the same R proposals on V views, flips[v]: view v is a mirror image
+    -> prob (R, C) = mean over views of the row softmax, reg (R, 4C) = mean with dx negated for mirrored views (one launch)"""
+    logits, reg = _dev(logits, "logits"), _dev(reg, "reg")
+    if logits.dim() != 3 or reg.dim() != 3 or logits.dtype != torch.float32 or reg.dtype != torch.float32:
+        raise ValueError("tta_merge_box: fp32 logits (V, R, C) and reg (V, R, 4C)")
+    V, R, C = logits.shape
+    if tuple(reg.shape) != (V, R, 4 * C):
+        raise ValueError("tta_merge_box: reg %s does not go with logits %s" % (tuple(reg.shape), tuple(logits.shape)))
+    mask = _tta_flip_mask(flips, V)
+    logits, reg = logits.contiguous(), reg.contiguous()
+    prob = torch.empty((R, C), dtype=torch.float32, device=logits.device)
+    out = torch.empty((R, 4 * C), dtype=torch.float32, device=logits.device)
+    _check(lib().mmt_tta_merge_box(_p(logits), _p(reg), V, R, C, mask, _p(prob), _p(out), _stream()), "mmt_tta_merge_box")
+    return prob, out
+
+
+def tta_merge_mask(logits, labels, flips):
+    """logits (V, D, C, M, M) of the same D detections on V views, labels (D,) int64 -> (D, 1, M, M): the mean over views of the
+    predicted class's sigmoid, mirrored views read right to left (one launch)"""
+    logits, labels = _dev(logits, "logits"), _dev(labels, "labels")
+    if logits.dim() != 5 or logits.shape[3] != logits.shape[4] or logits.dtype != torch.float32:
+        raise ValueError("tta_merge_mask: fp32 logits (V, D, C, M, M)")
+    V, D, C, M, _ = logits.shape
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (D,):
+        raise ValueError("tta_merge_mask: int64 labels (D,)")
+    mask = _tta_flip_mask(flips, V)
+    logits, labels = logits.contiguous(), labels.contiguous()
+    prob = torch.empty((D, 1, M, M), dtype=torch.float32, device=logits.device)
+    _check(lib().mmt_tta_merge_mask(_p(logits), _p(labels), V, D, C, M, mask, _p(prob), _stream()), "mmt_tta_merge_mask")
+    return prob
 
 
 # ------------------------------------------------------------------------------------------ input augmentation

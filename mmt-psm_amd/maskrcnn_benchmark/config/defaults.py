@@ -135,7 +135,9 @@ _DEFAULTS = {
     },
     "INPUT": {"MIN_SIZE_TRAIN": 800, "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333,
               "PIXEL_MEAN": [102.9801, 115.9465, 122.7717], "PIXEL_STD": [1.0, 1.0, 1.0], "TO_BGR255": True},
-    "TEST": {"TTA": False},
+    # TTA: multi-view inference (GeneralizedRCNN.forward_tta): TTA_VIEWS colour views per image (view 0 un-augmented), each followed
+    # by its mirror image when TTA_FLIP; at most 8 views in all
+    "TEST": {"TTA": False, "TTA_FLIP": True, "TTA_VIEWS": 1},
     "DATALOADER": {"SIZE_DIVISIBILITY": 32},
     "DATASETS": {"NO_LABEL": True, "SYN": False},
     "SOLVER": {"BASE_LR": 0.005, "BIAS_LR_FACTOR": 2, "MOMENTUM": 0.9, "WEIGHT_DECAY": 0.0001,

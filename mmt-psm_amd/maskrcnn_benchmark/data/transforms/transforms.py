@@ -283,3 +283,28 @@ def augment_views(base, transform, k, size_divisible=0):
             img, _ = t(img, None)
         pending.append(img)
     return _materialize(pending, ops[-1].mean, size_divisible)
+
+
+def tta_views(bases, transform, k, size_divisible=0):
+    """The K view batches of test-time augmentation (TEST.TTA_VIEWS = k) for n resized images of one size: view 0 is the
+    un-augmented batch, views 1..k-1 come from the colour chain of `transform` (the second part of build_transforms with TEST.TTA:
+    brightness, contrast, hue; its RandomErasing is left out -- an erased nucleus is a missed detection, not a view) through
+    augment_views.  bases: n DeviceImages -> list of k ImageLists of n images, ready for GeneralizedRCNN.forward_tta"""
+    from maskrcnn_benchmark.structures.image_list import ImageList
+    ops = transform.transforms
+    if not ops or not isinstance(ops[-1], Normalize):
+        raise ValueError("tta_views wants a Compose ending in Normalize")
+    if k < 1:
+        raise ValueError("TEST.TTA_VIEWS must be at least 1")
+    if len({b.size for b in bases}) != 1:
+        raise NotImplementedError("test-time augmentation: views of differing shapes (images of one batch must share a size)")
+    plain = Compose([ToTensor(), ops[-1]])
+    colour = Compose([t for t in ops if not isinstance(t, RandomErasing)])
+    per_image = []
+    for base in bases:
+        v = augment_views(base, plain, 1, size_divisible)
+        if k > 1:
+            v = torch.cat([v, augment_views(base, colour, k - 1, size_divisible)], 0)
+        per_image.append(v)
+    sizes = [(b.size[1], b.size[0]) for b in bases]
+    return [ImageList(torch.stack([v[j] for v in per_image]), list(sizes)) for j in range(k)]

@@ -27,14 +27,18 @@ def is_main_process():
 
 
 def compute_on_dataset(model, data_loader, device, tta=False):
-    """-> {image_id: BoxList on the host}; batches are (images, targets, image_ids) as the collators deliver them"""
-    if tta:
-        raise NotImplementedError("test-time augmentation is not on the MI355X hot path")
+    """-> {image_id: BoxList on the host}; batches are (images, targets, image_ids) as the collators deliver them.  `tta`: multi-view
+    inference (GeneralizedRCNN.forward_tta) -- a batch whose first element is a list or tuple of image batches carries the K views
+    of TEST.TTA_VIEWS (data/transforms: tta_views), an ordinary batch is its own single view (flip-only augmentation)"""
     model.eval()
     results, cpu = {}, torch.device("cpu")
     for images, _targets, image_ids in data_loader:
         with torch.no_grad():
-            output = model(images.to(device))
+            if tta:
+                views = list(images) if isinstance(images, (list, tuple)) else [images]
+                output = model([v.to(device) for v in views], tta=True)
+            else:
+                output = model(images.to(device))
         results.update({i: o.to(cpu) for i, o in zip(image_ids, output)})
     return results
 
@@ -68,16 +72,17 @@ def _accepts(fn, name):
 
 def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=False, device="cuda", expected_results=(),
               expected_results_sigma_tol=4, output_folder=None, generate_data=False, visual_num=0, evaluator=None,
-              eval_on_device=False):
+              eval_on_device=False, tta=False):
     """eval_on_device: handed on as `on_device` to the evaluator (the PAP evaluator then scores masks with the kernels of
-    csrc/maskeval.hip); an evaluator that does not take it cannot honour it: that raises, nothing falls back"""
+    csrc/maskeval.hip); an evaluator that does not take it cannot honour it: that raises, nothing falls back.
+    tta: handed on to compute_on_dataset (multi-view inference)"""
     device = torch.device(device)
     logger = logging.getLogger("maskrcnn_benchmark.inference")
     dataset = getattr(data_loader, "dataset", None)
     n_img = len(dataset) if dataset is not None else None
     logger.info("Start evaluation on {} dataset({} images).".format(dataset_name, n_img))
     t0 = time.time()
-    predictions = compute_on_dataset(model, data_loader, device)
+    predictions = compute_on_dataset(model, data_loader, device, tta=tta)
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     if _world() > 1:

@@ -4,6 +4,7 @@ forward(images, targets)            supervised student step -> loss dict / eval 
 forward_teacher(images)             coarse inference -> pseudo labels + masks; K-aug x flip pyramids; per-view logits
 forward_teacher(images, targets)    the same dict from ground truth: annotated boxes, decoded polygon masks
 forward_student(images, result_t)   MGD (mt_fg_loss) + PSM (mt_classifier)
+forward_tta(views, flip)            multi-view inference: K x flip views in one batch, merged probabilities / regressions / masks
 
 Same attribute tree (backbone, rpn, box_heads, mask_heads, relation_nms, hint_adaptor), same dict keys.  The IR-Net
 branches (relation_nms here, mask relation inside the mask head) follow generalized_rcnn.py:62-96."""
@@ -11,7 +12,7 @@ import torch
 from torch import nn
 
 from maskrcnn_benchmark.layers import fused
-from maskrcnn_benchmark.structures.image_list import to_image_list
+from maskrcnn_benchmark.structures.image_list import ImageList, to_image_list
 from ..backbone import build_backbone
 from ..rpn.rpn import build_rpn
 from ..roi_heads.roi_heads import box_roi_heads, mask_roi_heads
@@ -162,6 +163,11 @@ class GeneralizedRCNN(nn.Module):
     def forward(self, images, targets=None, tta=None, features=None):
         """`features`: optional precomputed backbone(images.tensors) pyramid (the engine batches the backbone pass of
         the labeled and unlabeled student crops; the teacher reuses view 0's pyramid for its coarse inference)."""
+        if tta:
+            # test-time augmentation: a list / tuple of image batches is the K views, anything else one batch (flip-only)
+            is_views = isinstance(images, (list, tuple)) and len(images) > 0 and (
+                hasattr(images[0], "image_sizes") or (torch.is_tensor(images[0]) and images[0].dim() == 4))
+            return self.forward_tta(list(images) if is_views else [images], flip=self.cfg.TEST.TTA_FLIP)
         if self.training and targets is None:
             raise ValueError("In training mode, targets should be passed")
         images = to_image_list(images)
@@ -211,6 +217,61 @@ class GeneralizedRCNN(nn.Module):
         if self.training:
             return result, loss
         return outs, None
+
+    def forward_tta(self, views, flip=True):
+        """Multi-view inference.  `views`: K >= 1 image batches (ImageList or tensor) of the same geometry, n images each; with
+        `flip` every batch is followed by its mirror image (V = 2K views, the teacher's order), else V = K.  All views go through
+        the backbone as one batch; the test-mode RPN runs on view 0; the box head pools every view with the same proposals
+        (mirrored about the padded width for a mirrored view) in one pass and `mmt_tta_merge_box` averages the class probabilities and the regressions
+        (dx negated for a mirrored view) in ascending view order; the merged pair goes through the unchanged decode and
+        post-processing; the mask head runs the detections over every view likewise and `mmt_tta_merge_mask` averages the
+        predicted class's probabilities.  -> the detections, as forward() returns them in eval mode."""
+        from maskrcnn_benchmark import _hip as H
+        if self.training:
+            raise ValueError("forward_tta is an eval-mode pass: model.eval() first")
+        if self.relation_nms is not None or self.box_heads.box.use_realation_nms:
+            raise NotImplementedError("MODEL.RELATION_NMS.USE_RELATION_NMS is not offered with test-time augmentation")
+        if self.mask_heads.mask.use_relation:
+            raise NotImplementedError("MODEL.RELATION_MASK.USE_RELATION is not offered with test-time augmentation")
+        if self.mask_heads.mask.on_image:
+            raise NotImplementedError("MODEL.ROI_MASK_HEAD.FEATURE_EXTRACTOR PRCNNFeatureExtractor is not offered with test-time "
+                                      "augmentation")
+        views = list(views)
+        V = len(views) * (2 if flip else 1)
+        if not 1 <= V <= H.TTA_MAX_VIEWS:
+            raise NotImplementedError("test-time augmentation with V = %d views (TEST.TTA_VIEWS x flip): 1 to %d"
+                                      % (V, H.TTA_MAX_VIEWS))
+        # (fresh ImageLists: extract_aug_feat mirrors them in place, the caller's stay as they are)
+        lists = [to_image_list(v) for v in views]
+        lists = [ImageList(il.tensors, list(il.image_sizes)) for il in lists]
+        if any(il.tensors.shape != lists[0].tensors.shape or il.image_sizes != lists[0].image_sizes for il in lists):
+            raise NotImplementedError("test-time augmentation: views of differing shapes (%s)"
+                                      % sorted({tuple(il.tensors.shape) for il in lists}))
+        first = ImageListView(lists[0])
+        # ImageList.hflip() mirrors the whole zero-padded batch tensor: a mirrored view's ROIs are mirrored about ITS width, which
+        # is where their content went (about an image's own width they would sit Wpad - w pixels off wherever an image is padded)
+        wpad = int(lists[0].tensors.shape[3])
+        flips = [flip and v % 2 == 1 for v in range(V)]
+        with torch.no_grad():
+            feats = self.extract_aug_feat(lists, mirror=flip)
+            batched, self._batched_pyr = self._batched_pyr, None
+            proposals, _ = self.rpn(first, feats[0], None)
+            proposals = self._tap("infer_proposals", proposals)
+            box = self.box_heads.box
+            box.batched_pyramid = batched
+            try:
+                _, logits, regs, _ = box._forward_single(proposals, None, feats, istrain=False, flips=flips, padded_width=wpad)
+            finally:
+                box.batched_pyramid = None
+            logits = self._tap("tta_view_logits", torch.stack(logits))
+            regs = self._tap("tta_view_regs", torch.stack(regs))
+            prob, reg = H.tta_merge_box(logits, regs, flips)
+            prob, reg = self._tap("tta_box_prob", prob), self._tap("tta_box_reg", reg)
+            result = box.post_processor.forward_prob(prob, reg, proposals)
+            result = self._tap("detections", result)
+            result, view_masks = self.mask_heads.mask.forward_views(batched[0], batched[1], flips, result, wpad)
+            self._tap("tta_view_mask_logits", view_masks)
+        return result
 
     def forward_teacher(self, images, targets=None):
         if targets is not None:
@@ -325,15 +386,17 @@ class GeneralizedRCNN(nn.Module):
                     box.batched_pyramid = None
         return loss_dict
 
-    def extract_aug_feat(self, imglist, teacher=True):
-        """generalized_rcnn.py:201-215 (ImageList.hflip mutates in place, as in the reference)"""
+    def extract_aug_feat(self, imglist, teacher=True, mirror=True):
+        """generalized_rcnn.py:201-215 (ImageList.hflip mutates in place, as in the reference).  `mirror` False (test-time
+        augmentation without flips): the batches as they are, still one backbone pass"""
         feats = []
         if teacher:
             views = []
             for img in imglist:
                 views.append(img.tensors)
-                img.hflip()
-                views.append(img.tensors)
+                if mirror:
+                    img.hflip()
+                    views.append(img.tensors)
             n = views[0].shape[0]
             if all(v.shape == views[0].shape for v in views):
                 if is_teacher_fpn(self.backbone):

@@ -20,7 +20,7 @@ from maskrcnn_benchmark.modeling.balanced_positive_negative_sampler import Balan
 from maskrcnn_benchmark.modeling.poolers import Pooler
 from maskrcnn_benchmark.structures.bounding_box import BoxList
 from maskrcnn_benchmark.structures.boxlist_ops import boxlist_iou
-from maskrcnn_benchmark.utils.miscellaneous import batch_boxlist_hflip
+from maskrcnn_benchmark.utils.miscellaneous import batch_boxlist_hflip, batch_boxlist_hflip_padded
 
 
 
@@ -310,7 +310,11 @@ class PostProcessor(nn.Module):
 
     def forward(self, x, boxes):
         class_logits, box_regression = x
-        prob = F.softmax(class_logits, -1)
+        return self.forward_prob(F.softmax(class_logits, -1), box_regression, boxes)
+
+    def forward_prob(self, prob, box_regression, boxes):
+        """forward() from class PROBABILITIES (R, C) instead of logits: everything behind the softmax, the same calls in the same
+        order (test-time augmentation hands in the probabilities and regressions merged over its views)"""
         per = [len(b) for b in boxes]
         dev = prob.device
         if all(getattr(b, "count_dev", None) is not None for b in boxes):
@@ -410,10 +414,17 @@ class ROIBoxHead(nn.Module):
         lc, lb = self.loss_evaluator([class_logits], [box_regression])
         return x, proposals, dict(loss_classifier=lc, loss_box_reg=lb), class_logits, box_regression
 
-    def _forward_single(self, proposals, targets, feats_list, istrain=False):
+    def _forward_single(self, proposals, targets, feats_list, istrain=False, flips=None, padded_width=None):
+        """`flips`: per view, whether it was computed on the mirror image (its ROIs are the mirrored proposals); None = every odd
+        view, the order extract_aug_feat builds.  `padded_width`: mirror the proposals about the width of the padded batch tensor
+        (utils/miscellaneous.py::batch_boxlist_hflip_padded: where ImageList.hflip() put their content) instead of each image's own
+        width, the reference's pairing, which the mean-teacher entry points keep"""
         if targets is not None:
             proposals = self.loss_evaluator.subsample(proposals, targets)
-        proposals_b = batch_boxlist_hflip(proposals)
+        proposals_b = (batch_boxlist_hflip(proposals) if padded_width is None
+                       else batch_boxlist_hflip_padded(proposals, padded_width))
+        if flips is None:
+            flips = [i % 2 == 1 for i in range(len(feats_list))]
         feats, logits, regs = [], [], []
         bp = getattr(self, "batched_pyramid", None)
         if bp is not None and len(feats_list) == bp[2] and feats_list[0][0].data_ptr() == bp[0][0].data_ptr():
@@ -422,13 +433,13 @@ class ROIBoxHead(nn.Module):
             pyr, n, nv = bp
             boxes = []
             for i in range(nv):
-                boxes += list(proposals if i % 2 == 0 else proposals_b)
+                boxes += list(proposals_b if flips[i] else proposals)
             x = self.feature_extractor(pyr, boxes, istrain=istrain, views=nv)
             cl, br = self.predictor(x, self._scale(istrain))
             R = x.shape[0] // nv
             return (list(x.split(R, 0)), list(cl.split(R, 0)), list(br.split(R, 0)), proposals)
         for i, feat in enumerate(feats_list):
-            x = self.feature_extractor(feat, proposals if i % 2 == 0 else proposals_b, istrain=istrain)
+            x = self.feature_extractor(feat, proposals_b if flips[i] else proposals, istrain=istrain)
             cl, br = self.predictor(x, self._scale(istrain))
             feats.append(x)
             logits.append(cl)

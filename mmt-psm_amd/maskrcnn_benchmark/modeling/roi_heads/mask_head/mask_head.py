@@ -257,6 +257,20 @@ class MaskPostProcessor(nn.Module):
             segs = prob.split(per, 0)
             if self.masker is not None:   # POSTPROCESS_MASKS (inference.py:62-63): the same rows, pasted into their image
                 segs = self.masker(segs, boxes)
+        return self._with_masks(segs, boxes)
+
+    def forward_prob(self, prob, boxes):
+        """forward() from the (D, 1, M, M) probabilities of the predicted class (test-time augmentation merges them over its views)"""
+        if self.masker is not None and not isinstance(self.masker, DetectionMasker):
+            raise NotImplementedError("the integral pseudo-mask is pasted from logits: probabilities go through the evaluation "
+                                      "post-processor only")
+        segs = prob.split([len(b) for b in boxes], 0)
+        if self.masker is not None:
+            segs = self.masker(segs, boxes)
+        return self._with_masks(segs, boxes)
+
+    @staticmethod
+    def _with_masks(segs, boxes):
         out = []
         for s, b in zip(segs, boxes):
             r = BoxList(b.bbox, b.size, "xyxy")
@@ -393,6 +407,41 @@ class ROIMaskHead(nn.Module):
             else:
                 result = self.mask_generator(mask_logits, proposals)
         return x, result, {}
+
+    def forward_views(self, pyramid, n, flips, detections, padded_width):
+        """Eval pass over the views of one batched backbone pass (test-time augmentation): `pyramid` holds len(flips) views of n
+        images each, image index = view * n + image; the detections -- for a mirrored view mirrored about `padded_width`, the width
+        of the padded batch tensor, where ImageList.hflip() put their content -- are pooled from every view in ONE ROIAlign + mask_fcn + predictor
+        pass, and the predicted class's probabilities are averaged over the views by one launch (csrc/tta.hip), mirrored views
+        read right to left.
+        -> (the detections with their `mask` field, the per-view logits (V, D, C, M, M) or None when nothing was detected)"""
+        if self.training:
+            raise ValueError("ROIMaskHead.forward_views is an eval-mode pass")
+        if self.use_relation:
+            raise NotImplementedError("MODEL.RELATION_MASK.USE_RELATION is not offered with test-time augmentation")
+        if self.on_image:
+            raise NotImplementedError("MODEL.ROI_MASK_HEAD.FEATURE_EXTRACTOR PRCNNFeatureExtractor is not offered with test-time "
+                                      "augmentation")
+        from maskrcnn_benchmark.utils.miscellaneous import batch_boxlist_hflip_padded
+        V, D = len(flips), sum(len(d) for d in detections)
+        if len(detections) != n or pyramid[0].shape[0] != V * n:
+            raise ValueError("forward_views: %d detection lists and a pyramid of %d images for %d views of %d images"
+                             % (len(detections), pyramid[0].shape[0], V, n))
+        M = self.cfg.MODEL.ROI_MASK_HEAD.RESOLUTION
+        with torch.no_grad():
+            if D == 0:   # nothing to pool: empty fields, no launch
+                dev = detections[0].bbox.device
+                return self.post_processor.forward_prob(torch.zeros((0, 1, M, M), dtype=torch.float32, device=dev), detections), None
+            mirrored = batch_boxlist_hflip_padded(detections, padded_width) if any(flips) else None
+            boxes = []
+            for f in flips:
+                boxes += list(mirrored if f else detections)
+            x, _ = self.feature_extractor(pyramid, boxes)
+            logits = self.predictor(x)                                  # (V * D, C, M, M), NHWC memory
+            logits = logits.contiguous().view(V, D, logits.shape[1], logits.shape[2], logits.shape[3])
+            labels = torch.cat([d.get_field("labels") for d in detections])
+            prob = H.tta_merge_mask(logits, labels, flips)
+            return self.post_processor.forward_prob(prob, detections), logits
 
 
 def build_roi_mask_head(cfg, is_student=False):

@@ -19,6 +19,23 @@ def batch_boxlist_hflip(boxlists):
     return [b.transpose(0) for b in boxlists]
 
 
+def batch_boxlist_hflip_padded(boxlists, padded_width):
+    """The boxes that cover, in `ImageList.hflip()`'s mirror image of a zero-padded batch tensor of width `padded_width`, what
+    they cover in the batch tensor: `hflip` flips the WHOLE padded tensor (a pixel moves from x to padded_width - 1 - x), so the
+    boxes are mirrored about the padded width, x1' = padded_width - 1 - x2 -- not about each image's own width, which is what
+    batch_boxlist_hflip does and which agrees only where no image of the batch is padded.  Size, mode and fields are kept as
+    they are (the lists of inference carry per-box tensors only)."""
+    from maskrcnn_benchmark.structures.bounding_box import BoxList
+    out = []
+    for b in boxlists:
+        m = BoxList(b.convert("xyxy").bbox, (padded_width, b.size[1]), "xyxy").transpose(0)
+        m.size = b.size
+        for k, v in b.extra_fields.items():
+            m.add_field(k, v)
+        out.append(m.convert(b.mode))
+    return out
+
+
 def sigmoid_rampup(current, rampup_length):
     if rampup_length == 0:
         return 1.0
