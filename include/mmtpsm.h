@@ -904,6 +904,27 @@ int mmt_mask_transition_positions(const uint64_t* words, int n, int H, int W, co
 int mmt_mask_pair_intersections(const uint64_t* dwords, const int32_t* drec, int m, const uint64_t* gwords,
                                 const int32_t* grec, int n, int H, int W, int32_t* inter, void* stream);
 
+/* ---------------------------------------------------------------- mask NMS at inference (csrc/masknms.hip)
+ * Greedy suppression of duplicate instances by the overlap of their MASKS (the reference stays in host Python:
+ * modeling/python_nms.py cyto_nms, set_cpu_nms).  words / rec: D masks of one H x W image as above; order int32 [D]: the rows by
+ * descending score, equal scores in row order (a permutation of 0 .. D-1); labels int32 [D].  Walk the order: detection j is dropped
+ * when an earlier detection i is still kept, has the same label (any label with class_agnostic != 0) and overlaps it:
+ *   inter = popcount(mask_i & mask_j) > 0  and  inter * 2^20 >= thresh_q20 * den,  in 64-bit integers,
+ *   den = area_i + area_j - inter (measure 0, IoU)  or  min(area_i, area_j) (measure 1, intersection over the smaller mask);
+ * thresh_q20 = round(t * 2^20) for a threshold t in (0, 1].  An empty mask suppresses nothing and is never suppressed; a dropped
+ * detection suppresses nothing.  keep uint8 [D] (1 = kept, in ROW order) and count int32 [1] (the kept rows) are written in full.
+ * Two launches: one wave per pair of sweep positions p < q whose labels and record boxes allow an overlap reads the words of the
+ * overlapping columns only and writes one byte of ws (every byte the second launch reads has exactly one writer); then one block
+ * resolves the sweep.  Integers only, no atomics, nothing read back, nothing allocated: the same bits run to run, in deterministic
+ * mode as well.  ws: at least the bytes that mmt_mask_nms_workspace(D, &bytes) reports (D * D; the query launches nothing).
+ * MMT_EINVAL, before any launch, for D < 0 or D > 1024, H * W >= 2^31, H or W <= 0, thresh_q20 outside [1, 2^20], a measure other
+ * than 0 or 1, a null pointer, or ws_bytes below the need.  D == 0 writes count = 0 and reads no array (only count must be given). */
+int mmt_mask_nms_workspace(int D, int64_t* bytes /*[host]*/);
+int mmt_mask_nms(const uint64_t* words /*[D][ceil(H*W/64)]*/, const int32_t* rec /*[D][MMT_MASK_REC_INTS]*/,
+                 const int32_t* order /*[D]*/, const int32_t* labels /*[D]*/, int D, int H, int W,
+                 int thresh_q20, int measure /*0 iou, 1 iomin*/, int class_agnostic,
+                 void* ws, int64_t ws_bytes, uint8_t* keep /*[D]*/, int32_t* count /*[1]*/, void* stream);
+
 /* ---------------------------------------------------------------- polygons at image size (csrc/polyfill.hip)
  * polygon_mask_words (structures/segmentation_mask.py:127-137 Polygons.convert("mask"): frPyObjects -> pycoco/maskApi.c:166-206
  * rleFrPoly, :53-74 union, :47-51 decode): instance g is the union of the fills of polygons inst_poly[g][0] .. inst_poly[g][1]-1

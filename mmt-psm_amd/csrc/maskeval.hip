@@ -9,17 +9,11 @@
 //
 // Integer arithmetic only; no atomics, every result is independent of scheduling.  The strings themselves (LEB128-like
 // characters) are written and parsed by the host.
-#include "common.h"
+#include "maskwords.h"
 #include <limits.h>
 
-typedef unsigned long long u64;
-
-#define REC MMT_MASK_REC_INTS   // area, xmin, xmax, ymin, ymax, wrap, 0, 0
 #define STRIP_MAX_H 4096        // the strip kernel keeps 64 columns of H bits in LDS (65 words per column at most)
-
-static inline bool bad_size(int H, int W) { return H <= 0 || W <= 0 || (long)H * (long)W >= (1L << 31); }
 #define MAX_MASKS 65535          // masks per call: they are the grid's second dimension
-static inline long words_of(int H, int W) { return ((long)H * W + 63) >> 6; }
 
 __device__ __forceinline__ u64 low_bits(int len) { return len < 64 ? (1ULL << len) - 1 : ~0ULL; }
 
@@ -215,13 +209,7 @@ __global__ __launch_bounds__(256) void trans_emit_kernel(const u64* __restrict__
 
 // ------------------------------------------------------------------------------------ pair intersections
 // one wave per (detection, ground truth): the boxes by rleToBbox's rule, then popcount(D & G) over the words of the
-// overlapping columns (contiguous in this layout); -1 marks a pair of disjoint boxes
-__device__ __forceinline__ void box_of(const int* __restrict__ r, int H, int& x, int& y, int& w, int& h) {
-  if (r[0] == 0) { x = y = w = h = 0; return; }
-  x = r[1]; w = r[2] - r[1] + 1;
-  if (r[5]) { y = 0; h = H; } else { y = r[3]; h = r[4] - r[3] + 1; }
-}
-
+// overlapping columns (contiguous in this layout); -1 marks a pair of disjoint boxes (box_of: maskwords.h)
 __global__ __launch_bounds__(256) void pair_kernel(const u64* __restrict__ dwords, const int* __restrict__ drec, int m,
                                                    const u64* __restrict__ gwords, const int* __restrict__ grec, int n, int H,
                                                    long nw, int* __restrict__ out) {

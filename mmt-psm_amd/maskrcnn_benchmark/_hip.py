@@ -6,6 +6,7 @@ autograd bookkeeping only; tensors cross the boundary as raw device pointers.
 """
 import ctypes
 import gc as _gc
+import math
 import weakref
 import os
 import threading as _threading
@@ -218,6 +219,9 @@ _SIGS = {
     "mmt_mask_transition_counts": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_mask_transition_positions": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "mmt_mask_pair_intersections": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "mmt_mask_nms_workspace": [c_int, c_void_p],
+    "mmt_mask_nms": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p,
+                     c_void_p, c_void_p],
     "mmt_polygon_mask_words_workspace": [c_int, c_int, c_int, c_void_p],
     "mmt_polygon_mask_words": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p,
                                c_void_p],
@@ -938,7 +942,7 @@ def _lib_raw():
 # pool, which keeps their addresses for the plan's life; its statistics slots from a block of the plan's own) and REPLAYED from then
 # on: ~70 ctypes calls instead of the Python that derives them (a manual graph: hipGraph replays of the two models serialise in
 # this runtime).  Only the input's address is patched.  Queries are not recorded.
-_NO_RECORD = frozenset(("mmt_polygon_mask_words_workspace", "mmt_conv_route", "mmt_conv_switches", "mmt_conv_wgrad_group_workspace",
+_NO_RECORD = frozenset(("mmt_polygon_mask_words_workspace", "mmt_mask_nms_workspace", "mmt_conv_route", "mmt_conv_switches", "mmt_conv_wgrad_group_workspace",
                         "mmt_conv_wgrad_route", "mmt_get_conv_precision", "mmt_packed_weight_elems", "mmt_set_conv_precision", "mmt_set_deterministic", "mmt_get_deterministic",
                         "mmt_stem_wgrad_ws_floats", "mmt_ciam_norm_lds_bytes", "mmt_ciam_norm_saved_floats", "mmt_ciam_norm_ws_floats"))
 LAYOUT_EPOCH = [0]    # bumped when a flat model (re)allocates its plane buffers (engine/flat.py)
@@ -3278,6 +3282,56 @@ def mask_pair_intersections(dwords, drec, gwords, grec, H, W):
     _check(lib().mmt_mask_pair_intersections(_p(dwords), _p(drec), m, _p(gwords), _p(grec), n, H, W, _p(out), _stream()),
            "mmt_mask_pair_intersections")
     return out
+
+
+# ---- mask NMS at inference (include/mmtpsm.h: mmt_mask_nms; csrc/masknms.hip)
+MASK_NMS_MAX = 1024                         # detections of one call
+MASK_NMS_MEASURES = {"iou": 0, "iomin": 1}  # the denominator: area_i + area_j - inter, or min(area_i, area_j)
+
+
+def mask_nms_threshold_q20(thresh):
+    """a threshold in (0, 1] as the library takes it: round(t * 2^20), halves up (0.3 acts as 314573 / 2^20)"""
+    t = float(thresh)
+    if not 0.0 < t <= 1.0:
+        raise RuntimeError("mask_nms: a threshold in (0, 1], not %r" % (thresh,))
+    q = int(math.floor(t * (1 << 20) + 0.5))   # (t * 2^20 is exact in binary floating point)
+    if q < 1:
+        raise RuntimeError("mask_nms: the threshold %r is below 2^-21 and quantises to zero" % (thresh,))
+    return q
+
+
+def mask_nms(words, rec, scores, labels, H, W, thresh, measure="iou", class_agnostic=False):
+    """greedy mask NMS over the D masks (words, rec) of one H x W image (mmt_mask_nms): walk the detections by descending score
+    (equal scores in row order); one is dropped when an earlier kept one of the same label (any label with class_agnostic)
+    overlaps it -- popcount(mask_i & mask_j) * 2^20 >= round(thresh * 2^20) * den, den = the union (measure "iou") or the smaller
+    area ("iomin"), all in integers.  -> (keep uint8 (D,) in row order, count int32 (1,)), both on the device; nothing is read
+    back.  What the library refuses raises RuntimeError here, before any launch"""
+    words, rec = _dev(words, "words"), _dev(rec, "rec")
+    scores, labels = _dev(scores, "scores"), _dev(labels, "labels")
+    H, W = int(H), int(W)
+    D = words.shape[0]
+    if measure not in MASK_NMS_MEASURES:
+        raise RuntimeError("mask_nms: measure %r is not one of %s" % (measure, sorted(MASK_NMS_MEASURES)))
+    tq = mask_nms_threshold_q20(thresh)
+    if D > MASK_NMS_MAX:
+        raise RuntimeError("mask_nms: %d detections, at most %d per call" % (D, MASK_NMS_MAX))
+    if H <= 0 or W <= 0 or H * W >= (1 << 31):
+        raise RuntimeError("masks of %d x %d: 0 < H * W < 2^31 only" % (H, W))
+    if (words.dtype != torch.int64 or words.dim() != 2 or words.shape[1] != (H * W + 63) // 64 or rec.dtype != torch.int32
+            or tuple(rec.shape) != (D, MASK_REC) or scores.numel() != D or labels.numel() != D):
+        raise RuntimeError("mask_nms: words int64 (D, ceil(H*W/64)), records int32 (D, %d), D scores and D labels" % MASK_REC)
+    order = torch.sort(scores.reshape(-1), descending=True, stable=True)[1].to(torch.int32)
+    labels = labels.reshape(-1).to(torch.int32).contiguous()
+    need = ctypes.c_int64(0)
+    if lib().mmt_mask_nms_workspace(D, ctypes.byref(need)) != 0:
+        raise RuntimeError("mmt_mask_nms_workspace refused %d detections" % D)
+    ws = torch.empty((max(int(need.value), 1),), dtype=torch.uint8, device=words.device)
+    keep = torch.empty((D,), dtype=torch.uint8, device=words.device)
+    count = torch.empty((1,), dtype=torch.int32, device=words.device)
+    _check(lib().mmt_mask_nms(_p(words.contiguous()), _p(rec.contiguous()), _p(order), _p(labels), D, H, W, tq,
+                              MASK_NMS_MEASURES[measure], 1 if class_agnostic else 0, _p(ws), int(need.value), _p(keep), _p(count),
+                              _stream()), "mmt_mask_nms")
+    return keep, count
 
 
 # ---- polygons at image size (include/mmtpsm.h: mmt_polygon_mask_words, mmt_mask_words_integral; csrc/polyfill.hip)

@@ -137,7 +137,10 @@ _DEFAULTS = {
               "PIXEL_MEAN": [102.9801, 115.9465, 122.7717], "PIXEL_STD": [1.0, 1.0, 1.0], "TO_BGR255": True},
     # TTA: multi-view inference (GeneralizedRCNN.forward_tta): TTA_VIEWS colour views per image (view 0 un-augmented), each followed
     # by its mirror image when TTA_FLIP; at most 8 views in all
-    "TEST": {"TTA": False, "TTA_FLIP": True, "TTA_VIEWS": 1},
+    # MASK_NMS: at inference, drop duplicate instances by the overlap of their pasted masks, behind the mask head (INTEGRATION.md,
+    # "Mask NMS at inference"): THRESH in (0, 1], MEASURE "iou" or "iomin" (intersection over the smaller mask)
+    "TEST": {"TTA": False, "TTA_FLIP": True, "TTA_VIEWS": 1,
+             "MASK_NMS": {"ENABLED": False, "THRESH": 0.5, "MEASURE": "iou", "CLASS_AGNOSTIC": False}},
     "DATALOADER": {"SIZE_DIVISIBILITY": 32},
     "DATASETS": {"NO_LABEL": True, "SYN": False},
     "SOLVER": {"BASE_LR": 0.005, "BIAS_LR_FACTOR": 2, "MOMENTUM": 0.9, "WEIGHT_DECAY": 0.0001,

@@ -15,7 +15,7 @@ from maskrcnn_benchmark.layers import Conv2d, ConvTranspose2d, fused
 from maskrcnn_benchmark.modeling.matcher import Matcher
 from maskrcnn_benchmark.modeling.poolers import Pooler
 from maskrcnn_benchmark.structures.bounding_box import BoxList
-from maskrcnn_benchmark.structures.boxlist_ops import boxlist_iou
+from maskrcnn_benchmark.structures.boxlist_ops import boxlist_iou, boxlist_mask_nms
 from maskrcnn_benchmark.structures.segmentation_mask import BinaryMaskList
 from maskrcnn_benchmark.utils.miscellaneous import dev_ints
 from maskrcnn_benchmark.modeling.relation.mask_relation_module import MaskRelationRefineNet
@@ -241,33 +241,51 @@ def make_roi_mask_loss_evaluator(cfg):
 
 
 class MaskPostProcessor(nn.Module):
-    """mask_head/inference.py:14-65: sigmoid prob of the predicted class, stored per image under 'mask'"""
+    """mask_head/inference.py:14-65: sigmoid prob of the predicted class, stored per image under 'mask'.
+    mask_nms: the TEST.MASK_NMS node, or None.  When it is enabled, every image's detections go through `boxlist_mask_nms` on
+    their M x M probabilities before the optional POSTPROCESS_MASKS paste, which then pastes the kept rows only.  Evaluation only:
+    the caller says so per call (`mask_nms=`: ROIMaskHead passes False on the teacher's passes), and a pseudo-mask masker or a
+    fixed-capacity list (`count_dev`) never takes it."""
 
-    def __init__(self, masker=None):
+    def __init__(self, masker=None, mask_nms=None):
         super().__init__()
         self.masker = masker
+        self.mask_nms = None
+        if mask_nms is not None and mask_nms.ENABLED:
+            if mask_nms.MEASURE not in H.MASK_NMS_MEASURES:
+                raise ValueError("TEST.MASK_NMS.MEASURE %r is not one of %s" % (mask_nms.MEASURE, sorted(H.MASK_NMS_MEASURES)))
+            if not 0.0 < float(mask_nms.THRESH) <= 1.0:
+                raise ValueError("TEST.MASK_NMS.THRESH %r is outside (0, 1]" % (mask_nms.THRESH,))
+            self.mask_nms = dict(thresh=float(mask_nms.THRESH), measure=mask_nms.MEASURE, class_agnostic=bool(mask_nms.CLASS_AGNOSTIC),
+                                 mask_threshold=getattr(masker, "threshold", 0.5))
 
-    def forward(self, x, boxes):
+    def forward(self, x, boxes, mask_nms=True):
         labels = torch.cat([b.get_field("labels") for b in boxes])
         per = [len(b) for b in boxes]
         if self.masker is not None and not isinstance(self.masker, DetectionMasker):
-            segs = self.masker(x, labels, boxes)
-        else:
-            prob = x.sigmoid()[torch.arange(x.shape[0], device=x.device), labels][:, None]
-            segs = prob.split(per, 0)
-            if self.masker is not None:   # POSTPROCESS_MASKS (inference.py:62-63): the same rows, pasted into their image
-                segs = self.masker(segs, boxes)
-        return self._with_masks(segs, boxes)
+            return self._with_masks(self.masker(x, labels, boxes), boxes)
+        prob = x.sigmoid()[torch.arange(x.shape[0], device=x.device), labels][:, None]
+        return self._finish(prob.split(per, 0), boxes, mask_nms)
 
-    def forward_prob(self, prob, boxes):
+    def forward_prob(self, prob, boxes, mask_nms=True):
         """forward() from the (D, 1, M, M) probabilities of the predicted class (test-time augmentation merges them over its views)"""
         if self.masker is not None and not isinstance(self.masker, DetectionMasker):
             raise NotImplementedError("the integral pseudo-mask is pasted from logits: probabilities go through the evaluation "
                                       "post-processor only")
-        segs = prob.split([len(b) for b in boxes], 0)
+        return self._finish(prob.split([len(b) for b in boxes], 0), boxes, mask_nms)
+
+    def _finish(self, segs, boxes, mask_nms):
+        """per-image (D, 1, M, M) probabilities -> the lists with their `mask` field: mask NMS when it applies, then the
+        POSTPROCESS_MASKS paste (inference.py:62-63: the same rows, pasted into their image)"""
+        if self.mask_nms is None or not mask_nms or any(getattr(b, "count_dev", None) is not None for b in boxes):
+            if self.masker is not None:
+                segs = self.masker(segs, boxes)
+            return self._with_masks(segs, boxes)
+        out = [boxlist_mask_nms(b, **self.mask_nms) for b in self._with_masks(segs, boxes)]
         if self.masker is not None:
-            segs = self.masker(segs, boxes)
-        return self._with_masks(segs, boxes)
+            for b, pasted in zip(out, self.masker([b.get_field("mask") for b in out], out)):
+                b.add_field("mask", pasted)
+        return out
 
     @staticmethod
     def _with_masks(segs, boxes):
@@ -352,7 +370,8 @@ class IntegralMask(object):
 
 def make_roi_mask_post_processor(cfg):
     return MaskPostProcessor(DetectionMasker(cfg.MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS_THRESHOLD, 1)
-                             if cfg.MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS else None)
+                             if cfg.MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS else None,
+                             mask_nms=cfg.TEST.MASK_NMS)
 
 
 def make_roi_mask_generator(cfg):
@@ -403,7 +422,8 @@ class ROIMaskHead(nn.Module):
         # the teacher produces a pseudo-mask is the concatenated logits, which is what `mask_logits` already is
         with torch.no_grad():
             if self.mode is None or self.mode == "train":
-                result = self.post_processor(mask_logits, proposals)
+                # (mask NMS belongs to evaluation: mode "train" is the teacher's second pass)
+                result = self.post_processor(mask_logits, proposals, mask_nms=self.mode is None)
             else:
                 result = self.mask_generator(mask_logits, proposals)
         return x, result, {}
@@ -431,7 +451,8 @@ class ROIMaskHead(nn.Module):
         with torch.no_grad():
             if D == 0:   # nothing to pool: empty fields, no launch
                 dev = detections[0].bbox.device
-                return self.post_processor.forward_prob(torch.zeros((0, 1, M, M), dtype=torch.float32, device=dev), detections), None
+                return self.post_processor.forward_prob(torch.zeros((0, 1, M, M), dtype=torch.float32, device=dev), detections,
+                                                        mask_nms=False), None
             mirrored = batch_boxlist_hflip_padded(detections, padded_width) if any(flips) else None
             boxes = []
             for f in flips:
@@ -441,7 +462,7 @@ class ROIMaskHead(nn.Module):
             logits = logits.contiguous().view(V, D, logits.shape[1], logits.shape[2], logits.shape[3])
             labels = torch.cat([d.get_field("labels") for d in detections])
             prob = H.tta_merge_mask(logits, labels, flips)
-            return self.post_processor.forward_prob(prob, detections), logits
+            return self.post_processor.forward_prob(prob, detections, mask_nms=self.mode is None), logits
 
 
 def build_roi_mask_head(cfg, is_student=False):

@@ -18,6 +18,24 @@ def boxlist_nms(boxlist, nms_thresh, max_proposals=-1, score_field="score"):
     return boxlist[keep].convert(mode)
 
 
+def boxlist_mask_nms(boxlist, thresh, measure="iou", class_agnostic=False, mask_threshold=0.5, score_field="scores"):
+    """Greedy NMS by MASK overlap on one BoxList whose `mask` field holds the (D, 1, M, M) probabilities of the predicted class:
+    the masks are pasted at the BoxList's size straight into mask words, `_hip.mask_nms` sweeps them by descending score (the
+    semantics: INTEGRATION.md, "Mask NMS at inference"), and the kept rows come back in their original order with every field
+    sliced alike.  The kept count is read back once -- the one host wait; zero detections return the list as it is"""
+    if len(boxlist) == 0:
+        return boxlist
+    from maskrcnn_benchmark import _hip as H
+    w, h = boxlist.size
+    words, rec = H.paste_mask_words(boxlist.get_field("mask"), boxlist.convert("xyxy").bbox, h, w, mask_threshold)
+    keep, count = H.mask_nms(words, rec, boxlist.get_field(score_field), boxlist.get_field("labels"), h, w, thresh, measure,
+                             class_agnostic)
+    n = int(count.item())
+    if n == len(boxlist):
+        return boxlist
+    return boxlist[torch.nonzero_static(keep, size=n).squeeze(1)]
+
+
 def remove_small_boxes(boxlist, min_size):
     wh = boxlist.convert("xywh").bbox
     keep = ((wh[:, 2] >= min_size) & (wh[:, 3] >= min_size)).nonzero().squeeze(1)
