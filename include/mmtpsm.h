@@ -105,6 +105,28 @@ int mmt_roi_align_maps_backward(const mmt_roi_maps* maps /*[host]*/, const float
 int mmt_nms_batched(const float* boxes, const int32_t* seg_off, int B, int max_n, float thr,
                     uint64_t* mask_ws, int32_t* keep, int32_t* keep_cnt, void* stream);
 
+/* ---------------------------------------------------------------- batched Soft-NMS (csrc/softnms.hip)
+ * The counterpart of mmt_nms_batched for B independent pre-sorted segments: a picked box decays the scores of its neighbours
+ * instead of removing them (Bodla et al. 2017).  Per segment, until nobody is left: pick the candidate with the largest
+ * CURRENT score (equal scores: the smaller position); stop if that score < min_score; otherwise it keeps that score, and every
+ * remaining candidate j with overlap ov (the IoU of mmt_nms_batched: "+1" areas, fp32, no contraction) gets
+ *   method 0 (linear):   s_j *= 1 - ov  when ov >= nms_thresh
+ *   method 1 (gaussian): s_j *= expf(-(ov * ov) / sigma)
+ * and an overlap that is not a number decays nothing.
+ *   boxes, scores  [total,4] xyxy / [total], each segment sorted by descending score
+ *   seg_off        int32 [B+1];  max_n <= 2048 upper bound on segment length
+ *   picked         int32 [B, max_n]: positions within the segment in pick order (= descending final score)
+ *   picked_cnt     int32 [B]
+ *   out_scores     [total]: every candidate's score when its segment stops (a picked one: its score when picked; one that was
+ *                  never decayed: its input score); may be the scores array itself
+ * One launch, one block per segment, no workspace, no atomics: the same bits on every run.  MMT_EINVAL before any launch for
+ * B < 0, max_n outside 0..2048, a method other than 0 or 1, sigma <= 0 or not finite (whatever the method), min_score or
+ * nms_thresh outside (0, 1], a null seg_off / picked_cnt, or (max_n > 0) any other null array.  B == 0 launches nothing; an
+ * empty segment writes its count 0. */
+int mmt_soft_nms_batched(const float* boxes, const float* scores, const int32_t* seg_off, int B, int max_n, int method,
+                         float nms_thresh, float sigma, float min_score, int32_t* picked, int32_t* picked_cnt, float* out_scores,
+                         void* stream);
+
 /* ---------------------------------------------------------------- input augmentation
  * replaces the PIL / torchvision calls behind data/transforms/transforms.py:28-205 (Resize, RandomHorizontalFlip,
  * AdjustBrightness, AdjustContrast, AdjustHue, RandomErasing, ToTensor, Normalize); images are uint8 [H][W][3] RGB on the
@@ -169,6 +191,14 @@ long mmt_det_workspace_bytes(int rows, int N, int nc);
 int mmt_det_postprocess(const float* prob, const float* boxes, const int32_t* row_off, const int32_t* row_off_host /*[host]*/,
                         int N, int nc, float score_thresh, float nms_thresh, int detections_per_img, void* workspace,
                         float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* out_cnt, void* stream);
+/* mmt_det_postprocess_soft: the same with mmt_soft_nms_batched in the place of mmt_nms_batched.  The picked candidates of a
+ *   class go out in ascending original row order with their DECAYED scores, the detections_per_img cut is taken on those.
+ *   Same outputs, same workspace query, same limits; besides what mmt_det_postprocess refuses, MMT_EINVAL before any launch for
+ *   what mmt_soft_nms_batched refuses (method, sigma, min_score, nms_thresh). */
+int mmt_det_postprocess_soft(const float* prob, const float* boxes, const int32_t* row_off, const int32_t* row_off_host /*[host]*/,
+                             int N, int nc, float score_thresh, float nms_thresh, int detections_per_img, int method, float sigma,
+                             float min_score, void* workspace, float* out_boxes, float* out_scores, int64_t* out_labels,
+                             int32_t* out_cnt, void* stream);
 /* mmt_rpn_post_select: after mmt_nms_batched over the N*L segments (keep [N*L,kmax], keep_cnt [N*L]): a kept candidate
  *   survives when its rank in its segment is < post_n and its position < own_pre[level] (rpn/inference.py:130-135); of the
  *   survivors the best fpn_post_n of the WHOLE BATCH (training: rpn/inference.py:223-234, written per image in (level,

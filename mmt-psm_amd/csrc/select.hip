@@ -959,9 +959,14 @@ extern "C" long mmt_det_workspace_bytes(int rows, int N, int nc) {
 // prob [rows][nc] / boxes [rows][nc * 4] of N images (row_off [N + 1], host copy row_off_host for the bounds) ->
 // out_boxes [N][capo][4], out_scores [N][capo], out_labels int64 [N][capo], out_cnt [N] with capo = max rows per image x (nc - 1).
 // Three kernels + the two of mmt_nms_batched, nothing read back.  Images of at most 2048 rows, nc <= 64.
-extern "C" int mmt_det_postprocess(const float* prob, const float* boxes, const int32_t* row_off, const int32_t* row_off_host,
-                                   int N, int nc, float score_thresh, float nms_thresh, int detections_per_img, void* workspace,
-                                   float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* out_cnt, void* stream) {
+// `soft`: null = greedy NMS (mmt_nms_batched); else {method, sigma, min_score} of mmt_soft_nms_batched, which decays the sorted
+// scores in place and writes its picks where the greedy sweep writes its kept positions -- det_finish_kernel orders the kept
+// positions of a class by row itself and cuts on the sorted scores, so it serves both
+struct DetSoft { int method; float sigma, min_score; };
+
+static int det_postprocess(const float* prob, const float* boxes, const int32_t* row_off, const int32_t* row_off_host, int N, int nc,
+                           float score_thresh, float nms_thresh, int detections_per_img, const DetSoft* soft, void* workspace,
+                           float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* out_cnt, void* stream) {
   if (!prob || !boxes || !row_off || !row_off_host || !workspace || !out_boxes || !out_scores || !out_labels || !out_cnt ||
       N < 1 || nc < 2 || nc > 64 || ((size_t)boxes & 15) || ((size_t)workspace & 15) || ((size_t)out_boxes & 15))
     return MMT_EINVAL;
@@ -970,6 +975,11 @@ extern "C" int mmt_det_postprocess(const float* prob, const float* boxes, const 
     const int R = row_off_host[n + 1] - row_off_host[n];
     if (R < 0 || R > 2048) return MMT_EINVAL;
     rmax = R > rmax ? R : rmax;
+  }
+  if (soft) {   // (B == 0: the parameter checks alone, nothing is launched)
+    const int e = mmt_soft_nms_batched(nullptr, nullptr, nullptr, 0, 0, soft->method, nms_thresh, soft->sigma, soft->min_score,
+                                       nullptr, nullptr, nullptr, stream);
+    if (e) return e;
   }
   const int rows = row_off_host[N] - row_off_host[0], F = nc - 1, B = N * F;
   hipStream_t s = (hipStream_t)stream;
@@ -993,10 +1003,32 @@ extern "C" int mmt_det_postprocess(const float* prob, const float* boxes, const 
   a.out_boxes = out_boxes; a.out_scores = out_scores; a.out_labels = (long*)out_labels; a.out_cnt = out_cnt;
   hipLaunchKernelGGL(det_sort_kernel, dim3(B), dim3(NT), 0, s, a);
   MMT_LAUNCH_CHECK();
-  if (hipMemsetAsync(keep_cnt, 0, (size_t)B * 4, s) != hipSuccess) return MMT_EINVAL;
-  const int e = mmt_nms_batched(a.sboxes, a.seg_off, B, rmax, nms_thresh, (uint64_t*)mask, keep, keep_cnt, stream);
-  if (e) return e;
+  if (soft) {
+    const int e = mmt_soft_nms_batched(a.sboxes, a.sscores, a.seg_off, B, rmax, soft->method, nms_thresh, soft->sigma,
+                                       soft->min_score, keep, keep_cnt, a.sscores, stream);
+    if (e) return e;
+  } else {
+    if (hipMemsetAsync(keep_cnt, 0, (size_t)B * 4, s) != hipSuccess) return MMT_EINVAL;
+    const int e = mmt_nms_batched(a.sboxes, a.seg_off, B, rmax, nms_thresh, (uint64_t*)mask, keep, keep_cnt, stream);
+    if (e) return e;
+  }
   hipLaunchKernelGGL(det_finish_kernel, dim3(N), dim3(NT), 0, s, a);
   MMT_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int mmt_det_postprocess(const float* prob, const float* boxes, const int32_t* row_off, const int32_t* row_off_host,
+                                   int N, int nc, float score_thresh, float nms_thresh, int detections_per_img, void* workspace,
+                                   float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* out_cnt, void* stream) {
+  return det_postprocess(prob, boxes, row_off, row_off_host, N, nc, score_thresh, nms_thresh, detections_per_img, nullptr, workspace,
+                         out_boxes, out_scores, out_labels, out_cnt, stream);
+}
+
+extern "C" int mmt_det_postprocess_soft(const float* prob, const float* boxes, const int32_t* row_off, const int32_t* row_off_host,
+                                        int N, int nc, float score_thresh, float nms_thresh, int detections_per_img, int method,
+                                        float sigma, float min_score, void* workspace, float* out_boxes, float* out_scores,
+                                        int64_t* out_labels, int32_t* out_cnt, void* stream) {
+  const DetSoft soft = {method, sigma, min_score};
+  return det_postprocess(prob, boxes, row_off, row_off_host, N, nc, score_thresh, nms_thresh, detections_per_img, &soft, workspace,
+                         out_boxes, out_scores, out_labels, out_cnt, stream);
 }

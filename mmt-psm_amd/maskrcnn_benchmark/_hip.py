@@ -116,6 +116,8 @@ _SIGS = {
     "mmt_roi_align_maps_forward": [ctypes.POINTER(RoiMaps), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_roi_align_maps_backward": [ctypes.POINTER(RoiMaps), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mmt_nms_batched": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mmt_soft_nms_batched": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                             c_void_p],
     "mmt_resample_u8": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "mmt_aug_views": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_float),
                       c_void_p, ctypes.c_long, c_int, c_int, c_void_p],
@@ -153,6 +155,8 @@ _SIGS = {
     "mmt_amax_stats": [c_void_p, ctypes.c_long, c_void_p, c_void_p],
     "mmt_det_postprocess": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_void_p,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mmt_det_postprocess_soft": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_float, c_float,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "mmt_position_embedding": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "mmt_sample_fg_bg_wide": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p],
@@ -1400,10 +1404,54 @@ def nms_batched(boxes, seg_off, max_n, thr):
     return keep, cnt
 
 
-def det_postprocess(prob, dec, per, score_thresh, nms_thresh, detections_per_img, zero_tails=False):
+SOFT_NMS_MAX = 2048                              # candidates of one segment (csrc/softnms.hip)
+SOFT_NMS_METHODS = {"linear": 0, "gaussian": 1}  # s *= 1 - ov where ov >= thr, or s *= exp(-ov^2 / sigma) everywhere
+
+
+def _soft_nms_args(what, method, nms_thresh, sigma, min_score):
+    """what mmt_soft_nms_batched refuses, refused here before any launch -> the method's number"""
+    if method not in SOFT_NMS_METHODS:
+        raise ValueError("%s: method %r is not one of %s" % (what, method, sorted(SOFT_NMS_METHODS)))
+    sigma, min_score, nms_thresh = float(sigma), float(min_score), float(nms_thresh)
+    if not (sigma > 0.0 and math.isfinite(sigma)):
+        raise ValueError("%s: sigma %r is not a positive finite number" % (what, sigma))
+    if not 0.0 < min_score <= 1.0:
+        raise ValueError("%s: min_score %r is outside (0, 1]" % (what, min_score))
+    if not 0.0 < nms_thresh <= 1.0:
+        raise ValueError("%s: nms_thresh %r is outside (0, 1]" % (what, nms_thresh))
+    return SOFT_NMS_METHODS[method]
+
+
+def soft_nms_batched(boxes, scores, seg_off, max_n, method="linear", nms_thresh=0.5, sigma=0.5, min_score=0.001):
+    """Soft-NMS of B pre-sorted segments in one launch (include/mmtpsm.h: mmt_soft_nms_batched).  boxes (T, 4) and scores (T,)
+    sorted by descending score within each segment; seg_off int32 (B + 1) on the device
+    -> picked (B, max_n) int32 positions within the segment in pick order, cnt (B,) int32, scores (T,) decayed -- or None when
+    max_n > 2048"""
+    m = _soft_nms_args("soft_nms_batched", method, nms_thresh, sigma, min_score)
+    if max_n < 0:
+        raise ValueError("soft_nms_batched: max_n %d" % max_n)
+    if max_n > SOFT_NMS_MAX:
+        return None
+    boxes = _dev(boxes).float().contiguous()
+    scores = _dev(scores).float().contiguous()
+    seg_off = _dev(seg_off).to(torch.int32).contiguous()
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or scores.dim() != 1 or scores.shape[0] != boxes.shape[0]:
+        raise ValueError("soft_nms_batched: boxes (T, 4) and scores (T,), not %s and %s" % (tuple(boxes.shape), tuple(scores.shape)))
+    B = seg_off.numel() - 1
+    picked = torch.empty((B, max_n), dtype=torch.int32, device=boxes.device)
+    cnt = torch.zeros((B,), dtype=torch.int32, device=boxes.device)
+    out = scores.clone()
+    if B > 0:
+        _check(lib().mmt_soft_nms_batched(_p(boxes), _p(scores), _p(seg_off), B, max_n, m, float(nms_thresh), float(sigma),
+                                          float(min_score), _p(picked), _p(cnt), _p(out), _stream()), "mmt_soft_nms_batched")
+    return picked, cnt, out
+
+
+def det_postprocess(prob, dec, per, score_thresh, nms_thresh, detections_per_img, zero_tails=False, soft=None):
     """PostProcessor.filter_results for a batch (prob (R, nc), dec (R, nc * 4), per = rows per image) on the device:
     -> boxes (N, cap, 4), scores (N, cap), labels int64 (N, cap), counts int32 (N,) -- or None when an image has more than
-    2048 rows / nc > 64 (the caller's tensor formulation takes those)"""
+    2048 rows / nc > 64 (the caller's tensor formulation takes those).  `soft`: (method number, sigma, min_score) of
+    det_postprocess_soft, which is this function with mmt_det_postprocess_soft as its entry"""
     N, nc = len(per), prob.shape[1]
     if N == 0 or nc < 2 or nc > 64 or max(per) > 2048 or prob.dtype != torch.float32:
         return None
@@ -1427,10 +1475,24 @@ def det_postprocess(prob, dec, per, score_thresh, nms_thresh, detections_per_img
     os_ = alloc((N, cap), dtype=torch.float32, device=dev)
     ol = alloc((N, cap), dtype=torch.int64, device=dev)
     oc = torch.empty((N,), dtype=torch.int32, device=dev)
-    _check(lib().mmt_det_postprocess(_p(prob), _p(dec), _p(row_off), ctypes.cast(host, c_void_p), N, nc, float(score_thresh),
-                                     float(nms_thresh), int(detections_per_img), _p(ws), _p(ob), _p(os_), _p(ol), _p(oc),
-                                     _stream()), "mmt_det_postprocess")
+    if soft is None:
+        _check(lib().mmt_det_postprocess(_p(prob), _p(dec), _p(row_off), ctypes.cast(host, c_void_p), N, nc, float(score_thresh),
+                                         float(nms_thresh), int(detections_per_img), _p(ws), _p(ob), _p(os_), _p(ol), _p(oc),
+                                         _stream()), "mmt_det_postprocess")
+    else:
+        _check(lib().mmt_det_postprocess_soft(_p(prob), _p(dec), _p(row_off), ctypes.cast(host, c_void_p), N, nc, float(score_thresh),
+                                              float(nms_thresh), int(detections_per_img), soft[0], float(soft[1]), float(soft[2]),
+                                              _p(ws), _p(ob), _p(os_), _p(ol), _p(oc), _stream()), "mmt_det_postprocess_soft")
     return ob, os_, ol, oc
+
+
+def det_postprocess_soft(prob, dec, per, score_thresh, nms_thresh, detections_per_img, method="linear", sigma=0.5, min_score=0.001,
+                         zero_tails=False):
+    """det_postprocess with Soft-NMS (mmt_det_postprocess_soft): the same outputs with DECAYED scores, the same None-when-out-of-
+    range contract; a method, sigma, min_score or nms_thresh that the library refuses raises ValueError before any launch"""
+    m = _soft_nms_args("det_postprocess_soft", method, nms_thresh, sigma, min_score)
+    return det_postprocess(prob, dec, per, score_thresh, nms_thresh, detections_per_img, zero_tails=zero_tails,
+                           soft=(m, sigma, min_score))
 
 
 # ------------------------------------------------------------------------------------------ test-time augmentation

@@ -107,7 +107,11 @@ _DEFAULTS = {
                 "FPN_POST_NMS_TOP_N_TRAIN": 2000, "FPN_POST_NMS_TOP_N_TEST": 1000, "RPN_HEAD": "SingleConvRPNHead"},
         "ROI_HEADS": {"USE_FPN": True, "FG_IOU_THRESHOLD": 0.5, "BG_IOU_THRESHOLD": 0.5,
                       "BBOX_REG_WEIGHTS": (10.0, 10.0, 5.0, 5.0), "BATCH_SIZE_PER_IMAGE": 512,
-                      "POSITIVE_FRACTION": 0.25, "SCORE_THRESH": 0.05, "NMS": 0.5, "DETECTIONS_PER_IMG": 200},
+                      "POSITIVE_FRACTION": 0.25, "SCORE_THRESH": 0.05, "NMS": 0.5, "DETECTIONS_PER_IMG": 200,
+                      # SOFT_NMS: at inference, a picked box decays the scores of its neighbours of the same class instead of
+                      # removing them ("Soft-NMS in the box head"); METHOD "linear" (x (1 - IoU) from IoU >= NMS)
+                      # or "gaussian" (x exp(-IoU^2 / SIGMA)); a candidate whose score fell below MIN_SCORE is dropped
+                      "SOFT_NMS": {"ENABLED": False, "METHOD": "linear", "SIGMA": 0.5, "MIN_SCORE": 0.001}},
         "ROI_BOX_HEAD": {"DO": 0.5, "K_HEAD": 1, "FEATURE_EXTRACTOR": "FPN2MLPFeatureExtractor",
                          "PREDICTOR": "FPNPredictor", "POOLER_RESOLUTION": 7, "POOLER_SAMPLING_RATIO": 2,
                          "POOLER_SCALES": (0.25, 0.125, 0.0625, 0.03125), "NUM_CLASSES": 3, "MLP_HEAD_DIM": 1024},

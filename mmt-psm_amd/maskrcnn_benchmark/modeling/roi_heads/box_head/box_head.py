@@ -4,6 +4,7 @@ hint adaptor) and the same three entry points: forward / forward_teacher / forwa
 
 Execution: 4-level ROIAlign in one launch -> fc6/fc7 on the fp32 MFMA GEMM with bias+ReLU(+dropout) in the
 epilogue -> cls_score and bbox_pred as ONE 15-wide GEMM; PSM loss as two small kernels."""
+import math
 import os
 
 import torch
@@ -301,18 +302,32 @@ def make_roi_box_loss_evaluator(cfg):
 
 class PostProcessor(nn.Module):
     """box_head/inference.py:11-145: softmax, decode, clip, per-class score threshold + NMS, keep top-k.
-    All (image, class) NMS problems of the batch go through one `mmt_nms_batched` call."""
+    All (image, class) NMS problems of the batch go through one `mmt_nms_batched` call.
 
-    def __init__(self, score_thresh=0.05, nms=0.5, detections_per_img=100, box_coder=None, cfg=None):
+    soft_nms: the MODEL.ROI_HEADS.SOFT_NMS node, or None.  When it is enabled, the post-processing goes through
+    `mmt_det_postprocess_soft` ("Soft-NMS in the box head") unless the caller says otherwise per call
+    (`soft_nms=`: ROIBoxHead passes False on the teacher's passes) or the lists are at fixed capacity (`defer_counts`, the
+    teacher's coarse inference).  Disabled, the node is not looked at and every call is what it was."""
+
+    def __init__(self, score_thresh=0.05, nms=0.5, detections_per_img=100, box_coder=None, cfg=None, soft_nms=None):
         super().__init__()
         self.score_thresh, self.nms, self.detections_per_img = score_thresh, nms, detections_per_img
         self.box_coder = box_coder if box_coder is not None else BoxCoder(weights=(10., 10., 5., 5.))
+        self.soft_nms = None
+        if soft_nms is not None and soft_nms.ENABLED:
+            if soft_nms.METHOD not in H.SOFT_NMS_METHODS:
+                raise ValueError("MODEL.ROI_HEADS.SOFT_NMS.METHOD %r is not one of %s" % (soft_nms.METHOD, sorted(H.SOFT_NMS_METHODS)))
+            if not (float(soft_nms.SIGMA) > 0.0 and math.isfinite(float(soft_nms.SIGMA))):
+                raise ValueError("MODEL.ROI_HEADS.SOFT_NMS.SIGMA %r is not a positive finite number" % (soft_nms.SIGMA,))
+            if not 0.0 < float(soft_nms.MIN_SCORE) <= 1.0:
+                raise ValueError("MODEL.ROI_HEADS.SOFT_NMS.MIN_SCORE %r is outside (0, 1]" % (soft_nms.MIN_SCORE,))
+            self.soft_nms = soft_nms
 
-    def forward(self, x, boxes):
+    def forward(self, x, boxes, soft_nms=True):
         class_logits, box_regression = x
-        return self.forward_prob(F.softmax(class_logits, -1), box_regression, boxes)
+        return self.forward_prob(F.softmax(class_logits, -1), box_regression, boxes, soft_nms=soft_nms)
 
-    def forward_prob(self, prob, box_regression, boxes):
+    def forward_prob(self, prob, box_regression, boxes, soft_nms=True):
         """forward() from class PROBABILITIES (R, C) instead of logits: everything behind the softmax, the same calls in the same
         order (test-time augmentation hands in the probabilities and regressions merged over its views)"""
         per = [len(b) for b in boxes]
@@ -336,7 +351,12 @@ class PostProcessor(nn.Module):
         # device (mmt_det_postprocess: five launches), ONE read-back (the detection counts) for the BoxList sizes.  The tensor
         # formulation it replaced is its checker (tests/tensor_formulations.py::det_filter_results)
         defer = getattr(self, "defer_counts", False)
-        out = H.det_postprocess(prob, dec, per, self.score_thresh, self.nms, self.detections_per_img, zero_tails=defer)
+        if self.soft_nms is not None and soft_nms and not defer:
+            sn = self.soft_nms
+            out = H.det_postprocess_soft(prob, dec, per, self.score_thresh, self.nms, self.detections_per_img, method=sn.METHOD,
+                                         sigma=sn.SIGMA, min_score=sn.MIN_SCORE)
+        else:
+            out = H.det_postprocess(prob, dec, per, self.score_thresh, self.nms, self.detections_per_img, zero_tails=defer)
         if out is None:
             raise RuntimeError("PostProcessor: at most 2048 proposals per image and 64 classes (mmt_det_postprocess is the only "
                                "implementation)")
@@ -379,7 +399,8 @@ def resolve_counts(boxlists):
 
 def make_roi_box_post_processor(cfg):
     r = cfg.MODEL.ROI_HEADS
-    return PostProcessor(r.SCORE_THRESH, r.NMS, r.DETECTIONS_PER_IMG, BoxCoder(weights=r.BBOX_REG_WEIGHTS), cfg=cfg)
+    return PostProcessor(r.SCORE_THRESH, r.NMS, r.DETECTIONS_PER_IMG, BoxCoder(weights=r.BBOX_REG_WEIGHTS), cfg=cfg,
+                         soft_nms=r.SOFT_NMS)
 
 
 class ROIBoxHead(nn.Module):
@@ -409,7 +430,8 @@ class ROIBoxHead(nn.Module):
         if not self.training:
             if not self.use_realation_nms:  # with IR-Net the relation module replaces score-threshold + greedy NMS
                 with torch.no_grad():
-                    proposals = self.post_processor((class_logits, box_regression), proposals)
+                    # (Soft-NMS, when configured, is for evaluation: never on a teacher's pass, as ROIMaskHead's mask NMS)
+                    proposals = self.post_processor((class_logits, box_regression), proposals, soft_nms=self.mode is None)
             return x, proposals, {}, class_logits, box_regression
         lc, lb = self.loss_evaluator([class_logits], [box_regression])
         return x, proposals, dict(loss_classifier=lc, loss_box_reg=lb), class_logits, box_regression
