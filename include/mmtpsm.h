@@ -333,6 +333,17 @@ int mmt_box_loss(const float* logits, const float* breg, const int64_t* labels, 
  * the number of rows with label >= 0; NULL = R, i.e. mmt_box_loss) */
 int mmt_box_loss_rows(const float* logits, const float* breg, const int64_t* labels, const float* regt, int R, int NC,
                       const int64_t* n_rows, float* out, float* dlogits, float* dbreg, void* stream);
+/* mmt_match_targets: ground-truth assignment of the candidates (anchors / proposals) of all N images of a batch (reference
+ * boxlist_iou + Matcher + the label rules of rpn/loss.py and box_head/loss.py + BoxCoder.encode).  cand [A_total][4], or with
+ * shared_cand one grid [A][4] that every image uses; cand_off / gt_off [N + 1]: image n owns candidates cand_off[n] ..
+ * cand_off[n + 1] and ground-truth boxes gt_off[n] .. gt_off[n + 1] of gt [G_total][4] / gt_labels [G_total].  Per candidate:
+ * matches = index (inside its image) of the first ground-truth box of maximal IoU, -1 below `low`, -2 in [low, high); with
+ * allow_low_quality (top_ws [max(G_total, 1)], cleared here) a candidate that is some box's best keeps its index.  Optional
+ * outputs: labels_f (1 matched, 0 background, -1 between the thresholds or not `visible`), labels_i (class of the matched box,
+ * 0 background, -1 between), reg [A_total][4] = encode(matched box -- box 0 of the image for the unmatched --, candidate).
+ * An image WITHOUT ground truth (gt_off[n] == gt_off[n + 1]) is all background: matches -1, labels_f 0 (-1 where not visible),
+ * labels_i 0, reg 0, and nothing outside the image's own (empty) range of gt / gt_labels is read; with G_total == 0 gt and
+ * gt_labels may be NULL.  An image without candidates writes nothing. */
 int mmt_match_targets(const float* cand, const int32_t* cand_off, const float* gt, const int32_t* gt_off,
                       const int64_t* gt_labels, const uint8_t* visible, int N, int A_total, int G_total, int shared_cand,
                       float high, float low, int allow_low_quality, float wx, float wy, float ww, float wh, uint32_t* top_ws,

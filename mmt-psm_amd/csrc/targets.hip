@@ -88,6 +88,8 @@ __global__ __launch_bounds__(256) void match_kernel(const float* __restrict__ ca
   if (best < low) m = -1;                                  // Matcher.BELOW_LOW_THRESHOLD
   else if (best < high) m = -2;                            // Matcher.BETWEEN_THRESHOLDS
   if (top != nullptr && is_best) m = arg;                  // allow_low_quality_matches (matcher.py:118-139)
+  const bool none = g1 <= g0;                              // an image without ground truth: all background, gt[g0] is not the image's
+  if (none) m = -1;
   matches[a] = m;
   const int mi = m < 0 ? 0 : m;
   if (labels_f != nullptr) {                               // RPN: 1 matched, 0 background, -1 ignored / not visible
@@ -97,12 +99,15 @@ __global__ __launch_bounds__(256) void match_kernel(const float* __restrict__ ca
     labels_f[a] = l;
   }
   if (labels_i != nullptr) {                               // box head: class of the matched gt, 0 background, -1 ignored
-    int64_t l = gt_labels[g0 + mi];
+    int64_t l = none ? 0 : gt_labels[g0 + mi];
     if (m == -1) l = 0;
     if (m == -2) l = -1;
     labels_i[a] = l;
   }
-  if (reg != nullptr) {                                    // BoxCoder.encode(gt[mi], candidate)
+  if (reg != nullptr && none) {
+    float* o = reg + (long)a * 4;
+    o[0] = o[1] = o[2] = o[3] = 0.f;
+  } else if (reg != nullptr) {                             // BoxCoder.encode(gt[mi], candidate)
     const float* gb = gt + (long)(g0 + mi) * 4;
     const float pw = c2 - c0 + 1.f, ph = c3 - c1 + 1.f;
     const float px = c0 + 0.5f * pw, py = c1 + 0.5f * ph;
@@ -258,7 +263,9 @@ extern "C" int mmt_match_targets(const float* cand, const int32_t* cand_off, con
                                  int shared_cand, float high, float low, int allow_low_quality, float wx, float wy, float ww,
                                  float wh, uint32_t* top_ws, int32_t* matches, float* labels_f, int64_t* labels_i, float* reg,
                                  void* stream) {
-  if (!cand || !cand_off || !gt || !gt_off || !matches || N < 1 || (labels_i && !gt_labels)) return MMT_EINVAL;
+  // (a batch without any ground truth, G_total == 0, reads neither gt nor gt_labels: match_kernel's `none`)
+  if (!cand || !cand_off || !gt_off || !matches || N < 1 || G_total < 0 || (G_total > 0 && (!gt || (labels_i && !gt_labels))))
+    return MMT_EINVAL;
   if (allow_low_quality && !top_ws) return MMT_EINVAL;
   if (A_total <= 0) return 0;
   hipStream_t s = (hipStream_t)stream;
